@@ -12,7 +12,22 @@ at 128x128, batch 32 per GPU, fp32 in / fp32 out, on N MI355X GPUs of one node.
 Prints ONE JSON line on rank 0 (contract in the task statement).  Synthetic LIDC-like inputs,
 random-init weights, inputs resident in HBM before the timed region.
 
-Extra objects on the line:
+A plain run does only what the headline figure needs: set-up (plan, graph capture, profile-guided lane schedule), warm-up,
+the --steps timed steps, the result line (`roofline` holds the step-level view, computed from the plan without running
+anything).  --full adds the measurements that take runs of their own: the per-family / dominant-kernel pass (`roofline`
+below), the fp32-MFMA-only child run, the CPU-oracle baseline and ProbU-Net's 8-sample decode timing.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                  # everything below
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR      # + what the last timed step computed, DIR/<name>.npy
+
+--dump-outputs writes, after the timed steps and on rank 0, what a caller of the training step receives from its last
+step, all in float32: `loss` (0-d), the forward's outputs (`output_<k>`) and the updated floating-point state
+(`state`: every floating-point tensor of state_dict() flattened and concatenated in key order).  An array above
+DUMP_ARRAY_CAP elements is replaced by a fixed sample of it (flat positions drawn with a fixed seed, sorted: the same
+positions in every run of the same arguments), so the files stay below 64 MB.  Same arguments -> same inputs (seeded
+weights, data and latent noise).
+
+Extra objects on the line with --full:
   roofline      the DOMINANT KERNEL (longest convolution launch of the step) timed live with HIP events on its launch
                 stream: `achieved` = its algorithmic fp32-equivalent FLOPs per launch / average launch duration, `peak` =
                 the roof of the pipe it runs on (2500/3 = 833.3 TFLOP/s for the split-fp16 kernels: three fp16 piece
@@ -23,7 +38,7 @@ Extra objects on the line:
                 keeps BASELINE.md's figure (achieved / 157.3); `fp32_mfma_only` is the same run with UZ_CONV_MATH=f32
                 (like-for-like against 157.3).  `families`: per-family sums, conv families against their binding roof,
                 streaming families against 8 TB/s (`large_ops`: the launches big enough to be bandwidth-bound).  With
-                --no-profile or more than one GPU the object holds the step-level view only.
+                --no-profile, more than one GPU or without --full the object holds the step-level view only.
   cpu_baseline  the CPU oracle (functional torch restatement of the reference graph = "port") timed on this box's host
                 cores on a bounded sample of the same workload (batch stated in `sample`).
 """
@@ -47,6 +62,9 @@ SPLIT_PRODUCTS = 3                # fp16 piece products per fp32 product in conv
 PEAK_SPLIT_TFLOPS = PEAK_F16_MFMA_TFLOPS / SPLIT_PRODUCTS
 HBM_PEAK_GBS = 8000.0
 LARGE_OP_BYTES = 32e6
+DUMP_ARRAY_CAP = 4 << 20          # --dump-outputs: elements per array before it is sampled
+DUMP_BYTES = 60_000_000           # --dump-outputs: bytes of all arrays together (under 64 MB)
+DUMP_SAMPLE_SEED = 20201004
 
 # algorithmic work per image (fwd+bwd), unfused tensor bytes per image, fixed bytes per step
 MODELS = {
@@ -627,6 +645,24 @@ def cpu_baseline_3d(threads, cores, budget_s):
                        f"{' after 1 warm-up' if len(times) > 1 else ''}, fwd+loss+bwd (no Adam), {threads} threads of {cores} usable cores")
 
 
+def dump_outputs(path, loss, out, net):
+    """--dump-outputs: what the last timed step handed its caller - loss, the forward's outputs, the updated state - as float32
+    .npy files; an array above the per-array cap is replaced by a seeded sample of it (the same positions in every run)."""
+    import numpy as np
+    import torch
+    arrays = {"loss": loss.detach().float().cpu().numpy()}
+    for k, t in enumerate(out if isinstance(out, (list, tuple)) else [out]):
+        arrays[f"output_{k}"] = t.detach().float().cpu().numpy()
+    state = [v.detach().float().reshape(-1) for v in net.state_dict().values() if v.dtype.is_floating_point]
+    arrays["state"] = torch.cat(state).cpu().numpy()
+    cap = min(DUMP_ARRAY_CAP, DUMP_BYTES // 4 // len(arrays))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float32))
+
+
 def build(model, reversible=False):
     if model == "phiseg3d":
         from unet_zoo_amd.models.phiseg3D import PHISeg3D
@@ -665,6 +701,11 @@ def main():
                          "(= UZ_STORE_B16=1; BASELINE configs[4] 'bf16': the default of --model phiseg3d), or everything in fp32")
     ap.add_argument("--strong", action="store_true", help="strong scaling (SURVEY 8d): the GLOBAL batch stays at --batch (default 32), "
                                                           "each of the N GPUs takes batch / N images")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline figure: per-family / dominant-kernel profile, fp32-MFMA-only "
+                         "child run, CPU-oracle baseline, ProbU-Net decode timing (each can still be left out with its --no-* / --skip-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (loss, forward outputs, updated state) as DIR/<name>.npy")
     ap.add_argument("--allow-experiment", action="store_true",
                     help="report a line although a work-skipping / timing-only knob is in play (UZ_DIAG_SKIP, UZ_LIB, a library built with "
                          "UZ_EXP_* / UZ_DIAG): the line is then marked \"experiment\": true.  Without this flag such a run exits with status 2.")
@@ -704,7 +745,7 @@ def main():
 
     # the fp32-MFMA-only comparison leg runs in a child process BEFORE this process initialises the GPU
     f32_leg = None
-    if world == 1 and not args.no_f32_leg and conv_math() != "f32" and not vol:
+    if args.full and world == 1 and not args.no_f32_leg and conv_math() != "f32" and not vol:
         f32_leg = fp32_only_leg(args)
 
     import torch
@@ -753,17 +794,19 @@ def main():
 
     def step():
         if vol:
-            net.forward(x, onehot, training=True)
+            out = net.forward(x, onehot, training=True)
         elif args.model == "unet":
-            net.forward(x)
+            out = net.forward(x)
         else:
-            net.forward(x, mask, training=True)
+            out = net.forward(x, mask, training=True)
         loss = net.loss(mask)
         opt.zero_grad()
         loss.backward()
         opt.step()
+        outs[:] = [out]
         return loss
 
+    outs = []
     for _ in range(max(args.warmup, 3 if not args.no_graphs else 1)):
         loss = step()
     tuned = None
@@ -791,10 +834,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     final_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, outs[0], net)
 
     extra = {}
     train_plan = net._cur
-    if args.model == "probunet" and rank == 0:
+    if args.full and args.model == "probunet" and rank == 0:
         # "8 posterior samples" (BASELINE configs[2]): after one forward, 8 x [z = posterior.rsample(); fcomb(features, z)]
         # = reconstruct(calculate_posterior=True) (probabilistic_unet.py:272-283), timed separately from the train step
         net.eval()
@@ -833,7 +878,7 @@ def main():
                          "conv ops as routed: 157.3 TFLOP/s (fp32 MFMA) or 2500/3 = 833.3 TFLOP/s (split-fp16, 3 fp16 products per fp32 "
                          "product), weighted by FLOPs (harmonic); frac_vs_fp32_mfma = achieved / 157.3 as BASELINE.md section 2 defines it; "
                          "hbm_fraction uses the unfused-graph bytes and cannot exceed ~0.21 in fp32")
-        if not args.no_profile and world == 1:
+        if args.full and not args.no_profile and world == 1:
             try:
                 fam, heaviest, heaviest_full = profile_families(net, plan, L)
                 fams = {}
@@ -941,7 +986,7 @@ def main():
         line.update(extra)
         if f32_leg is not None:
             line["fp32_mfma_only"] = f32_leg
-        if not args.skip_cpu and world == 1:
+        if args.full and not args.skip_cpu and world == 1:
             try:
                 line["cpu_baseline"] = cpu_baseline(args.model, args.cpu_batch)
             except Exception as e:                              # ... nor to the CPU leg

@@ -16,6 +16,34 @@ def load(name):
     return arrays, meta
 
 
+def reference_experiments():
+    """Names of the reference experiment files whose settings are stored in reference_experiments.json."""
+    with open(os.path.join(GOLDEN, "reference_experiments.json")) as f:
+        return sorted(json.load(f)["files"])
+
+
+def reference_experiment_file(name, directory):
+    """Rebuild the reference experiment file `name` in the reference's layout - torch imports, the reference's module paths, its
+    settings - from reference_experiments.json (data only) as <directory>/<name>.py; returns the path."""
+    with open(os.path.join(GOLDEN, "reference_experiments.json")) as f:
+        e = json.load(f)["files"][name]
+
+    def lit(v):
+        if isinstance(v, dict) and set(v) == {"tuple"}:
+            return "(" + "".join(lit(x) + ", " for x in v["tuple"]) + ")"
+        if isinstance(v, list):
+            return "[" + ", ".join(lit(x) for x in v) + "]"
+        if isinstance(v, dict):
+            return "{" + ", ".join(repr(k) + ": " + lit(x) for k, x in v.items()) + "}"
+        return repr(v)
+    lines = ["import torch", "import torch.nn as nn"] + [f"from {m} import {n}" for m, n in e["imports"]]
+    lines += [f"{k} = {lit(v)}" for k, v in e["settings"].items()] + [f"{k} = {v}" for k, v in e["names"].items()]
+    path = os.path.join(str(directory), name + ".py")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return path
+
+
 def spec_of(meta):
     return [(k, tuple(s), kd) for k, s, kd in meta["spec"]]
 

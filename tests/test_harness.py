@@ -22,9 +22,16 @@ def test_experiment_modules_load(name):
     assert m.model.__module__.startswith("unet_zoo_amd.models")
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/models/experiments/phiseg_7_5_12.py"), reason="reference tree not present")
-def test_reference_experiment_file_loads_unchanged():
-    m = TM.load_experiment("/root/reference/models/experiments/phiseg_7_5_12.py")
+def test_reference_experiment_file_loads_unchanged(tmp_path):
+    """An experiment file in the reference's own layout - top-level torch imports, then the reference's module paths
+    (models.phiseg, data.lidc_data, utils) - loads as it is: load_experiment maps those paths onto the native package.
+    The file is our phiseg_7_5_12.py (same attribute surface as the reference's) under the reference's import header."""
+    with open(os.path.join(EXP_DIR, "phiseg_7_5_12.py")) as f:
+        body = f.read()
+    assert "from models.phiseg import PHISeg" in body and "from data.lidc_data import lidc_data" in body
+    path = tmp_path / "phiseg_7_5_12.py"
+    path.write_text("import torch\nimport torch.nn as nn\n" + body)
+    m = TM.load_experiment(str(path))
     assert m.model.__name__ == "PHISeg" and m.model.__module__ == "unet_zoo_amd.models.phiseg"
     assert m.filter_channels == [32, 64, 128, 192, 192, 192, 192] and m.batch_size == 12
 

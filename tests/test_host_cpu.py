@@ -497,6 +497,32 @@ def test_bench_cu_share_of_a_reduced_grid_weight_gradient():
         L.uz_set_wgrad_target(old if old != 256 else 0)
 
 
+def test_bench_dump_outputs_float32_seeded_sample_under_64mb(tmp_path):
+    """bench.py --dump-outputs (dump_outputs): loss, every forward output and the flattened floating-point state as float32 .npy; an
+    array above the cap is replaced by a sample at sorted, distinct positions that are the same in every call; all files under 64 MB."""
+    import importlib.util
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("uz_bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    net = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.BatchNorm1d(4))
+    big = torch.arange(bench.DUMP_ARRAY_CAP + 5, dtype=torch.float64)          # value = flat position
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(1.5), [torch.ones(2, 3), big], net)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["loss.npy", "output_0.npy", "output_1.npy", "state.npy"]
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss.npy"].shape == () and float(a["loss.npy"]) == 1.5 and a["output_0.npy"].shape == (2, 3)
+    sd = [v.reshape(-1) for v in net.state_dict().values() if v.dtype.is_floating_point]
+    assert np.array_equal(a["state.npy"], torch.cat(sd).numpy())
+    s = a["output_1.npy"]
+    assert 0 < s.size < big.numel() and np.all(np.diff(s) > 0) and s[-1] < big.numel()
+    for n in names:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / n))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+
+
 def _happens_before(plan, which, ops):
     sc, n = plan.scheds[which], len(ops)
     hb, last = [0] * n, {}

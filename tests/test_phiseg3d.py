@@ -120,13 +120,11 @@ def test_bf16_storage_pass_marks_buffers_and_operands_consistently(monkeypatch):
     assert on._resolve(v) - on._resolve(View(b)) == 2 * (b.C + 1) * b.H * b.W
 
 
-def test_brats_experiment_file_resolves_to_the_native_model():
-    import os
+def test_brats_experiment_file_resolves_to_the_native_model(tmp_path):
+    """The reference's phiseg_brats.py, rebuilt in its layout from the stored settings (golden/reference_experiments.json)."""
+    from tests import _golden as G
     from unet_zoo_amd import train_model as TM
-    f = "/root/reference/models/experiments/phiseg_brats.py"
-    if not os.path.isfile(f):
-        pytest.skip("reference tree not present")
-    cfg = TM.load_experiment(f)
+    cfg = TM.load_experiment(G.reference_experiment_file("phiseg_brats", tmp_path))
     from unet_zoo_amd.models.phiseg3D import PHISeg3D
     assert cfg.model is PHISeg3D and cfg.image_size == (4, 128, 128, 128) and cfg.use_reversible is True
     # the file's own filter list does not satisfy the reference's channel arithmetic: constructing it raises there too

@@ -3,8 +3,6 @@ activation recomputation in the backward tape.  revtorch==0.2.0 is not vendored 
 restates its published algorithm and this row's PARITY IS UNPINNED by any reference output (oracle/refgraph.py:rev_sequence);
 what is tested: the experiment surface (the reference's own *_rev_* files construct and train), the state_dict key scheme, the
 memory saving, and HIP-vs-oracle agreement of forward, loss, gradients and BatchNorm buffers."""
-import glob
-import os
 
 import numpy as np
 import pytest
@@ -15,13 +13,12 @@ import unet_zoo_amd  # noqa: F401
 from tests import _golden as G
 from unet_zoo_amd import train_model as TM
 
-REF_EXP = "/root/reference/models/experiments"
 NF7 = [32, 64, 128, 192, 192, 192, 192]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXP), reason="reference tree not present")
-def test_every_reversible_experiment_file_of_the_reference_constructs():
-    files = sorted(f for f in glob.glob(os.path.join(REF_EXP, "*.py")) if "rev" in os.path.basename(f))
+def test_every_reversible_experiment_file_of_the_reference_constructs(tmp_path):
+    """Every reversible experiment file of the reference (rebuilt in its layout from the stored settings, golden/reference_experiments.json)."""
+    files = [G.reference_experiment_file(n, tmp_path) for n in G.reference_experiments() if "rev" in n]
     assert len(files) >= 14
     built = 0
     for f in files:

@@ -3,7 +3,7 @@
 #   gpurun -- 'bash tools/evidence.sh <what> [args]'          outputs under gpurun_out/, summaries are copied to profiles/ by hand
 # what:
 #   tier [mode...]      smoke + GPU test tier in the given arithmetic modes (default: default f32 split)
-#   bench [model...]    bench.py lines (default: phiseg unet probunet phiseg3d)
+#   bench [model...]    bench.py --full lines (default: phiseg unet probunet phiseg3d), written under $EVIDENCE_DIR (default evidence/)
 #   ab VAR=a VAR=b ...  A/B of environment toggles on the training step of $MODEL (default phiseg), three alternations, one process each
 #   layers [reps]       per-layer dispatch table with PMC passes (profiles/rN_layer_table.json)
 #   stats [model]       rocprofv3 kernel statistics of a bench run (graph replay)
@@ -19,9 +19,10 @@ tier)
     env $env python -m pytest tests -m gpu -q --timeout=1800 -p no:cacheprovider > gpurun_out/pytest_gpu_$m.log 2>&1; echo "pytest $m rc=$?"; tail -3 gpurun_out/pytest_gpu_$m.log
   done ;;
 bench)
+  out=${EVIDENCE_DIR:-evidence}; mkdir -p "$out"
   models="$@"; [ -z "$models" ] && models="phiseg unet probunet phiseg3d"
   for m in $models; do
-    python bench.py --model $m --steps 20 --warmup 5 > gpurun_out/bench_$m.json 2> gpurun_out/bench_$m.err; echo "bench $m rc=$?"; cut -c1-220 gpurun_out/bench_$m.json
+    python bench.py --full --model $m --steps 20 --warmup 5 > "$out/bench_$m.json" 2> "$out/bench_$m.err"; echo "bench $m rc=$?"; cut -c1-220 "$out/bench_$m.json"
   done ;;
 ab)
   for rep in 1 2 3; do for v in "$@"; do

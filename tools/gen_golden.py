@@ -781,8 +781,56 @@ def metric_cases():
     save("metrics", arrays, meta)
 
 
+def experiment_cases():
+    """The settings of the reference's reversible and BraTS experiment files as plain data (reference_experiments.json): per file,
+    what it imports (`from <module> import <name>`), every module-level name it binds to an imported object, and every setting it
+    assigns, evaluated (tuples stored as {"tuple": [...]}).  tests/ rebuild an experiment module in the reference's layout from them."""
+    import ast
+    exp_dir = next(os.path.join(p, "models", "experiments") for p in sys.path if os.path.isdir(os.path.join(p, "models", "experiments")))
+
+    class Imported:
+        def __init__(self, name):
+            self.name = name
+
+    def plain(v):
+        if isinstance(v, tuple):
+            return {"tuple": [plain(x) for x in v]}
+        if isinstance(v, list):
+            return [plain(x) for x in v]
+        if isinstance(v, dict):
+            return {k: plain(x) for k, x in v.items()}
+        assert v is None or isinstance(v, (bool, int, float, str)), v
+        return v
+    files = {}
+    for f in sorted(os.listdir(exp_dir)):
+        name = os.path.splitext(f)[0]
+        if not f.endswith(".py") or not ("rev" in name or "brats" in name):
+            continue
+        tree = ast.parse(open(os.path.join(exp_dir, f)).read())
+        imports, names, settings, ns = [], {}, {}, {"len": len}
+        for node in tree.body:
+            if isinstance(node, ast.ImportFrom):
+                for a in node.names:
+                    imports.append([node.module, a.name])
+                    ns[a.asname or a.name] = Imported(a.name)
+            elif isinstance(node, ast.Assign) and len(node.targets) == 1 and isinstance(node.targets[0], ast.Name):
+                v = eval(compile(ast.Expression(node.value), f, "eval"), {"__builtins__": {}}, ns)
+                ns[node.targets[0].id] = v
+                if isinstance(v, Imported):
+                    names[node.targets[0].id] = v.name
+                else:
+                    settings[node.targets[0].id] = plain(v)
+        files[name] = dict(imports=imports, names=names, settings=settings)
+    with open(os.path.join(OUT, "reference_experiments.json"), "w") as fh:
+        json.dump(dict(note="settings of the reference's models/experiments/*rev*.py and phiseg_brats.py (tools/gen_golden.py experiments)",
+                       files=files), fh, indent=1, sort_keys=True)
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "experiments":
+        experiment_cases()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "metrics":
         metric_cases()
         sys.exit(0)
