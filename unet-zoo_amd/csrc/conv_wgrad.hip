@@ -163,9 +163,10 @@ __global__ __launch_bounds__(NT, 2) void wgrad_kernel(const WgP p) {
         __syncthreads();
         if (tn < p.T) gload(tn, cur ^ 1);      // in flight during the MFMA loop below
         {
-            // pixel pair (2s, 2s+1): the second pixel sits one word to the right (or one image further when TW == 1)
+            // pixel pair (2s, 2s+1): the second pixel sits one word to the right, or when TW == 1 one patch row down (TH > 1) or
+            // one image further (TH == 1)
             const float* Ab = dYl + (wm * 32 + l31) * p.PTP + h;
-            const float* Bb = Xl + (wn * 32 + l31) * p.PSP + (p.TW > 1 ? h : h * p.PSI);
+            const float* Bb = Xl + (wn * 32 + l31) * p.PSP + (p.TW > 1 ? h : h * (p.TH > 1 ? p.PW : p.PSI));
             auto mma_loop = [&](auto ntap_c, auto tap0_c) {
                 constexpr int NTAP = decltype(ntap_c)::value, TAP0 = decltype(tap0_c)::value;
 #pragma unroll 4
