@@ -326,7 +326,9 @@ def test_unet_plan_folds_the_relu_backward_into_the_last_writer_of_dA(monkeypatc
     n_units = sum(o["code"] == "UZ_OP_CONV_FWD" and o["i"][8] == 1 for o in plan.fwd_ops)          # convolutions with the fused forward ReLU
     assert n_units == 21
     assert count(plan, "UZ_OP_RELU_BWD") == 1 and count(plan, "UZ_OP_CHAN_SUM_TABLE") == 1 and count(plan, "UZ_OP_CHAN_SUM_PARTIALS") == 0
-    folded = [o for o in plan.bwd_ops if o["code"] in ("UZ_OP_CONV_BWD_DATA", "UZ_OP_AVGPOOL_BWD", "UZ_OP_BILINEAR_BWD") and len(o["p"]) > 7 - 5 * (o["code"] != "UZ_OP_CONV_BWD_DATA")]
+    # (the folded forms carry the unit's activation and the bias-gradient partials: CONV_BWD_DATA p[7] / p[8], pooling and interpolation p[2] / p[3])
+    folded = [o for o in plan.bwd_ops if o["code"] in ("UZ_OP_CONV_BWD_DATA", "UZ_OP_AVGPOOL_BWD", "UZ_OP_BILINEAR_BWD")
+              and o.p("fold_arg" if o["code"] == "UZ_OP_CONV_BWD_DATA" else "a") is not None and o.p("partials") is not None]
     assert len(folded) == 20
     monkeypatch.setenv("UZ_LANES", "2")
     plan2 = Unet(1, 2, [32, 64, 128, 192], device="cpu")._build(32, 128, 128)
@@ -337,7 +339,7 @@ def test_unet_plan_folds_the_relu_backward_into_the_last_writer_of_dA(monkeypatc
 
 
 def test_phiseg_plan_round4_passes(monkeypatch):
-    """Plan-level view of split storage at the BASELINE size (Plan._round4_passes): every buffer kept as operand
+    """Plan-level view of split storage at the BASELINE size (Plan._split_storage_passes): every buffer kept as operand
     pieces is written only by launches that know their bound beforehand (BatchNorm apply with the convolution's statistics, pooling,
     interpolation) and read only by split-path convolutions; a concat buffer's two producers own one bound slot each and the
     forward consumer switches scales on a 16-channel boundary; dy is packed exactly where the unit's backward is not the

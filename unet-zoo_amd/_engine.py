@@ -231,7 +231,8 @@ class NativeModel(nn.Module):
         cuts = [k for k, o in enumerate(ops) if o["code"] == "UZ_OP_EVENT_RECORD"]
         segs, start = [], 0
         for k in cuts:
-            segs.append((start, k, ops[k]["p"][0][1]))          # [start, k) then record event of bucket b
+            _, bucket = ops[k].p("event")
+            segs.append((start, k, bucket))                     # [start, k) then record event of that bucket
             start = k + 1
         if start < n:
             segs.append((start, n, None))

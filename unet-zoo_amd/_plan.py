@@ -21,7 +21,8 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _ffi
+from . import _ffi, _ops
+from ._ops import conv_dims
 
 BN_EPS = 1e-3        # reference torchlayers.py:20
 BN_MOMENTUM = 0.01   # reference torchlayers.py:20
@@ -97,7 +98,7 @@ class Buf:
         self.amax, self.amax_cov = None, []      # magnitude-bound slot and the channel ranges whose producers maintain it
         self.alias = None                        # pooled scratch: several differently shaped Bufs share one arena region
         self.relu = None                         # set by Plan.conv_relu: {(c0, C): state} of Conv -> ReLU units writing into this buffer
-        self.packed = False                      # kept in split storage (Plan._round4_passes): Plan.tensor() of it is NOT fp32 values
+        self.packed = False                      # kept in split storage (Plan._split_storage_passes): Plan.tensor() of it is NOT fp32 values
         self.b16 = False                         # kept in bf16 storage (Plan._b16_pass): 2-byte elements, Plan.tensor() of it is a bfloat16 tensor
         self.vol = False                         # a volume (Plan.vol): [D + 2][C][H][W]
 
@@ -140,6 +141,15 @@ class View:
     @property
     def numel(self):
         return self.N * self.C * self.H * self.W
+
+
+def _buf_of(r):
+    """The Buf behind one operand ref - a view, a dy that has a buffer of its own, a volume's depth window - or None."""
+    if isinstance(r, tuple) and r and r[0] == "win":
+        r = r[1]
+    if isinstance(r, _ScratchView):
+        r = r.view
+    return r.buf if isinstance(r, View) else None
 
 
 class Latent:
@@ -272,13 +282,14 @@ class Plan:
 
     # ------------------------------------------------------------------ op emission
     def _emit(self, lst, code, p=(), i=(), f=(), n=0, detached=False):
-        """detached: a scheduling group of its own, whatever is emitted around it (parameter-only preparation ops: they are ready at
+        """p / i / f: operands in wire order or by name (_ops.make pads them to the op's schema).
+        detached: a scheduling group of its own, whatever is emitted around it (parameter-only preparation ops: they are ready at
         the head of the tape and must not sit in a layer's chain)."""
         gid = self._gid
         if detached:
             self._detached = getattr(self, "_detached", 0) + 1
             gid = ("detached", self._detached)
-        op = dict(code=code, p=list(p), i=[int(x) for x in i], f=[float(x) for x in f], n=int(n), gid=gid)
+        op = _ops.make(code, p, i, f, n, gid)
         lst.append(op)
         return op
 
@@ -378,7 +389,7 @@ class Plan:
     def _conv_bwd(self, x, wkey, gy, ks, db_key=None, wrow0=0, rec=None):
         """Weight gradient (+ optional bias gradient) and, when the input carries a gradient,
         the data gradient.  gy: gradient w.r.t. the conv output (a View).  rec (dict): receives the emitted 2-D ops
-        ("wgrad", "dgrad") for the round-4 passes of finalize()."""
+        ("wgrad", "dgrad") for the split-storage passes of finalize()."""
         rec = rec if rec is not None else {}
         cin, cout = x.C, gy.C
         if x.nb is not None and ks == 3:                      # volume: see _conv_fwd
@@ -396,7 +407,7 @@ class Plan:
             slabbuf = self.vec(wkey + ":wslabs", nslab * 9 * cout * 3 * cin) if nslab else None
             rec["wgrad"] = self._emit(self.bwd_ops, "UZ_OP_CONV_BWD_WEIGHT",
                        p=[("win", x), gy, self.G(wkey), None, ("scratch", "wgrad"), self.amax_in(x), self.amax_in(gy), None, slabbuf],
-                       i=[3 * cin, x.Ctot, cout, gy.Ctot, x.N, x.H, x.W, 3, 0, 0, 0, 1 if nslab else 0, nslab], n=ws)      # i[12]: slabs the buffer was sized for
+                       i=[3 * cin, x.Ctot, cout, gy.Ctot, x.N, x.H, x.W, 3, 0, 0, 0, 1 if nslab else 0, nslab], n=ws)      # nslab: slabs the buffer was sized for
             if nslab:
                 self.__dict__.setdefault("_wgrad_jobs", []).append((slabbuf, wkey, nslab, cout, 3 * cin, 9, cin))
             x = x_orig
@@ -431,7 +442,7 @@ class Plan:
             rec["wgrad"] = self._emit(self.bwd_ops, "UZ_OP_CONV_BWD_WEIGHT",
                                       p=[x, gy, self.G(wkey, wextra), self.G(db_key, wrow0) if db_key else None, ("scratch", "wgrad"),
                                          self.amax_in(x), self.amax_in(gy), None, slabbuf],
-                                      i=[cin, x.Ctot, cout, gy.Ctot, x.N, x.H, x.W, ks, 0, 0, 0, 1 if nslab else 0, nslab], n=ws)      # i[12]: slabs the buffer was sized for (checked at launch: ADVICE r5)
+                                      i=[cin, x.Ctot, cout, gy.Ctot, x.N, x.H, x.W, ks, 0, 0, 0, 1 if nslab else 0, nslab], n=ws)      # nslab: slabs the buffer was sized for (checked at launch: ADVICE r5)
             if nslab:
                 self.__dict__.setdefault("_wgrad_jobs", []).append((slabbuf, wkey, nslab, cout, cin, ks * ks))
         # dy in a buffer of its own (small planes): the data gradient - the only thing the next layer's backward waits for -
@@ -535,7 +546,7 @@ class Plan:
         a = out if out is not None else new(name + ":a")
         assert a.C == cout and a.H == x.H and a.W == x.W
         # (4 C floats: mean, rstd and - where the statistics come from the convolution's partials - alpha, beta' for a data gradient
-        # that folds this unit's backward reduction, see _round4_passes)
+        # that folds this unit's backward reduction, see _split_storage_passes)
         save = save if save is not None else self.vec(name + ":bnsave", 4 * cout)
         # BatchNorm statistics in the convolution's epilogue (torchlayers.py:18-21: every Conv2d of a unit feeds a BatchNorm2d):
         # where the forward kernel supports it, it leaves per-tile {sum, sum of squares, max, max(-y)} partials and the
@@ -559,7 +570,7 @@ class Plan:
         bnws = self.L.uz_bn_workspace(cout, x.N, x.H, x.W)
         self.scratch["bn"] = max(self.scratch["bn"], bnws)
         gam, bet = bprefix + ".weight", bprefix + ".bias"
-        # unit record for the round-4 passes (finalize -> _round4_passes); units inside reversible sequences (shared scratch,
+        # unit record for the split-storage passes (finalize -> _split_storage_passes); units inside reversible sequences (shared scratch,
         # recomputation inside the backward tape) and volume units stay as they are
         plain = ybuf is None and a_grad is None and x.nb is None and self.__dict__.get("_rev_ctx") is None and self.target is self.fwd_ops
         unit = dict(name=name, y=y, a=a, save=save, relu=int(relu), npart=npart, C=cout, N=x.N, H=x.H, W=x.W) if plain else None
@@ -1066,13 +1077,36 @@ class Plan:
         self.ptr_tables.append(refs)
         return ("ptrtab", len(self.ptr_tables) - 1)
 
-    # ------------------------------------------------------------------ round-4 passes over the emitted ops
-    # p[] slots through which an op may WRITE / READ a buffer that is kept in split storage (csrc/split_f16.h: one word per element
-    # holding the two fp16 pieces of the scaled value - what the split-fp16 convolutions otherwise form in their staging)
-    _PACK_WRITERS = {"UZ_OP_BN_RELU_FWD": (6, 8), "UZ_OP_BILINEAR_FWD": (1, 3), "UZ_OP_AVGPOOL_FWD": (1, 3)}     # (view slot, bound slot)
-    _PACK_READERS = {"UZ_OP_CONV_FWD": 0, "UZ_OP_CONV_BWD_WEIGHT": 0}
+    # ------------------------------------------------------------------ split-storage passes over the emitted ops
+    def _all_tapes(self):
+        return [("fwd", self.fwd_ops), ("loss", self.loss_ops), ("bwd", self.bwd_ops)] + list(self.extra_ops.items())
 
-    def _round4_passes(self):
+    def _users_of(self, v):
+        """(writers, readers) of the channels of view `v` across all tapes, each a list of (op, slot name, ref)."""
+        writers, readers = [], []
+        for _, ops in self._all_tapes():
+            for o in ops:
+                wr = _ops.writes(o)
+                for j, r in enumerate(o["p"]):
+                    if isinstance(r, View) and r.buf is v.buf and r.c0 < v.c0 + v.C and v.c0 < r.c0 + r.C:
+                        (writers if j in wr else readers).append((o, _ops.SCHEMA[o["code"]].p[j], r))
+        return writers, readers
+
+    def _sole_dgrad(self, u, tabbed):
+        """The plain data gradient that is the ONLY writer of unit `u`'s dA, which nothing but the unit's BatchNorm backward reads;
+        None when there is no such op."""
+        B, ga = u.get("bn_bwd"), u.get("ga")
+        if B is None or not isinstance(ga, View) or ga.nb is not None or id(ga.buf) in tabbed:
+            return None
+        writers, readers = self._users_of(ga)
+        if len(writers) != 1 or len(readers) != 1 or readers[0][0] is not B:
+            return None
+        W, nm, r = writers[0]
+        if W["code"] != "UZ_OP_CONV_BWD_DATA" or nm != "dx" or (r.c0, r.C, r.nb) != (ga.c0, ga.C, None) or W.p("fold_arg") is not None or W.i("accumulate"):
+            return None
+        return W
+
+    def _split_storage_passes(self):
         """Plan-time rewrites on the Conv2D units (torchlayers.py:18-21) of the large planes, all decided from the emitted ops:
           1. folded backward reduction - where the ONLY writer of a unit's dA is an unsplit split-path data gradient, that launch masks
              dA with the unit's ReLU and leaves the BatchNorm-backward sums in its epilogue; the unit's backward runs a per-channel
@@ -1090,16 +1124,6 @@ class Plan:
             return info                              # fp32-only / bf16 modes have no two-piece operands
         env = lambda k: os.environ.get(k, "1") == "1"
         large = lambda u: u["N"] * u["H"] * u["W"] > 4096 and (u["H"] * u["W"]) % 4 == 0
-        all_ops = [("fwd", self.fwd_ops), ("loss", self.loss_ops), ("bwd", self.bwd_ops)] + list(self.extra_ops.items())
-
-        def touches(r, buf):
-            if isinstance(r, View):
-                return r.buf is buf
-            if isinstance(r, _ScratchView):
-                return r.view is not None and r.view.buf is buf
-            if isinstance(r, tuple) and r and r[0] in ("win",):
-                return r[1].buf is buf
-            return False
         tabbed = {id(q.buf) for t in self.ptr_tables for q in t if isinstance(q, View)}
         # ---- 1. folded backward reduction
         # (off by default: measured on MI355X the epilogue's extra read of y is exposed - the 64-channel-tile kernel keeps ONE
@@ -1107,34 +1131,21 @@ class Plan:
         #  269 -> 170 us for the unit's BatchNorm backward; step +-0)
         if os.environ.get("UZ_FOLD_BN_BWD", "0") == "1" and self.bwd_ops:
             for u in units:
-                B = u.get("bn_bwd")
-                if B is None or not large(u) or u["npart"] <= 0:
+                if not large(u) or u["npart"] <= 0:
                     continue
-                ga = u["ga"]
-                if not isinstance(ga, View) or ga.nb is not None or id(ga.buf) in tabbed:
+                W = self._sole_dgrad(u, tabbed)
+                if W is None:
                     continue
-                writers, readers = [], []
-                for tape, ops in all_ops:
-                    for o in ops:
-                        wr = self._op_writes(o)
-                        for j, r in enumerate(o["p"]):
-                            if touches(r, ga.buf) and isinstance(r, View) and r.c0 < ga.c0 + ga.C and ga.c0 < r.c0 + r.C:
-                                (writers if j in wr else readers).append((o, j, r))
-                if len(writers) != 1 or len(readers) != 1 or readers[0][0] is not B:
+                _, cin_w, cout_w, N, H, Wd, ks = conv_dims(W)
+                if ks != 3:
                     continue
-                W, j, r = writers[0]
-                if W["code"] != "UZ_OP_CONV_BWD_DATA" or j != 2 or (r.c0, r.C, r.nb) != (ga.c0, ga.C, None) or len(W["p"]) != 7 or W["i"][8] != 0 or W["i"][7] != 3:
-                    continue
-                cout_w, cin_w, N, H, Wd = W["i"][0], W["i"][2], W["i"][4], W["i"][5], W["i"][6]
                 rows = self.L.uz_conv_bwd_relu_partials(cin_w, cout_w, N, H, Wd, 3)
                 if rows <= 0 or cin_w != u["C"]:
                     continue
                 part = self.vec(u["name"] + ":bwdpart", 4 * u["C"] * rows)
                 y = u["y"]
-                W["p"] = W["p"][:7] + [y, part, None, u["save"]]
-                W["i"] = W["i"][:9] + [y.Ctot, 2, 0, u["relu"]]
-                B["p"] = B["p"][:11] + [part]
-                B["i"][8] = rows
+                W.set(p={"fold_arg": y, "partials": part, "bn_stats": u["save"]}, i={"ctot_fold": y.Ctot, "fold": 2, "fold_relu": u["relu"]})
+                u["bn_bwd"].set(p={"da_partials": part}, i={"npart": rows})
                 info["folded"] += 1
         # ---- 1b. small planes: the data gradient's split-K reduce folded into the consumer's BatchNorm backward (the mirror of the
         # forward's uz_conv_fwd_slabs / uz_bn_relu_fwd_slabs): where the ONLY writer of a unit's dA is a split-K fp32 data gradient, that
@@ -1143,31 +1154,18 @@ class Plan:
         info["dgrad_folded"] = 0
         if env("UZ_BN_FOLD_DGRAD") and self.bwd_ops:
             for u in units:
-                B = u.get("bn_bwd")
-                ga = u.get("ga")
-                if B is None or u["N"] * u["H"] * u["W"] > 4096 or not isinstance(ga, View) or ga.nb is not None or id(ga.buf) in tabbed:
+                if u["N"] * u["H"] * u["W"] > 4096:
                     continue
-                writers, readers = [], []
-                for tape, ops in all_ops:
-                    for o in ops:
-                        wr = self._op_writes(o)
-                        for j, r in enumerate(o["p"]):
-                            if touches(r, ga.buf) and isinstance(r, View) and r.c0 < ga.c0 + ga.C and ga.c0 < r.c0 + r.C:
-                                (writers if j in wr else readers).append((o, j, r))
-                if len(writers) != 1 or len(readers) != 1 or readers[0][0] is not B:
+                W = self._sole_dgrad(u, tabbed)
+                if W is None:
                     continue
-                W, j, r = writers[0]
-                if W["code"] != "UZ_OP_CONV_BWD_DATA" or j != 2 or (r.c0, r.C, r.nb) != (ga.c0, ga.C, None) or len(W["p"]) != 7 or W["i"][8] != 0:
-                    continue
-                cout_w, cin_w, N, H, Wd, ksw = W["i"][0], W["i"][2], W["i"][4], W["i"][5], W["i"][6], W["i"][7]
+                _, cin_w, cout_w, N, H, Wd, ksw = conv_dims(W)
                 parts = self.L.uz_conv_bwd_splitk_parts(cin_w, cout_w, N, H, Wd, ksw)
                 if parts <= 1 or cin_w != u["C"]:
                     continue
                 slabs = self.vec(u["name"] + ":daslabs", parts * N * cin_w * H * Wd)
-                W["p"] = W["p"][:7] + [slabs]
-                W["i"] = W["i"][:9] + [0, 3]
-                B["p"] = (B["p"] + [None])[:11] + [slabs]
-                B["i"] = (B["i"] + [0])[:11] + [parts]
+                W.set(p={"fold_arg": slabs}, i={"fold": 3})
+                u["bn_bwd"].set(p={"da_partials": slabs}, i={"nslab": parts})
                 info["dgrad_folded"] += 1
         # ---- 2. dY in split storage
         if env("UZ_PACK_DY") and self.bwd_ops:
@@ -1179,15 +1177,11 @@ class Plan:
                     continue                         # one-launch backward (channel's batch on chip): no tensor-wide bound before the first write
                 if self.L.uz_conv_route(2, u["cin"], u["C"], u["N"], u["H"], u["W"], 3) != 1:
                     continue
-                if dg is not None and (self.L.uz_conv_route(1, u["cin"], u["C"], u["N"], u["H"], u["W"], 3) != 1 or dg["i"][10:11] == [1]):
+                if dg is not None and (self.L.uz_conv_route(1, u["cin"], u["C"], u["N"], u["H"], u["W"], 3) != 1 or dg.i("fold") == 1):
                     continue
-                B["i"][9] = 1
-                B["p"] = (B["p"] + [None])[:12]
-                wg["i"][10] = 1
-                if dg is not None:
-                    dg["i"] = (dg["i"] + [0, 0, 0, 0])[:13]
-                    dg["i"][11] = 1
-                    dg["p"] = (dg["p"] + [None] * 4)[:11]
+                for o in (B, wg, dg):
+                    if o is not None:
+                        o.set(i={"dy_packed": 1})
                 info["dy_packed"] += 1
         # ---- 3. activations in split storage
         if env("UZ_PACK_ACT") and not self.extra_ops:
@@ -1196,28 +1190,27 @@ class Plan:
                 if b.alias is not None or id(b) in tabbed or id(b) in named or (b.H * b.W) % 4 or b.N * b.H * b.W <= max(4096, self._chain_limit()):
                     continue                                 # (planes of the deep-level chain stay fp32: its convolutions split on the fly)
                 wr_list, rd_list, ok = [], [], True
-                for tape, ops in all_ops:
+                for tape, ops in self._all_tapes():
                     for o in ops:
-                        for j, r in enumerate(o["p"]):
-                            if not touches(r, b):
+                        c = o["code"]
+                        writer, reader = _ops.SPLIT_WRITERS.get(c), _ops.SPLIT_READERS.get(c)
+                        for nm, r in zip(_ops.SCHEMA[c].p, o["p"]):
+                            if _buf_of(r) is not b:
                                 continue
-                            c = o["code"]
                             if not isinstance(r, View) or r.nb is not None:
                                 ok = False
-                            elif c in self._PACK_WRITERS and j == self._PACK_WRITERS[c][0]:
+                            elif writer and nm == writer[0]:
                                 if c == "UZ_OP_BN_RELU_FWD":
-                                    i = o["i"]
-                                    npx = i[3] * i[4] * i[5]
-                                    one_launch = 4096 < npx <= self.L.uz_bn_fwd_fused_limit(i[4], i[5])      # mid path: a-priori bound from the parameters
-                                    if not (i[6] and i[9] == 0 and (i[8] > 0 or one_launch)):
+                                    N, H, W = o.i("N", "H", "W")
+                                    one_launch = 4096 < N * H * W <= self.L.uz_bn_fwd_fused_limit(H, W)      # mid path: a-priori bound from the parameters
+                                    if not (o.i("training") and o.i("nslab") == 0 and (o.i("npart") > 0 or one_launch)):
                                         ok = False           # needs the bound before the first word is written
-                                if c != "UZ_OP_BN_RELU_FWD" and o["p"][2] is None:
+                                elif o.p("x_amax") is None:
                                     ok = False               # pooling / interpolation forward their INPUT's bound
                                 wr_list.append((o, r))
-                            elif c in self._PACK_READERS and j == self._PACK_READERS[c]:
-                                i = o["i"]
-                                kind = 0 if c == "UZ_OP_CONV_FWD" else 2
-                                if i[7] != 3 or self.L.uz_conv_route(kind, i[0], i[2], i[4], i[5], i[6], 3) != 1 or (kind == 0 and i[9]):
+                            elif reader and nm == reader[0]:
+                                kind, cin, cout, N, H, W, ks = conv_dims(o)
+                                if ks != 3 or self.L.uz_conv_route(kind, cin, cout, N, H, W, 3) != 1 or (kind == 0 and o.i("slabs_only")):
                                     ok = False
                                 rd_list.append((o, r))
                             else:
@@ -1240,30 +1233,13 @@ class Plan:
                     continue
                 slot_of = {}
                 for o, r in wr_list:
-                    vi, bi = self._PACK_WRITERS[o["code"]]
+                    _, bound, flag = _ops.SPLIT_WRITERS[o["code"]]
                     slot = slot_of[(r.c0, r.c0 + r.C)] = ("amax", self._new_amax())
-                    o["p"][bi] = slot + ("acc",)
-                    if o["code"] == "UZ_OP_BN_RELU_FWD":
-                        o["i"] = (o["i"] + [0])[:11]
-                        o["i"][10] = 1
-                    elif o["code"] == "UZ_OP_BILINEAR_FWD":
-                        o["i"] = (o["i"] + [0])[:8]
-                        o["i"][7] = 1
-                    else:
-                        o["i"] = (o["i"] + [0])[:7]
-                        o["i"][6] = 1
+                    o.set(p={bound: slot + ("acc",)}, i={flag: 1})
                 for o, r, cov in plan_rd:
-                    s1 = slot_of[cov[0]]
-                    s2 = slot_of[cov[1]] if len(cov) == 2 else None
-                    seg = cov[1][0] - r.c0 if len(cov) == 2 else 0
-                    if o["code"] == "UZ_OP_CONV_FWD":
-                        o["p"] = (o["p"] + [None])[:11]
-                        o["p"][5], o["p"][10] = s1, s2
-                        o["i"] = (o["i"] + [0, 0])[:12]
-                        o["i"][10], o["i"][11] = 1, seg
-                    else:
-                        o["p"][5], o["p"][7] = s1, s2
-                        o["i"][8], o["i"][9] = 1, seg
+                    _, bound, bound2, seg2_c0, flag = _ops.SPLIT_READERS[o["code"]]
+                    two = len(cov) == 2
+                    o.set(p={bound: slot_of[cov[0]], bound2: slot_of[cov[1]] if two else None}, i={flag: 1, seg2_c0: cov[1][0] - r.c0 if two else 0})
                 b.packed = True
                 info["act_packed"] += 1
                 info["act_views"] += len(wr_list)
@@ -1284,109 +1260,80 @@ class Plan:
         ops = self.fwd_ops
         for u in [u for u in self.__dict__.get("_units", []) if "bn_fwd" in u]:
             B = u["bn_fwd"]
-            i = B["i"]
-            if not (len(i) > 10 and i[10] == 1 and i[8] > 0 and i[9] == 0 and i[6] == 1) or (len(i) > 11 and i[11]) or (len(i) > 13 and i[13]):
+            if not (B.i("a_packed") == 1 and B.i("npart") > 0 and B.i("nslab") == 0 and B.i("training") == 1) or B.i("phase") or B.i("b16"):
                 continue                                             # large path, statistics from the convolution's partials, split-storage output
-            if i[3] * i[4] * i[5] <= self.L.uz_bn_fwd_fused_limit(i[4], i[5]) or not any(o is B for o in ops):
+            N, H, W = B.i("N", "H", "W")
+            if N * H * W <= self.L.uz_bn_fwd_fused_limit(H, W) or not any(o is B for o in ops):
                 continue
-            y, a = B["p"][0], B["p"][6]
+            y, a = B.p("y", "a")
             if not (isinstance(a, View) and isinstance(y, View)) or a.nb is not None or y.nb is not None or not a.contiguous:
                 continue
-            readers = [(o, j) for o in ops for j, r in enumerate(o["p"]) if o is not B and isinstance(r, View) and r.buf is a.buf]
+            readers = [(o, nm, r) for o in ops for nm, r in zip(_ops.SCHEMA[o["code"]].p, o["p"]) if o is not B and isinstance(r, View) and r.buf is a.buf]
             if len(readers) != 1 or any(isinstance(r, View) and r.buf is a.buf for o in self.loss_ops for r in o["p"]):
                 continue
-            R, j = readers[0]
-            ri, rv = R["i"], R["p"][0]
-            if R["code"] != "UZ_OP_CONV_FWD" or j != 0 or ri[7] != 3 or ri[8] or not (len(ri) > 10 and ri[10] == 1) or (len(ri) > 11 and ri[11]) or \
-                    (len(ri) > 9 and ri[9]) or (len(ri) > 12 and ri[12]) or (len(ri) > 13 and ri[13]) or (rv.c0, rv.C, rv.nb) != (0, a.buf.C, None):
+            R, nm, rv = readers[0]
+            if R["code"] != "UZ_OP_CONV_FWD" or nm != "x" or R.i("ks") != 3 or R.i("x_packed") != 1 or any(R.i("relu", "x_seg2_c0", "slabs_only", "bn_in", "b16")) or \
+                    (rv.c0, rv.C, rv.nb) != (0, a.buf.C, None):
                 continue
             k = next(n for n, o in enumerate(ops) if o is B)
-            fin = dict(B, p=list(B["p"]), i=(list(i) + [0, 0])[:12], f=list(B["f"]))
-            fin["p"][0] = fin["p"][6] = None
-            fin["i"][11] = 1
+            fin = B.clone().set(p={"y": None, "a": None}, i={"phase": 1})
             self._detached = getattr(self, "_detached", 0) + 1
-            app = dict(B, p=list(B["p"]), i=(list(i) + [0, 0])[:12], f=list(B["f"]), gid=("bnapply", self._detached))
-            app["p"][3] = app["p"][4] = app["p"][9] = None
-            app["p"][8] = tuple(app["p"][8][:2])                       # reads the bound the statistics launch published
-            app["i"][11] = 2
+            kind, slot, _acc = B.p("a_amax")                         # the apply pass reads the bound the statistics launch published
+            app = B.clone(gid=("bnapply", self._detached)).set(p={"running_mean": None, "running_var": None, "bn_partials": None, "a_amax": (kind, slot)},
+                                                                    i={"phase": 2})
             ops[k:k + 1] = [fin, app]
             u["bn_fwd"] = fin
-            R["p"] = (list(R["p"]) + [None] * 12)[:12]
-            R["p"][0], R["p"][10], R["p"][11] = y, None, B["p"][5]
-            R["i"] = (list(ri) + [0] * 13)[:13]
-            R["i"][1], R["i"][10], R["i"][12] = y.Ctot, 0, 1 | (int(i[7]) << 1)
+            R.set(p={"x": y, "x_amax2": None, "bn_stats": B.p("save")}, i={"ctot_x": y.Ctot, "x_packed": 0, "bn_in": 1 | (B.i("relu") << 1)})
             info["units"] += 1
         return info
 
     # ------------------------------------------------------------------ bf16 storage (BASELINE config 5: PHiSeg3D "bf16")
-    # tensor operand slots of the ops that have a bf16-storage form (include/uz_api.h, "bf16 storage"), in the order of the bits of i[13]
-    _B16_SLOTS = {
-        "UZ_OP_CONV_FWD": (0, 3), "UZ_OP_CONV_BWD_DATA": (0, 2), "UZ_OP_CONV_BWD_WEIGHT": (0, 1),
-        "UZ_OP_BN_RELU_FWD": (0, 6), "UZ_OP_BN_RELU_BWD": (0, 1, 5),
-        "UZ_OP_AVGPOOL3D_FWD": (0, 1), "UZ_OP_AVGPOOL3D_BWD": (0, 1), "UZ_OP_DEPTH_LERP_FWD": (0, 1), "UZ_OP_DEPTH_LERP_BWD": (0, 1),
-        "UZ_OP_BILINEAR_FWD": (0, 1), "UZ_OP_BILINEAR_BWD": (0, 1),          # (only the high-resolution side: see _b16_slots)
-    }
-
     def _b16_slots(self, o):
-        """(p[] slot, bit of i[13]) of the tensor operands of op `o` that may be bf16; () = no bf16-storage form."""
-        c = o["code"]
-        slots = self._B16_SLOTS.get(c)
-        if not slots:
-            return ()
-        if c.startswith("UZ_OP_CONV_") and o["i"][7] == 1:       # 1x1 head: only the many-channel side (x / dx), the 1 .. 8-channel side stays fp32
-            return {"UZ_OP_CONV_FWD": ((0, 0),), "UZ_OP_CONV_BWD_DATA": ((2, 1),), "UZ_OP_CONV_BWD_WEIGHT": ((0, 0),)}[c]
-        if c == "UZ_OP_BILINEAR_FWD":
-            return ((1, 1),)
-        if c == "UZ_OP_BILINEAR_BWD":
-            return ((0, 0),)
-        return tuple((j, k) for k, j in enumerate(slots))
+        """(p[] slot, format bit) of the tensor operands of op `o` that may be bf16; () = no bf16-storage form.  A pass-through to
+        _ops.b16_slots, kept because callers outside this module ask the plan."""
+        return _ops.b16_slots(o)
 
     def _b16_ok(self, o):
-        """Can op `o` run through its bf16-storage entry point (whatever the formats of its operands turn out to be)?"""
-        c, i, p = o["code"], o["i"][:13], o["p"]                # (i[13] = the format bits this pass sets)
-        if c in ("UZ_OP_CONV_FWD", "UZ_OP_CONV_BWD_DATA", "UZ_OP_CONV_BWD_WEIGHT") and i[7] == 1:
-            kind = {"UZ_OP_CONV_FWD": 0, "UZ_OP_CONV_BWD_DATA": 1, "UZ_OP_CONV_BWD_WEIGHT": 2}[c]
-            cin, cout = (i[2], i[0]) if kind == 1 else (i[0], i[2])
-            if cout not in (1, 2, 3, 4, 6, 8) or cin > 512 or (i[5] * i[6]) % 4:
+        """Can op `o` run through its bf16-storage entry point (whatever the formats of its operands turn out to be)?  Only the base
+        form of a kernel has one (Op.base_form: the format bits themselves are what this pass sets, they do not count)."""
+        c = o["code"]
+        if c in _ops.CONV_KIND:
+            kind, cin, cout, N, H, W, ks = conv_dims(o)
+            base = o.base_form() and (kind != 1 or o.p("fold_arg") is None)
+            if ks == 1:
+                return cout in (1, 2, 3, 4, 6, 8) and cin <= 512 and (H * W) % 4 == 0 and base
+            if ks != 3 or W % 32:
                 return False
-            if kind == 0:
-                return not any(i[8:])                          # (no ReLU, no slabs)
-            if kind == 1:
-                return not any(i[9:]) and len(p) <= 7
-            return not any(i[8:])
-        if c in ("UZ_OP_CONV_FWD", "UZ_OP_CONV_BWD_DATA", "UZ_OP_CONV_BWD_WEIGHT"):
-            kind = {"UZ_OP_CONV_FWD": 0, "UZ_OP_CONV_BWD_DATA": 1, "UZ_OP_CONV_BWD_WEIGHT": 2}[c]
-            W = i[6]
-            # (a weight gradient may leave its slabs to the table launch - i[11] - in either storage: uz_conv_bwd_weight_b16 takes slabs_out)
-            if i[7] != 3 or W % 32 or (any(i[8:11]) or any(i[13:]) if kind == 2 else any(i[8:]) and kind != 1):      # (weight gradient: i[11] slabs-only, i[12] the slab count the buffer was sized for)
+            if kind == 2:
+                # (a weight gradient may leave its slabs to the table launch - slabs_only / nslab - in either storage: uz_conv_bwd_weight_b16 takes slabs_out)
+                if any(o.i("x_packed", "x_seg2_c0", "dy_packed")) or o.p("db") is not None:
+                    return False
+            elif not base:
                 return False
-            if kind == 1 and (any(i[9:]) or len(p) > 7):
+            if kind != 2 and self.L.uz_conv_split_parts(kind, cin, cout, N, H, W) != 1:
                 return False
-            if kind == 2 and p[3] is not None:
-                return False
-            cin, cout = (i[2], i[0]) if kind == 1 else (i[0], i[2])
-            if kind != 2 and self.L.uz_conv_split_parts(kind, cin, cout, i[4], i[5], i[6]) != 1:
-                return False
-            return self.L.uz_conv_route(kind, cin, cout, i[4], i[5], i[6], 3) == 1
+            return self.L.uz_conv_route(kind, cin, cout, N, H, W, 3) == 1
         if c == "UZ_OP_BN_RELU_FWD":
-            return i[3] * i[4] * i[5] > 32768 and (i[4] * i[5]) % 4 == 0 and i[6] == 1 and not any(i[9:])
+            N, H, W = o.i("N", "H", "W")
+            return N * H * W > 32768 and (H * W) % 4 == 0 and o.i("training") == 1 and o.base_form()
         if c == "UZ_OP_BN_RELU_BWD":
-            return i[4] * i[5] * i[6] > 32768 and (i[5] * i[6]) % 4 == 0 and not any(i[8:]) and len(p) <= 11
+            N, H, W = o.i("N", "H", "W")
+            return N * H * W > 32768 and (H * W) % 4 == 0 and o.base_form() and o.p("da_partials") is None
         if c in ("UZ_OP_AVGPOOL3D_FWD", "UZ_OP_AVGPOOL3D_BWD"):
-            return i[5] % 4 == 0 and i[4] % 2 == 0
+            return o.i("W") % 4 == 0 and o.i("H") % 2 == 0
         if c in ("UZ_OP_DEPTH_LERP_FWD", "UZ_OP_DEPTH_LERP_BWD"):
-            return (i[4] * i[5]) % 4 == 0
-        if c == "UZ_OP_BILINEAR_FWD":                          # i = [C, CtotX, CtotY, N, H, W, align_corners, (packed)]: the band kernel's shapes
-            return i[5] % 4 == 0 and i[5] <= 128 and i[4] >= 4 and not any(i[7:]) and (len(p) < 3 or True)
-        if c == "UZ_OP_BILINEAR_BWD":                          # i = [C, CtotDy, CtotDx, N, H, W, align_corners, acc]
-            return 2 * i[5] <= 128 and i[4] >= 4 and 256 % i[5] == 0 and len(p) <= 2 and not any(i[8:])
+            return (o.i("H") * o.i("W")) % 4 == 0
+        if c == "UZ_OP_BILINEAR_FWD":                          # the band kernel's shapes
+            return o.i("W") % 4 == 0 and o.i("W") <= 128 and o.i("H") >= 4 and o.base_form() and (o.p("x_amax") is None or True)
+        if c == "UZ_OP_BILINEAR_BWD":
+            return 2 * o.i("W") <= 128 and o.i("H") >= 4 and 256 % o.i("W") == 0 and o.p("a") is None and o.base_form()
         return False
 
     def _b16_pass(self):
         """Which volume tensors are kept in bf16 (UZ_STORE_B16=1 / Plan.store_b16, single-piece bf16 arithmetic only): a buffer whose
         EVERY reader and writer - in every tape - is an op with a bf16-storage form on a shape that form serves (the 3x3x3
         convolutions on the matrix pipe with planes wider than 32, the large-plane BatchNorm path, AvgPool3d, the depth stage of the
-        trilinear interpolation).  The decision is per buffer, every op carries one format bit per tensor operand (i[13]), so the
+        trilinear interpolation).  The decision is per buffer, every op carries one format bit per tensor operand (its b16 slot), so the
         two formats mix freely: what some other op touches (the 1x1x1 heads' inputs, the in-plane interpolation's operands, the
         latent and loss tensors, the image) stays fp32.  A unit's dy moves to a bf16 twin of the zero-bordered scratch class when
         its three backward ops all qualify.  Returns / keeps a summary in self.b16_info."""
@@ -1397,15 +1344,6 @@ class Plan:
         all_ops = [o for ops in (self.fwd_ops, self.loss_ops, self.bwd_ops) for o in ops]
         tabbed = {id(q.buf) for t in self.ptr_tables for q in t if isinstance(q, View)}
         named = {id(v.buf) for v in self.named.values() if isinstance(v, View)}
-
-        def buf_of(r):
-            if isinstance(r, View):
-                return r.buf
-            if isinstance(r, _ScratchView):
-                return r.view.buf if r.view is not None else None
-            if isinstance(r, tuple) and r and r[0] == "win":
-                return r[1].buf
-            return None
         ok_cache = {}
         bad, seen = set(), set()
         for o in all_ops:
@@ -1413,7 +1351,7 @@ class Plan:
             if id(o) not in ok_cache:
                 ok_cache[id(o)] = bool(slots) and self._b16_ok(o)
             for j, r in enumerate(o["p"]):
-                b = buf_of(r)
+                b = _buf_of(r)
                 if b is None:
                     continue
                 seen.add(id(b))
@@ -1438,12 +1376,12 @@ class Plan:
             new = (old[0], old[1], 16)
             self._gyz[new] = max(self._gyz.get(new, 0), (self._gyz[old] + 1) // 2)
             gyv.zkey = new
-            assert B["p"][5] == ("gyvol", old)
-            B["p"][5] = ("gyvol", new)
+            assert B.p("dy") == ("gyvol", old)
+            B.set(p={"dy": ("gyvol", new)})
             B["b16_dy"] = Wg["b16_dy"] = True
             if Dg is not None:
-                assert Dg["p"][0] == ("gywin", old)
-                Dg["p"][0] = ("gywin", new)
+                assert Dg.p("dy") == ("gywin", old)
+                Dg.set(p={"dy": ("gywin", new)})
                 Dg["b16_dy"] = True
             info["dy"] += 1
         used = set()
@@ -1460,17 +1398,13 @@ class Plan:
             slots = self._b16_slots(o)
             if not slots or not ok_cache.get(id(o)):
                 continue
+            dy_slot = _ops.SCHEMA[o["code"]].px["dy"] if o.get("b16_dy") else None
             bits = 0
             for j, k in slots:
-                r = o["p"][j]
-                b = buf_of(r)
-                is16 = b is not None and b.b16
-                if o.get("b16_dy") and ((o["code"] == "UZ_OP_BN_RELU_BWD" and j == 5) or (o["code"] == "UZ_OP_CONV_BWD_WEIGHT" and j == 1) or (o["code"] == "UZ_OP_CONV_BWD_DATA" and j == 0)):
-                    is16 = True
-                bits |= int(is16) << k
+                b = _buf_of(o["p"][j])
+                bits |= int((b is not None and b.b16) or j == dy_slot) << k
             if bits:
-                o["i"] = (o["i"] + [0] * 14)[:14]
-                o["i"][13] = bits
+                o.set(i={"b16": bits})
                 info["ops"] += 1
         return info
 
@@ -1536,62 +1470,70 @@ class Plan:
         """The sub-network an op belongs to (first component of the name of the tensor / parameter it is about): backward chains are
         built per sub-network, so that the prior's deep levels - which only wait for the KL gradients - run beside the likelihood's
         device-filling kernels instead of behind them."""
-        c, p = o["code"], o["p"]
-        ref = {"UZ_OP_BN_RELU_BWD": 1, "UZ_OP_BN_RELU_FWD": 0, "UZ_OP_AVGPOOL_BWD": 0, "UZ_OP_BILINEAR_BWD": 0,
-               "UZ_OP_LATENT_BWD": 5, "UZ_OP_LATENT_HEADS_BWD_DATA": 0}.get(c)
+        c = o["code"]
         if c in ("UZ_OP_CONV_BWD_DATA", "UZ_OP_CONV_FWD"):
-            return p[1][1].split(".")[0] if isinstance(p[1], tuple) else None
-        if ref is None or not isinstance(p[ref], View):
+            w = o.p("w")
+            return w[1].split(".")[0] if isinstance(w, tuple) else None          # w = ("param", key, offset)
+        slot = {"UZ_OP_BN_RELU_BWD": "y", "UZ_OP_BN_RELU_FWD": "y", "UZ_OP_AVGPOOL_BWD": "dy", "UZ_OP_BILINEAR_BWD": "dy",
+                "UZ_OP_LATENT_BWD": "dmu", "UZ_OP_LATENT_HEADS_BWD_DATA": "dy_a"}.get(c)
+        if slot is None or not isinstance(o.p(slot), View):
             return None
-        nm = p[ref].buf.name
+        nm = o.p(slot).buf.name
         return (nm[5:] if nm.startswith("grad:") else nm).split(".")[0]
 
     def _chain_eligible_fwd(self, o, px):
-        c, i, p = o["code"], o["i"], o["p"]
-        b16 = len(i) > 13 and i[13]
-        if b16:
-            return False
+        c = o["code"]
         if c == "UZ_OP_CONV_FWD":
-            cin, cout, N, H, W, ks = i[0], i[2], i[4], i[5], i[6], i[7]
-            if ks != 3 or N * H * W > px or i[8] or (len(i) > 10 and i[10]) or (len(p) > 9 and p[9] is not None) or not isinstance(p[0], View) or p[0].nb is not None:
+            _, cin, cout, N, H, W, ks = conv_dims(o)
+            x = o.p("x")
+            if o.i("b16") or ks != 3 or N * H * W > px or o.i("relu") or o.i("x_packed") or o.p("bn_partials") is not None or not isinstance(x, View) or x.nb is not None:
                 return False
             if cin <= 4:
                 return True
-            return cin % 16 == 0 and cout % 32 == 0 and p[5] is not None
+            return cin % 16 == 0 and cout % 32 == 0 and o.p("x_amax") is not None
         if c == "UZ_OP_BN_RELU_FWD":
-            return i[6] == 1 and i[8] == 0 and not (len(i) > 10 and i[10]) and i[3] * i[4] * i[5] <= px and isinstance(p[0], View) and p[0].nb is None
+            N, H, W = o.i("N", "H", "W")
+            y = o.p("y")
+            return not o.i("b16") and o.i("training") == 1 and o.i("npart") == 0 and not o.i("a_packed") and N * H * W <= px and isinstance(y, View) and y.nb is None
         if c == "UZ_OP_AVGPOOL_FWD":
-            return i[3] * ((i[4] + 1) // 2) * ((i[5] + 1) // 2) <= px and not (len(i) > 6 and i[6]) and p[0].nb is None
+            N, H, W = o.i("N", "H", "W")
+            return N * ((H + 1) // 2) * ((W + 1) // 2) <= px and not o.i("y_packed") and o.p("x").nb is None
         if c == "UZ_OP_BILINEAR_FWD":
-            return i[3] * 4 * i[4] * i[5] <= px and not (len(i) > 7 and i[7]) and p[0].nb is None
+            N, H, W = o.i("N", "H", "W")
+            return not o.i("b16") and N * 4 * H * W <= px and not o.i("y_packed") and o.p("x").nb is None
         if c == "UZ_OP_LATENT_HEADS_FWD":
-            return i[2] == 2 and i[3] * i[4] * i[5] <= px
+            N, H, W = o.i("N", "H", "W")
+            return o.i("L") == 2 and N * H * W <= px
         return False
 
     def _chain_eligible_bwd(self, o, px):
-        c, i, p = o["code"], o["i"], o["p"]
-        if len(i) > 13 and i[13]:
-            return False
+        c = o["code"]
         own_dy = lambda r: isinstance(r, _ScratchView) and r.view is not None and r.zkey is None
         if c == "UZ_OP_BN_RELU_BWD":
-            return (i[4] * i[5] * i[6] <= px and i[8] == 0 and i[9] == 0 and i[10] == 0 and own_dy(p[5]) and isinstance(p[0], View) and p[0].nb is None
-                    and isinstance(p[1], View) and not p[1].buf.packed)
+            N, H, W = o.i("N", "H", "W")
+            da, y = o.p("da", "y")
+            return (not o.i("b16") and N * H * W <= px and not any(o.i("npart", "dy_packed", "dbias_rows")) and own_dy(o.p("dy"))
+                    and isinstance(da, View) and da.nb is None and isinstance(y, View) and not y.buf.packed)
         if c == "UZ_OP_CONV_BWD_DATA":
-            cout, cin, N, H, W, ks = i[0], i[2], i[4], i[5], i[6], i[7]
-            fold = i[10] if len(i) > 10 else 0
-            if ks != 3 or N * H * W > px or not own_dy(p[0]) or fold not in (0, 3) or (len(i) > 11 and i[11]) or p[2].nb is not None:
+            _, cin, cout, N, H, W, ks = conv_dims(o)
+            fold = o.i("fold")
+            if o.i("b16") or ks != 3 or N * H * W > px or not own_dy(o.p("dy")) or fold not in (0, 3) or o.i("dy_packed") or o.p("dx").nb is not None:
                 return False
             if cin <= 4:
                 return fold == 0
-            return cout % 16 == 0 and cin % 32 == 0 and p[4] is not None
+            return cout % 16 == 0 and cin % 32 == 0 and o.p("dy_amax") is not None
         if c == "UZ_OP_AVGPOOL_BWD":
-            return i[3] * i[4] * i[5] <= px and (len(p) < 3 or p[2] is None) and p[0].nb is None
+            N, H, W = o.i("N", "H", "W")
+            return N * H * W <= px and o.p("a") is None and o.p("dy").nb is None
         if c == "UZ_OP_BILINEAR_BWD":
-            return i[3] * 4 * i[4] * i[5] <= px and (len(p) < 3 or p[2] is None) and p[0].nb is None
+            N, H, W = o.i("N", "H", "W")
+            return not o.i("b16") and N * 4 * H * W <= px and o.p("a") is None and o.p("dy").nb is None
         if c == "UZ_OP_LATENT_BWD":
-            return isinstance(p[5], View) and p[5].C == 2 and p[5].N * p[5].H * p[5].W <= px
+            dmu = o.p("dmu")
+            return isinstance(dmu, View) and dmu.C == 2 and dmu.N * dmu.H * dmu.W <= px
         if c == "UZ_OP_LATENT_HEADS_BWD_DATA":
-            return i[0] == 2 and i[3] * i[4] * i[5] <= px
+            N, H, W = o.i("N", "H", "W")
+            return o.i("L") == 2 and N * H * W <= px
         return False
 
     def _chain_pass(self):
@@ -1632,8 +1574,8 @@ class Plan:
             self._chain_imgbuf[which] = self.vec("chain_weights:" + which, off // 4)
             tape = self.fwd_ops if which == "fwd" else self.bwd_ops
             pos = next(k for k, o in enumerate(tape) if o["code"] == "UZ_OP_CHAIN")
-            tape.insert(pos, dict(code="UZ_OP_CHAIN_PACK", p=[self.ptr_table(refs), ("amaxw", 0), self._chain_imgbuf[which]], i=[len(imgs), blk], f=[], n=0,
-                                  gid=("chainpack", which)))
+            tape.insert(pos, _ops.make("UZ_OP_CHAIN_PACK", p=[self.ptr_table(refs), ("amaxw", 0), self._chain_imgbuf[which]], i=[len(imgs), blk],
+                                       gid=("chainpack", which)))
 
     def _chain_build(self, which, ops, elig, net, px):
         fwd = which == "fwd"
@@ -1646,14 +1588,14 @@ class Plan:
         ywriter, bn_of_y, dgrad_of_dx, bn_of_da = {}, {}, {}, {}
         for k, o in enumerate(ops):
             c = o["code"]
-            if c == "UZ_OP_CONV_FWD" and isinstance(o["p"][3], View):
-                ywriter[vkey(o["p"][3])] = k
+            if c == "UZ_OP_CONV_FWD" and isinstance(o.p("y"), View):
+                ywriter[vkey(o.p("y"))] = k
             elif c == "UZ_OP_BN_RELU_FWD":
-                bn_of_y[vkey(o["p"][0])] = k
-            elif c == "UZ_OP_CONV_BWD_DATA" and isinstance(o["p"][2], View):
-                dgrad_of_dx.setdefault(vkey(o["p"][2]), []).append(k)
-            elif c == "UZ_OP_BN_RELU_BWD" and isinstance(o["p"][0], View):
-                bn_of_da[vkey(o["p"][0])] = k
+                bn_of_y[vkey(o.p("y"))] = k
+            elif c == "UZ_OP_CONV_BWD_DATA" and isinstance(o.p("dx"), View):
+                dgrad_of_dx.setdefault(vkey(o.p("dx")), []).append(k)
+            elif c == "UZ_OP_BN_RELU_BWD" and isinstance(o.p("da"), View):
+                bn_of_da[vkey(o.p("da"))] = k
         Es = set(E)
         changed = True
         while changed:
@@ -1661,15 +1603,15 @@ class Plan:
             for k in sorted(Es):
                 o = ops[k]
                 c = o["code"]
-                if c == "UZ_OP_BN_RELU_FWD" and o["i"][9] > 0 and ywriter.get(vkey(o["p"][0])) not in Es:
+                if c == "UZ_OP_BN_RELU_FWD" and o.i("nslab") > 0 and ywriter.get(vkey(o.p("y"))) not in Es:
                     Es.discard(k); changed = True                 # its convolution leaves slabs for it outside the chain
-                elif c == "UZ_OP_CONV_FWD" and o["i"][9] and bn_of_y.get(vkey(o["p"][3])) not in Es:
+                elif c == "UZ_OP_CONV_FWD" and o.i("slabs_only") and bn_of_y.get(vkey(o.p("y"))) not in Es:
                     Es.discard(k); changed = True
-                elif c == "UZ_OP_BN_RELU_BWD" and len(o["i"]) > 11 and o["i"][11] > 0:
-                    dg = dgrad_of_dx.get(vkey(o["p"][0]), [])
+                elif c == "UZ_OP_BN_RELU_BWD" and o.i("nslab") > 0:
+                    dg = dgrad_of_dx.get(vkey(o.p("da")), [])
                     if len(dg) != 1 or dg[0] not in Es:
                         Es.discard(k); changed = True             # dA arrives as slabs of a data gradient that is not in the chain
-                elif c == "UZ_OP_CONV_BWD_DATA" and len(o["i"]) > 10 and o["i"][10] == 3 and bn_of_da.get(vkey(o["p"][2])) not in Es:
+                elif c == "UZ_OP_CONV_BWD_DATA" and o.i("fold") == 3 and bn_of_da.get(vkey(o.p("dx"))) not in Es:
                     Es.discard(k); changed = True
                 elif c == "UZ_OP_LATENT_BWD" and not (k + 1 < len(ops) and ops[k + 1]["code"] == "UZ_OP_LATENT_HEADS_BWD_DATA" and (k + 1) in Es):
                     Es.discard(k); changed = True
@@ -1723,7 +1665,7 @@ class Plan:
             level[k] = 1 + max((level[d] for d in deps[k] if d in Es), default=-1)
         imgs = self._chain_imgs.setdefault(which, {})
         G = int(os.environ.get("UZ_CHAIN_WGS" if fwd else "UZ_CHAIN_WGS_BWD", str(self.chain_wgs if fwd else self.chain_wgs_bwd)))
-        sub = []
+        sub, flops = [], 0.0
 
         def emit(k, code, p, i, f=(), lvl=None):
             sub.append(dict(code=code, p=list(p), i=[int(v) for v in i], f=list(f), level=level[k] if lvl is None else lvl, orig=ops[k], k=k))
@@ -1733,68 +1675,76 @@ class Plan:
                 imgs[wkey] = dict(mc=mc, kc=kc, cin=cin, dgrad=dgrad, bytes=self.L.uz_chain_packed_bytes(kc, mc), blocks=self.L.uz_chain_pack_blocks(kc, mc))
             return ("chainimg", which, wkey)
 
+        def weight_key(w):
+            kind, wkey, offset = w
+            assert kind == "param" and offset == 0, w
+            return wkey
+
         extra_levels = {}            # op index -> 1 when a slab-sum phase was put behind it (shifts everything that depends on it)
         slab_of = {}
         for k in sorted(Es, key=lambda k: (level[k], k)):
             o = ops[k]
-            c, i, p = o["code"], o["i"], o["p"]
+            c, I, P = o["code"], o.i, o.p
             if c == "UZ_OP_CONV_FWD":
-                cin, cout, N, H, W = i[0], i[2], i[4], i[5], i[6]
+                _, cin, cout, N, H, W, _ = conv_dims(o)
+                x, w, bias, y = P("x", "w", "bias", "y")
                 if cin <= 4:
-                    emit(k, "UZ_CH_CONV3_SMALL", [p[0], p[1], p[2], p[3]], [cin, i[1], cout, i[3], N, H, W])
+                    emit(k, "UZ_CH_CONV3_SMALL", [x, w, bias, y], [cin, I("ctot_x"), cout, I("ctot_y"), N, H, W])
                     continue
-                bk = bn_of_y.get(vkey(p[3]))
+                bk = bn_of_y.get(vkey(y))
                 S = self.L.uz_chain_conv_ksplit(cin, cout, N, H, W, G) if (bk in Es) else 1
-                wkey = p[1][1]
-                assert p[1][0] == "param" and p[1][2] == 0, p[1]
+                wkey = weight_key(w)
                 slab = self.vec(wkey + ":chslab", S * N * cout * H * W) if S > 1 else None
                 if slab is not None:
-                    slab_of[vkey(p[3])] = (slab, S)
-                emit(k, "UZ_CH_CONV3", [p[0], image(wkey, cout, cin, cin, 0), p[2] if S == 1 else None, p[3] if S == 1 else None, slab, p[5], p[6]],
-                     [cin, i[1], cout, i[3], N, H, W, S, 0])
+                    slab_of[vkey(y)] = (slab, S)
+                emit(k, "UZ_CH_CONV3", [x, image(wkey, cout, cin, cin, 0), bias if S == 1 else None, y if S == 1 else None, slab, P("x_amax"), P("w_amax")],
+                     [cin, I("ctot_x"), cout, I("ctot_y"), N, H, W, S, 0])
+                flops += 2.0 * N * H * W * cin * cout * 9
                 self._packs["fwd"].pop(wkey, None)          # the image replaces the per-tape LDS image of the split kernels
             elif c == "UZ_OP_BN_RELU_FWD":
-                slab, S = slab_of.get(vkey(p[0]), (None, 1))
-                cbias = ops[ywriter[vkey(p[0])]]["p"][2] if S > 1 else None
-                emit(k, "UZ_CH_BN_FWD", [p[0], p[1], p[2], p[3], p[4], p[5], p[6], slab, p[8], cbias], [i[0], i[1], i[2], i[3], i[4] * i[5], i[7], S], [o["f"][0], o["f"][1]])
+                slab, S = slab_of.get(vkey(P("y")), (None, 1))
+                cbias = ops[ywriter[vkey(P("y"))]].p("bias") if S > 1 else None
+                emit(k, "UZ_CH_BN_FWD", [*P("y", "gamma", "beta", "running_mean", "running_var", "save", "a"), slab, P("a_amax"), cbias],
+                     [*I("C", "ctot_y", "ctot_a", "N"), I("H") * I("W"), I("relu"), S], o.f("eps", "momentum"))
             elif c == "UZ_OP_AVGPOOL_FWD":
-                emit(k, "UZ_CH_AVGPOOL_FWD", [p[0], p[1], p[2], p[3]], i[:6])
+                emit(k, "UZ_CH_AVGPOOL_FWD", P("x", "y", "x_amax", "y_amax"), I("C", "ctot_x", "ctot_y", "N", "H", "W"))
             elif c == "UZ_OP_BILINEAR_FWD":
-                emit(k, "UZ_CH_BILINEAR_FWD", [p[0], p[1], p[2], p[3]], i[:7])
+                emit(k, "UZ_CH_BILINEAR_FWD", P("x", "y", "x_amax", "y_amax"), I("C", "ctot_x", "ctot_y", "N", "H", "W", "align_corners"))
             elif c == "UZ_OP_LATENT_HEADS_FWD":
-                emit(k, "UZ_CH_HEADS_FWD", p[:10], [i[0], i[1], i[3], i[4] * i[5], i[6]])
+                emit(k, "UZ_CH_HEADS_FWD", o["p"], [*I("cin", "ctot_h", "N"), I("H") * I("W"), I("act")])
             elif c == "UZ_OP_BN_RELU_BWD":
-                slab, S = slab_of.get(("da",) + vkey(p[0]), (None, 1))
-                emit(k, "UZ_CH_BN_BWD", [p[0], p[1], p[2], p[4], p[5].view, p[6], p[7], p[8], p[10], slab, p[3]], [i[1], i[0], i[2], i[4], i[5] * i[6], i[7], S])
+                slab, S = slab_of.get(("da",) + vkey(P("da")), (None, 1))
+                emit(k, "UZ_CH_BN_BWD", [*P("da", "y", "gamma", "save"), P("dy").view, *P("dgamma", "dbeta", "dbias", "dy_amax"), slab, P("beta")],
+                     [*I("C", "ctot_da", "ctot_y", "N"), I("H") * I("W"), I("relu"), S])
             elif c == "UZ_OP_CONV_BWD_DATA":
-                cout, cin, N, H, W, acc = i[0], i[2], i[4], i[5], i[6], i[8]
-                wkey = p[1][1]
-                assert p[1][0] == "param" and p[1][2] == 0, p[1]
+                _, cin, cout, N, H, W, _ = conv_dims(o)
+                acc, dy, dx = I("accumulate"), P("dy").view, P("dx")
+                wkey = weight_key(P("w"))
                 if cin <= 4:
-                    emit(k, "UZ_CH_CONV3_SMALL_BWD_DATA", [p[0].view, p[1], p[2]], [cin, i[3], cout, i[1], N, H, W, acc])
+                    emit(k, "UZ_CH_CONV3_SMALL_BWD_DATA", [dy, P("w"), dx], [cin, I("ctot_dx"), cout, I("ctot_dy"), N, H, W, acc])
                     continue
                 S = self.L.uz_chain_conv_ksplit(cout, cin, N, H, W, G)
-                folded = len(i) > 10 and i[10] == 3              # the consumer's BatchNorm backward adds the slabs (the only reader of a dA this op alone writes)
+                folded = I("fold") == 3                           # the consumer's BatchNorm backward adds the slabs (the only reader of a dA this op alone writes)
                 slab = self.vec(wkey + ":chdslab", S * N * cin * H * W) if S > 1 else None
-                emit(k, "UZ_CH_CONV3", [p[0].view, image(wkey, cin, cout, cin, 1), None, p[2] if S == 1 else None, slab, p[4], p[5]],
-                     [cout, i[1], cin, i[3], N, H, W, S, acc if S == 1 else 0])
+                emit(k, "UZ_CH_CONV3", [dy, image(wkey, cin, cout, cin, 1), None, dx if S == 1 else None, slab, P("dy_amax"), P("w_amax")],
+                     [cout, I("ctot_dy"), cin, I("ctot_dx"), N, H, W, S, acc if S == 1 else 0])
+                flops += 2.0 * N * H * W * cout * cin * 9
                 if S > 1 and folded:
-                    slab_of[("da",) + vkey(p[2])] = (slab, S)
+                    slab_of[("da",) + vkey(dx)] = (slab, S)
                 elif S > 1:
                     # other writers / readers of dx: a reduction phase of its own right behind the convolution
                     extra_levels[k] = 1
-                    emit(k, "UZ_CH_SLAB_SUM", [slab, p[2]], [S, N, cin, i[3], H * W, acc], lvl=level[k] + 0.5)
+                    emit(k, "UZ_CH_SLAB_SUM", [slab, dx], [S, N, cin, I("ctot_dx"), H * W, acc], lvl=level[k] + 0.5)
                 self._packs["bwd"].pop(wkey, None)
             elif c == "UZ_OP_AVGPOOL_BWD":
-                emit(k, "UZ_CH_AVGPOOL_BWD", [p[0], p[1]], i[:7])
+                emit(k, "UZ_CH_AVGPOOL_BWD", P("dy", "dx"), I("C", "ctot_dy", "ctot_dx", "N", "H", "W", "accumulate"))
             elif c == "UZ_OP_BILINEAR_BWD":
-                emit(k, "UZ_CH_BILINEAR_BWD", [p[0], p[1]], i[:8])
+                emit(k, "UZ_CH_BILINEAR_BWD", P("dy", "dx"), I("C", "ctot_dy", "ctot_dx", "N", "H", "W", "align_corners", "accumulate"))
             elif c == "UZ_OP_LATENT_BWD":
                 h = ops[k + 1]
-                hi, hp = h["i"], h["p"]
                 # (head a = the sigma head: LATENT_HEADS_BWD_DATA p = g_pre, g_mu, w_sigma, w_mu, dh)
-                emit(k, "UZ_CH_LATENT_HEADS_BWD", [p[0], p[1], p[2], p[3], p[4], p[5], p[6], hp[2], hp[3], hp[4]], [hi[1], hi[2], hi[3], hi[4] * hi[5], i[0], hi[6]],
-                     lvl=level[k + 1])
+                emit(k, "UZ_CH_LATENT_HEADS_BWD", [*o["p"], *h.p("w_a", "w_b", "dh")],
+                     [*h.i("cin", "ctot_h", "N"), h.i("H") * h.i("W"), I("act"), h.i("accumulate")], lvl=level[k + 1])
             elif c == "UZ_OP_LATENT_HEADS_BWD_DATA":
                 pass                                              # fused into the sub-op of the LATENT_BWD in front of it
             else:
@@ -1818,18 +1768,14 @@ class Plan:
         # access of the whole launch = the union of what its sub-ops touch (the packed images instead of the split kernels' ones)
         acc_ops = []
         for k in sorted(Es):
-            q = dict(ops[k])
-            q["p"] = list(q["p"])
-            if q["code"] == "UZ_OP_CONV_FWD" and len(q["p"]) > 8:
-                q["p"][8] = None
-            if q["code"] == "UZ_OP_CONV_BWD_DATA" and len(q["p"]) > 6:
-                q["p"][6] = None
+            q = ops[k].clone()
+            if q["code"] in ("UZ_OP_CONV_FWD", "UZ_OP_CONV_BWD_DATA"):
+                q.set(p={"w_image": None})
             acc_ops.append(q)
         n_ph = 1 + max(e["level"] for e in sub)
-        flops = sum(2.0 * e["i"][4] * e["i"][5] * e["i"][6] * e["i"][0] * e["i"][2] * 9 for e in sub if e["code"] == "UZ_CH_CONV3")
-        chain_op = dict(code="UZ_OP_CHAIN", p=[("chaintab", idx, "ops"), ("chaintab", idx, "phases"), ("chaintab", idx, "state")],
-                        i=[n_ph, G, len(sub)], f=[], n=0, gid=("chain", idx), _acc_ops=acc_ops, _which=which,
-                        _cost_s=n_ph * 12e-6 + flops / 100e12)        # (first guess for the lane scheduler; tune_schedule measures it)
+        chain_op = _ops.make("UZ_OP_CHAIN", p=[("chaintab", idx, "ops"), ("chaintab", idx, "phases"), ("chaintab", idx, "state")],
+                             i=[n_ph, G, len(sub)], gid=("chain", idx), _acc_ops=acc_ops, _which=which,
+                             _cost_s=n_ph * 12e-6 + flops / 100e12)   # (flops: the chain's 3 x 3 convolutions; first guess for the lane scheduler, tune_schedule measures it)
         new_ops = [ops[k] for k in range(len(ops)) if k in anc] + [chain_op] + [ops[k] for k in range(len(ops)) if k not in anc and k not in Es]
         ops[:] = new_ops
         self.chain_info.setdefault(which, []).append(dict(net=net, ops=len(sub), phases=n_ph, convs=sum(e["code"] == "UZ_CH_CONV3" for e in sub), workgroups=G))
@@ -1933,7 +1879,7 @@ class Plan:
                 self._newgroup()
                 self._emit(self.bwd_ops, "UZ_OP_EVENT_RECORD", p=[("event", b), ("gflat_range", lo, hi)])
         self._bwd = []
-        self._round4_passes()
+        self._split_storage_passes()
         self._bn_offchain_pass()
         self._b16_pass()
         self._chain_pass()
@@ -1962,14 +1908,14 @@ class Plan:
             # a scheduling group of its own (gid head - 1) behind the bound measurement: only the layers that READ the packed images wait for
             # it - the first layers of both encoders (1 / 3 input channels: fp32 matrix path) start beside it (40 us off the forward's chain)
             own = os.environ.get("UZ_PACK_OWN_GROUP", "1") == "1"
-            pack_ops[which] = dict(code="UZ_OP_PACK_WEIGHTS", p=[self.ptr_table(refs), ("amaxw", 0), self._packbuf[which]], i=[len(lst), rows], f=[], n=0,
-                                   gid=head - 1 if own else head)
+            pack_ops[which] = _ops.make("UZ_OP_PACK_WEIGHTS", p=[self.ptr_table(refs), ("amaxw", 0), self._packbuf[which]], i=[len(lst), rows],
+                                        gid=head - 1 if own else head)
         if "bwd" in pack_ops and self.bwd_ops:
             self.bwd_ops[:0] = [pack_ops["bwd"]]
         if self.fwd_ops:
             ops0 = []
-            ops0.append(dict(code="UZ_OP_MEMSET", p=[("amaxrange", 0, self.n_amax_fwd)], i=[], f=[], n=4 * _AMAX_FLOATS * self.n_amax_fwd, gid=head))
-            ops0.append(dict(code="UZ_OP_ABSMAX", p=[("pflat",), ("amaxw", 0)], i=[], f=[], n=self.ptab.n_params, gid=head))
+            ops0.append(_ops.make("UZ_OP_MEMSET", p=[("amaxrange", 0, self.n_amax_fwd)], n=4 * _AMAX_FLOATS * self.n_amax_fwd, gid=head))
+            ops0.append(_ops.make("UZ_OP_ABSMAX", p=[("pflat",), ("amaxw", 0)], n=self.ptab.n_params, gid=head))
             if "fwd" in pack_ops:
                 ops0.append(pack_ops["fwd"])
             self.fwd_ops[:0] = ops0
@@ -1977,13 +1923,12 @@ class Plan:
         # behind an optimiser step or a load_state_dict the bound may be stale, and a bound more than 4x too small overflows the
         # fp16 pieces.  A tape with a convolution on the split path therefore re-measures the bound at its own head.
         for name, ops in self.extra_ops.items():
-            if any(o["code"] == "UZ_OP_CONV_FWD" and o["i"][7] == 3 and
-                   self.L.uz_conv_route(0, o["i"][0], o["i"][2], o["i"][4], o["i"][5], o["i"][6], 3) == 1 for o in ops):
-                ops[:0] = [dict(code="UZ_OP_MEMSET", p=[("amaxrange", 0, 1)], i=[], f=[], n=4 * _AMAX_FLOATS, gid=head),
-                           dict(code="UZ_OP_ABSMAX", p=[("pflat",), ("amaxw", 0)], i=[], f=[], n=self.ptab.n_params, gid=head)]
+            if any(o["code"] == "UZ_OP_CONV_FWD" and o.i("ks") == 3 and self.L.uz_conv_route(*conv_dims(o)) == 1 for o in ops):
+                ops[:0] = [_ops.make("UZ_OP_MEMSET", p=[("amaxrange", 0, 1)], n=4 * _AMAX_FLOATS, gid=head),
+                           _ops.make("UZ_OP_ABSMAX", p=[("pflat",), ("amaxw", 0)], n=self.ptab.n_params, gid=head)]
         if self.bwd_ops and bwd_slots:
-            self.bwd_ops[:0] = [dict(code="UZ_OP_MEMSET", p=[("amaxrange", self.n_amax_fwd, self.n_amax)], i=[], f=[],
-                                     n=4 * _AMAX_FLOATS * (self.n_amax - self.n_amax_fwd), gid=head)]
+            self.bwd_ops[:0] = [_ops.make("UZ_OP_MEMSET", p=[("amaxrange", self.n_amax_fwd, self.n_amax)],
+                                          n=4 * _AMAX_FLOATS * (self.n_amax - self.n_amax_fwd), gid=head)]
         # arena layout
         off = 0
         for slot in self.__dict__.get("_rev_slots", {}).values():
@@ -2113,7 +2058,7 @@ class Plan:
         for k, o in enumerate(ops):
             e = arr[k]
             e.code = self.codes[o["code"]]
-            assert len(o["i"]) <= 15 and len(o["f"]) <= 4 and len(o["p"]) <= 12, o["code"]
+            assert len(o["i"]) <= len(e.i) and len(o["f"]) <= len(e.f) and len(o["p"]) <= len(e.p), o["code"]
             for j, v in enumerate(o["i"]):
                 e.i[j] = v
             for j, v in enumerate(o["f"]):
@@ -2124,32 +2069,9 @@ class Plan:
         return arr, len(ops)
 
     # ------------------------------------------------------------------ lane scheduling
-    # Which p[] slots an op writes (every other slot is read).  Scratch slots are private to a
+    # Which p[] slots an op writes (every other slot is read) is part of its schema (_ops.writes).  Scratch slots are private to a
     # group and parameters are read-only inside a tape, so neither creates a dependency.
-    _WRITES = {
-        "UZ_OP_CONV_FWD": (3, 9), "UZ_OP_CONV_BWD_DATA": (2, 8, 9), "UZ_OP_CONV_BWD_WEIGHT": (2, 3, 8),      # (slabs-only data gradient: see _op_writes)
-        "UZ_OP_BN_RELU_FWD": (3, 4, 5, 6), "UZ_OP_BN_RELU_BWD": (5, 6, 7, 8), "UZ_OP_RELU_BWD": (2, 3),
-        "UZ_OP_AVGPOOL_FWD": (1,), "UZ_OP_AVGPOOL_BWD": (1, 3, 4), "UZ_OP_BILINEAR_FWD": (1,), "UZ_OP_BILINEAR_BWD": (1, 3, 4),
-        "UZ_OP_NEAREST_FWD": (1,), "UZ_OP_NEAREST_BWD": (1,), "UZ_OP_SPATIAL_MEAN_FWD": (1,), "UZ_OP_SPATIAL_MEAN_BWD": (1,),
-        "UZ_OP_POSTERIOR_INPUT": (2,), "UZ_OP_LATENT_FWD": (3, 4), "UZ_OP_LATENT_BWD": (5, 6),
-        "UZ_OP_LATENT_HEADS_FWD": (6, 7, 8, 9), "UZ_OP_LATENT_HEADS_BWD_DATA": (4,), "UZ_OP_LATENT_HEADS_BWD_WEIGHT": (3, 4, 5, 6),
-        "UZ_OP_KL_FWD": (4,), "UZ_OP_KL_BWD": (5, 6, 7, 8), "UZ_OP_CE_FWD": (2,), "UZ_OP_CE_BWD": (1,),
-        "UZ_OP_SUM_TERMS": (1,), "UZ_OP_SCALE": (0,), "UZ_OP_COPY": (0,), "UZ_OP_MEMSET": (0,),
-        "UZ_OP_L2_NORMS": (2,), "UZ_OP_L2_NORMS_BWD": (4,),
-        "UZ_OP_BCAST_CHANNELS": (1,), "UZ_OP_BCAST_CHANNELS_BWD": (1,), "UZ_OP_EVENT_RECORD": (0,), "UZ_OP_ABSMAX": (1,),
-        "UZ_OP_ADD_VIEWS": (2,), "UZ_OP_W3D_PERMUTE": (1,), "UZ_OP_AVGPOOL3D_FWD": (1,), "UZ_OP_AVGPOOL3D_BWD": (1,),
-        "UZ_OP_DEPTH_LERP_FWD": (1,), "UZ_OP_DEPTH_LERP_BWD": (1,), "UZ_OP_NEAREST3D_FWD": (1,), "UZ_OP_NEAREST3D_BWD": (1,),
-        "UZ_OP_ABSMAX_COPY": (), "UZ_OP_PACK_WEIGHTS": (2,), "UZ_OP_CHAIN_PACK": (2,), "UZ_OP_CHAN_SUM_PARTIALS": (1,), "UZ_OP_CHAN_SUM_TABLE": (1,), "UZ_OP_WGRAD_REDUCE_TABLE": (1,),
-    }
-
-    def _op_writes(self, o):
-        """p[] slots op `o` writes: the static table, except for a slabs-only data gradient (i[10] == 3: partial sums into p[7], its
-        gradient view p[2] is NOT written - the consumer's BatchNorm backward reads the slabs instead)."""
-        if o["code"] == "UZ_OP_CONV_BWD_DATA" and len(o["i"]) > 10 and o["i"][10] == 3:
-            return (7,)
-        if o["code"] == "UZ_OP_BN_RELU_FWD" and len(o["i"]) > 11 and o["i"][11]:
-            return (3, 4, 5) if o["i"][11] == 1 else (6,)          # phase 1: statistics table + running buffers; phase 2: the activation only
-        return self._WRITES[o["code"]]
+    _WRITES = _ops.WRITES          # the static part, by op code: an alias kept for callers that read Plan._WRITES; nothing is restated here
 
     def _access(self, o):
         """(reads, writes, accumulates) of op `o` as resource ranges.  Accumulates (bound slots only) commute with each other
@@ -2164,7 +2086,7 @@ class Plan:
             #  tape the launch both accumulates into and reads those slots: declare them written)
             writes.extend(accs)
             return reads, writes, []
-        wr = self._op_writes(o)
+        wr = _ops.writes(o)
         reads, writes, accs = [], [], []
         for j, r in enumerate(o["p"]):
             if j in wr:
@@ -2232,28 +2154,30 @@ class Plan:
     def _op_cost(o):
         """Rough duration (s) of one op on MI355X - only the RELATIVE sizes matter: the list scheduler
         below uses them to decide which chains can share a lane."""
-        c, i = o["code"], o["i"]
+        c = o["code"]
         if "_cost_s" in o:
             return o["_cost_s"]
-        if c in ("UZ_OP_CONV_FWD", "UZ_OP_CONV_BWD_DATA", "UZ_OP_CONV_BWD_WEIGHT"):
-            cin, cout, N, H, W, ks = i[0], i[2], i[4], i[5], i[6], i[7]
+        if c in _ops.CONV_KIND:
+            kind, cin, cout, N, H, W, ks = conv_dims(o)
             flop = 2.0 * N * H * W * cin * cout * ks * ks
             # measured fp32-equivalent TFLOP/s per plane size at batch 32 (tools/op_profile.py), forward / data
             # gradient and weight gradient; small channel counts and 1x1 kernels run far below these
             px = N * H * W
             table = ((262144, 180, 150), (65536, 190, 159), (16384, 148, 122), (4096, 97, 85), (1024, 37, 31), (256, 11, 9), (0, 3, 2.2))
-            rate = next((f if c != "UZ_OP_CONV_BWD_WEIGHT" else w) for lim, f, w in table if px >= lim) * 1e12
+            rate = next((f if kind != 2 else w) for lim, f, w in table if px >= lim) * 1e12
             if min(cin, cout) < 32 or ks == 1:
                 rate = min(rate, 20e12)
             return flop / rate + 4e-6
-        if c == "UZ_OP_BN_RELU_FWD":
-            if len(i) > 11 and i[11] == 1:
-                return 6e-6                                          # statistics from the convolution's partials: one small launch
-            return i[0] * i[3] * i[4] * i[5] * 12.0 / 4e12 + 10e-6
-        if c in ("UZ_OP_BN_RELU_BWD", "UZ_OP_RELU_BWD"):
-            return i[1] * i[4] * i[5] * i[6] * 20.0 / 4e12 + 14e-6
+        if c == "UZ_OP_BN_RELU_FWD" and o.i("phase") == 1:
+            return 6e-6                                              # statistics from the convolution's partials: one small launch
+        if c in ("UZ_OP_BN_RELU_FWD", "UZ_OP_BN_RELU_BWD", "UZ_OP_RELU_BWD"):
+            C_, N, H, W = o.i("C", "N", "H", "W")
+            if c == "UZ_OP_BN_RELU_FWD":
+                return C_ * N * H * W * 12.0 / 4e12 + 10e-6
+            return C_ * N * H * W * 20.0 / 4e12 + 14e-6
         if c in ("UZ_OP_AVGPOOL_FWD", "UZ_OP_AVGPOOL_BWD", "UZ_OP_BILINEAR_FWD", "UZ_OP_BILINEAR_BWD", "UZ_OP_NEAREST_FWD", "UZ_OP_NEAREST_BWD"):
-            return i[0] * i[3] * i[4] * i[5] * 24.0 / 2e12 + 6e-6
+            C_, N, H, W = o.i("C", "N", "H", "W")
+            return C_ * N * H * W * 24.0 / 2e12 + 6e-6
         return 6e-6
 
     @staticmethod
@@ -2280,7 +2204,7 @@ class Plan:
         elif c in ("UZ_OP_BILINEAR_FWD", "UZ_OP_BILINEAR_BWD", "UZ_OP_NEAREST_FWD", "UZ_OP_NEAREST_BWD"):
             us = 18.0 + 0.42 * m
         elif c == "UZ_OP_WGRAD_REDUCE_TABLE":
-            us = 8.0 + 0.0031 * o["i"][1]                 # HBM-bound: PHiSeg's 106 layers = 95 301 blocks take 300 us
+            us = 8.0 + 0.0031 * o.i("total_blocks")       # HBM-bound: PHiSeg's 106 layers = 95 301 blocks take 300 us
         elif c in ("UZ_OP_MEMSET",):
             us = 8.0
         elif c in ("UZ_OP_W3D_PERMUTE", "UZ_OP_AVGPOOL3D_FWD", "UZ_OP_AVGPOOL3D_BWD", "UZ_OP_DEPTH_LERP_FWD", "UZ_OP_DEPTH_LERP_BWD",
@@ -2293,31 +2217,34 @@ class Plan:
 
     @staticmethod
     def _vol_bytes(o):
-        """Bytes a volume / view op moves (input + output once), from its i[] (C, ..., D, H, W in the layouts of include/uz_api.h)."""
-        c, i = o["code"], o["i"]
+        """Bytes a volume / view op moves (input + output once)."""
+        c = o["code"]
         if c == "UZ_OP_W3D_PERMUTE":
-            return 8.0 * i[0] * i[1] * 27
+            return 8.0 * o.i("cout") * o.i("cin") * 27
         if c == "UZ_OP_ADD_VIEWS":
-            return 12.0 * i[3] * i[4] * i[5] * i[6]
-        C_, D, H, W = i[0], i[3], i[4], i[5]
+            C_, N, H, W = o.i("C", "N", "H", "W")
+            return 12.0 * C_ * N * H * W
+        C_, D, H, W = o.i("C", "D", "H", "W")
         n = float(C_) * D * H * W
         if c in ("UZ_OP_AVGPOOL3D_FWD", "UZ_OP_AVGPOOL3D_BWD"):
             return 4.0 * n * (1.0 + 0.125)
         if c in ("UZ_OP_DEPTH_LERP_FWD", "UZ_OP_DEPTH_LERP_BWD"):
             return 4.0 * n * 3.0
-        return 4.0 * n * (1.0 + float(i[6]) * i[6] * (i[7] if len(i) > 7 else 1))
+        return 4.0 * n * (1.0 + float(o.i("factor")) * o.i("factor") * o.i("factor_z"))          # nearest-neighbour 3-D
 
     @staticmethod
     def _op_heavy(o):
         """True for ops that fill the chip on their own (only one of those is simulated in flight at a time)."""
-        c, i = o["code"], o["i"]
-        if c in ("UZ_OP_CONV_FWD", "UZ_OP_CONV_BWD_DATA", "UZ_OP_CONV_BWD_WEIGHT"):
-            return i[4] * i[5] * i[6] >= 2048 and i[0] * i[2] >= 32 * 32      # measured: 512..8192 pixels all within 1 %
+        c = o["code"]
+        if c in _ops.CONV_KIND:
+            _, cin, cout, N, H, W, _ = conv_dims(o)
+            return N * H * W >= 2048 and cin * cout >= 32 * 32      # measured: 512..8192 pixels all within 1 %
         if c in ("UZ_OP_BN_RELU_FWD", "UZ_OP_BN_RELU_BWD", "UZ_OP_RELU_BWD"):
-            C, N, H, W = (i[0], i[3], i[4], i[5]) if c == "UZ_OP_BN_RELU_FWD" else (i[1], i[4], i[5], i[6])
-            return C * N * H * W >= 4.0e6
+            C_, N, H, W = o.i("C", "N", "H", "W")
+            return C_ * N * H * W >= 4.0e6
         if c in ("UZ_OP_AVGPOOL_FWD", "UZ_OP_AVGPOOL_BWD", "UZ_OP_BILINEAR_FWD", "UZ_OP_BILINEAR_BWD", "UZ_OP_NEAREST_FWD", "UZ_OP_NEAREST_BWD"):
-            return i[0] * i[3] * i[4] * i[5] >= 2.0e6
+            C_, N, H, W = o.i("C", "N", "H", "W")
+            return C_ * N * H * W >= 2.0e6
         return False
 
     def _schedule(self, ops):

@@ -227,7 +227,8 @@ class GradSync:
         pos = {}
         for k, o in enumerate(plan.bwd_ops):
             if o["code"] == "UZ_OP_EVENT_RECORD":
-                pos[o["p"][0][1]] = k
+                _, bucket = o.p("event")
+                pos[bucket] = k
         return sorted(pos, key=pos.get)
 
     def sync(self, plan, serial=False):
