@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Forward and data gradient of the small-plane 3x3 convolutions through the C ABI against fp64 (the LDS-free one-wave kernel,
-conv_mfma.hip conv_free_kernel, takes the split-K calls with N * H * W <= UZ_CONV_FREE_PX; 0 = the LDS-staged kernel).  Ragged channel
-counts, channel-slice views, accumulate.  Prints one line per case and ALL OK; exit code 1 on a miss."""
+"""Forward and data gradient of the small-plane 3x3 convolutions through the C ABI against fp64: the 2 x 2 ... 8 x 8 planes, whose
+channel loop the LDS-staged kernel of conv_mfma.hip splits (split-K slabs + ordered reduce).  Ragged channel counts, channel-slice views,
+accumulate.  Prints one line per case and ALL OK; exit code 1 on a miss.  A check of the product's route, run by
+tests/test_conv_abi_checks_gpu.py."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

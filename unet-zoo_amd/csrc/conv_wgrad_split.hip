@@ -70,12 +70,8 @@ struct WS {
 // group; the four pixel quarters are folded through LDS at the end; 74 KB of LDS -> two workgroups per CU)
 // XF / DF = storage format of X / dY: 0 fp32 values, 1 split storage (two fp16 pieces per word, NP == 2), 2 bf16 storage (2-byte
 // elements, NP == 1: staged as they are - no conversion, half the bytes)
-// M16: the matrix products on v_mfma_f32_16x16x32_f16 instead of 32x32x16 (64-channel tiles of the 32-wide geometry, two-piece mode): a
-// wave's 32 x 32 block becomes 2 x 2 blocks of 16 x 16, one tile row (32 pixels) is one K step; same fragment bytes, same MFMA cycles,
-// same accumulator registers - the chip holds a higher clock on this shape under load (MI355X_MICROARCH.md, DVFS item 7)
-template <int TWv, int CT, int NP, int XF = 0, int DF = 0, int M16 = 0>
+template <int TWv, int CT, int NP, int XF = 0, int DF = 0>
 __global__ __launch_bounds__(NT) void wgrad_split_kernel(const WS p) {
-    static_assert(!M16 || (CT == 64 && TWv == 32 && NP == 2), "16x16x32 form: 64-channel tiles, 32-wide rows, two-piece mode");
     constexpr bool XPK = XF == 1, DPK = DF == 1, XB = XF == 2, DB = DF == 2;
     constexpr unsigned XE = XB ? 2u : 4u, DE = DB ? 2u : 4u;      // bytes per element
     static_assert(NP == 2 || (!XPK && !DPK), "split storage is the two-piece fp16 format");
@@ -250,19 +246,11 @@ __global__ __launch_bounds__(NT) void wgrad_split_kernel(const WS p) {
     auto run = [&](auto ntap_c, auto tap0_c) __attribute__((always_inline)) {
         constexpr int NTAP = decltype(ntap_c)::value, TAP0 = decltype(tap0_c)::value;
         constexpr int DY0 = TAP0 / 3;                        // first patch-row offset this tap group needs (0 or 1)
-        f32x16 acc[M16 ? 1 : NTAP];
-        f32x4 acc16[M16 ? NTAP : 1][2][2];
+        f32x16 acc[NTAP];
 #pragma unroll
-        for (int k = 0; k < (M16 ? 1 : NTAP); ++k)
+        for (int k = 0; k < NTAP; ++k)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-#pragma unroll
-        for (int k = 0; k < (M16 ? NTAP : 1); ++k)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { acc16[k][0][0][r] = 0.f; acc16[k][0][1][r] = 0.f; acc16[k][1][0][r] = 0.f; acc16[k][1][1][r] = 0.f; }
-        const int l15 = lane & 15, kg = lane >> 4;
-        const char* Ab16 = dYl + (wm * 32 + l15) * DYROW + kg * 16;
-        const char* Bb16 = Xl + (wn * 32 + l15) * XCH + kg * 16;
         int t = split;
         long long st0 = 0, st1 = 0, stl = 0, rt0 = 0;
         if (p.stamps) { st0 = __builtin_amdgcn_s_memtime(); rt0 = __builtin_amdgcn_s_memrealtime(); }
@@ -274,54 +262,6 @@ __global__ __launch_bounds__(NT) void wgrad_split_kernel(const WS p) {
             lstore(t);
             __syncthreads();
             if (p.stamps) { const long long tb = __builtin_amdgcn_s_memtime(); if (t == split) st1 = tb; else stl += tb - ta; }
-            if constexpr (M16) {
-#pragma unroll
-                for (int sr = 0; sr < TH; ++sr) {            // one tile row = 32 pixels = one K step
-                    gload(t + p.S, 2 * sr);
-                    gload(t + p.S, 2 * sr + 1);
-                    u32x4 a[2][NP];
-#pragma unroll
-                    for (int sa = 0; sa < 2; ++sa)
-#pragma unroll
-                        for (int q = 0; q < NP; ++q) a[sa][q] = *reinterpret_cast<const u32x4*>(Ab16 + q * DYPLANE + sa * 16 * DYROW + sr * TW * 2);
-#pragma unroll
-                    for (int d = 0; d < 2; ++d)
-#pragma unroll
-                        for (int sb = 0; sb < 2; ++sb) {
-                            u32x4 v[NP];
-                            unsigned v4[NP];
-#pragma unroll
-                            for (int q = 0; q < NP; ++q) {
-                                const char* src = Bb16 + q * XPLANE + sb * 16 * XCH + (sr + DY0 + d) * XROW;
-                                v[q] = *reinterpret_cast<const u32x4*>(src);
-                                v4[q] = *reinterpret_cast<const unsigned*>(src + 16);
-                            }
-#pragma unroll
-                            for (int dx = 0; dx < 3; ++dx) {
-                                const int tap = (DY0 + d) * 3 + dx, k = tap - TAP0;
-                                if (k >= 0 && k < NTAP) {
-                                    u32x4 b[NP];
-#pragma unroll
-                                    for (int q = 0; q < NP; ++q) {
-                                        if (dx == 0) b[q] = v[q];
-                                        else if (dx == 2) b[q] = u32x4{v[q].y, v[q].z, v[q].w, v4[q]};
-                                        else b[q] = u32x4{__builtin_amdgcn_alignbit(v[q].y, v[q].x, 16), __builtin_amdgcn_alignbit(v[q].z, v[q].y, 16),
-                                                          __builtin_amdgcn_alignbit(v[q].w, v[q].z, 16), __builtin_amdgcn_alignbit(v4[q], v[q].w, 16)};
-                                    }
-                                    const int kc = k < 0 ? 0 : (k >= NTAP ? NTAP - 1 : k);
-#pragma unroll
-                                    for (int sa = 0; sa < 2; ++sa) {
-                                        f32x4 c = acc16[kc][sa][sb];
-                                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[sa][1]), __builtin_bit_cast(f16x8, b[0]), c, 0, 0, 0);
-                                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[sa][0]), __builtin_bit_cast(f16x8, b[1]), c, 0, 0, 0);
-                                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[sa][0]), __builtin_bit_cast(f16x8, b[0]), c, 0, 0, 0);
-                                        acc16[kc][sa][sb] = c;
-                                    }
-                                }
-                            }
-                        }
-                }
-            } else
 #pragma unroll
             for (int si = 0; si < PT / 16 / WK; ++si) {
                 // A portion of the next tile's loads per k-step, in flight during the MFMAs.  Unconditional: behind the last tile the
@@ -404,26 +344,9 @@ __global__ __launch_bounds__(NT) void wgrad_split_kernel(const WS p) {
         }
         float* out = p.slab + (size_t)split * 9 * p.Cout * p.Cin;
         const float inv_dy = NP == 2 ? uz::split_inv_scale(uz::amax_read(p.dy_amax)) : 1.f;
-        if constexpr (M16) {
-#pragma unroll
-            for (int sb = 0; sb < 2; ++sb) {
-                const int ci = ci0 + wn * 32 + sb * 16 + l15;
-                const float inv_x = uz::split_inv_scale(uz::amax_read((XPK && p.x_amax2 && ci >= p.seg_channels) ? p.x_amax2 : p.x_amax));
-#pragma unroll
-                for (int k = 0; k < NTAP; ++k)
-#pragma unroll
-                    for (int sa = 0; sa < 2; ++sa)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int co = co0 + wm * 32 + sa * 16 + 4 * kg + r;
-                            if (co < p.Cout && ci < p.Cin) out[((size_t)(TAP0 + k) * p.Cout + co) * p.Cin + ci] = acc16[k][sa][sb][r] * inv_dy * inv_x;
-                        }
-            }
-        }
         const int ci = ci0 + wn * 32 + l31;
         // exact powers of two; with two-segment split storage the input scale is a property of the column (ci) - K is pixels here
         const float inv_x = NP == 2 ? uz::split_inv_scale(uz::amax_read((XPK && p.x_amax2 && ci >= p.seg_channels) ? p.x_amax2 : p.x_amax)) : 1.f;
-        if constexpr (!M16) {
 #pragma unroll
         for (int k = 0; k < NTAP; ++k)
 #pragma unroll
@@ -431,7 +354,6 @@ __global__ __launch_bounds__(NT) void wgrad_split_kernel(const WS p) {
                 const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 if (co < p.Cout && ci < p.Cin) out[((size_t)(TAP0 + k) * p.Cout + co) * p.Cin + ci] = acc[k][r] * inv_dy * inv_x;
             }
-        }
         if (p.stamps) {
             __builtin_amdgcn_s_waitcnt(0);
             const long long st3 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
@@ -440,633 +362,6 @@ __global__ __launch_bounds__(NT) void wgrad_split_kernel(const WS p) {
                 o[0] = st0; o[1] = st1; o[2] = stl; o[3] = st2; o[4] = st3; o[5] = rt0; o[6] = rt1; o[7] = (p.T - split + p.S - 1) / p.S;
             }
         }
-    };
-    if (tg == 0) run(std::integral_constant<int, 5>{}, std::integral_constant<int, 0>{});
-    else run(std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{});
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Second form (round 6): 256 threads, one wave per SIMD and workgroup, TWO workgroups per CU.
-// A workgroup still owns a 64 x 64 (co x ci) tile, but each of its four waves carries ALL NINE taps of a 32 x 32 block (144
-// accumulator registers) and the pixel tile is 64 pixels (2 rows x 32 columns or 4 rows x 16):
-//   * a k-step feeds 27 MFMAs from 2 dY fragment reads + 6 X fragment reads (the first form: 13.5 MFMAs from 2 + 4): 0.30 instead of
-//     0.44 ds_read_b128 per MFMA, and the dY fragment is read once for nine taps instead of once per tap group;
-//   * 61 KB of LDS and <= 256 registers per workgroup: two INDEPENDENT workgroups share a CU, so the staging phase of one (global ->
-//     registers -> split -> LDS, behind its barriers) runs under the MFMA phase of the other - the first form's eight waves all stand
-//     in the same phase; launched with one workgroup per CU it leaves half of every CU (registers, LDS, wave slots) to the other lanes'
-//     kernels instead of nothing on half the chip.
-// The price: the haloed X patch is 4 rows for 2 (2x the X bytes from L2 instead of 1.5x).  Same slab layout, same staging helpers.
-constexpr int NT9 = 256, PT9 = 64;
-constexpr int DYROW9 = PT9 * 2 + 16;                     // 144 B = 36 dwords per co row: sixteen lanes' b128 reads land on sixteen different 16-byte slots
-template <int TWv> struct WGeo9 {
-    static constexpr int TW = TWv, TH = PT9 / TWv;
-    static constexpr int XROW = (TWv + 8) * 2;           // 80 / 48 B per patch row
-    static constexpr int PROWS = TH + 2;                 // 4 / 6
-    static constexpr int XCH = PROWS * XROW + 16;        // 336 / 304 B = 84 / 76 dwords per ci: 4 * odd -> conflict-free b128 reads
-};
-
-template <int TWv, int NP, int XF, int DF>
-__global__ __launch_bounds__(NT9, 2) void wgrad9_kernel(const WS p) {
-    constexpr bool XPK = XF == 1, DPK = DF == 1;
-    static_assert(NP == 2 || (!XPK && !DPK), "split storage is the two-piece fp16 format");
-    using GEO = WGeo9<TWv>;
-    constexpr int TW = GEO::TW, TH = GEO::TH, XROW = GEO::XROW, PROWS = GEO::PROWS, XCH = GEO::XCH;
-    constexpr int SROW = TW / 16, KSTEPS = PT9 / 16;
-    constexpr int CT = 64;
-    constexpr int DYPLANE = CT * DYROW9, XPLANE = CT * XCH;
-    constexpr int DQ = PT9 / 4, DQROW = TW / 4, XQ = TW / 4;
-    constexpr int DYSLOTS = CT * DQ / NT9;                            // 4
-    constexpr int XQSLOTS = (CT * PROWS * XQ + NT9 - 1) / NT9;        // 8 / 6
-    constexpr int XPSLOTS = (CT * PROWS + NT9 - 1) / NT9;             // 1 / 2
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    char* dYl = lds;
-    char* Xl = lds + NP * DYPLANE;
-
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wn = wave & 1, wm = wave >> 1;
-    const int wid = uz::xcd_remap(blockIdx.x, gridDim.x);
-    const int nTile = p.nCoT * p.nCiT;
-    const int split = wid / nTile, tl = wid - split * nTile;
-    const int co0 = (tl / p.nCiT) * CT, ci0 = (tl % p.nCiT) * CT;
-
-    for (int i = tid * 16; i < NP * DYPLANE + NP * XPLANE; i += NT9 * 16) *reinterpret_cast<u32x4*>(lds + i) = u32x4{0u, 0u, 0u, 0u};
-
-    const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.dy), 0, (unsigned)(((size_t)(p.N - 1) * p.CoutTot + p.Cout) * p.HW * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rxx = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x), 0, (unsigned)(((size_t)(p.N - 1) * p.CinTot + p.Cin) * p.HW * 4u), 0x00020000);
-
-    f32x4 dreg[DYSLOTS];
-    f32x4 xq[XQSLOTS];
-    float xp[XPSLOTS][2];
-    // the next tile's loads are issued in KSTEPS portions, one per k-step of the MFMA loop (part < 0: all at once, prologue)
-    auto gload = [&](int t, int part) __attribute__((always_inline)) {
-        const int txi = t % p.tilesX, t2 = t / p.tilesX;
-        const int x0 = txi * TW, y0 = (t2 % p.tilesY) * TH, b0 = t2 / p.tilesY;
-        const unsigned dbase = 4u * (unsigned)((b0 * p.CoutTot + co0) * p.HW + y0 * p.W + x0);
-#pragma unroll
-        for (int i = 0; i < DYSLOTS; ++i) {
-            if (part >= 0 && i % KSTEPS != part) continue;
-            const int e = tid + i * NT9, co = e / DQ, q = e % DQ, row = q / DQROW, c4 = (q % DQROW) * 4;
-            const unsigned m = ((y0 + row) < p.H && (co0 + co) < p.Cout) ? 0u : 0xFFFFFFFFu;
-            dreg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rdy, (dbase + 4u * (unsigned)(co * p.HW + row * p.W + c4)) | m, 0, 0));
-        }
-        const int xbase = (b0 * p.CinTot + ci0) * p.HW + y0 * p.W + x0;
-#pragma unroll
-        for (int i = 0; i < XQSLOTS; ++i) {
-            if (part >= 0 && (i + DYSLOTS) % KSTEPS != part) continue;
-            const int e = tid + i * NT9;
-            const int q = e % XQ, r = e / XQ, ci = r / PROWS, prow = r - ci * PROWS;
-            const int yy = y0 + prow - 1;
-            const bool rowok = e < CT * PROWS * XQ && (ci0 + ci) < p.Cin && yy >= 0 && yy < p.H;
-            const int sh = (q == 0 && x0 == 0) ? 1 : 0;           // image column -1: load columns 0.. and shift in lstore
-            const int off = xbase + ci * p.HW + (prow - 1) * p.W + 4 * q - 1 + sh;
-            xq[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rxx, rowok ? 4u * (unsigned)off : 0xFFFFFFFFu, 0, 0));
-        }
-#pragma unroll
-        for (int i = 0; i < XPSLOTS; ++i) {
-            if (part >= 0 && (i + DYSLOTS + XQSLOTS) % KSTEPS != part) continue;
-            const int e = tid + i * NT9;
-            const int ci = e / PROWS, prow = e - ci * PROWS;
-            const int yy = y0 + prow - 1;
-            const bool rowok = e < CT * PROWS && (ci0 + ci) < p.Cin && yy >= 0 && yy < p.H;
-            const int off = xbase + ci * p.HW + (prow - 1) * p.W + TW - 1;
-            xp[i][0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxx, rowok ? 4u * (unsigned)off : 0xFFFFFFFFu, 0, 0));
-            xp[i][1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxx, (rowok && x0 + TW < p.W) ? 4u * (unsigned)(off + 1) : 0xFFFFFFFFu, 0, 0));
-        }
-    };
-    const float sdy = NP == 2 ? uz::split_scale(uz::amax_read(p.dy_amax)) : 1.f, sx = NP == 2 ? uz::split_scale(uz::amax_read(p.x_amax)) : 1.f;
-    bool xbad = false, dbad = false;
-    auto xpieces = [&](float v0, float v1, unsigned (&out)[NP]) __attribute__((always_inline)) {
-        if constexpr (XPK) uz::packed_pair(__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1), out[0], out[1]);
-        else {
-            if constexpr (NP == 2) xbad |= uz::bound_violated(v0 * sx, v1 * sx);
-            pieces<NP>(v0 * sx, v1 * sx, out);
-        }
-    };
-    auto dpieces = [&](float v0, float v1, unsigned (&out)[NP]) __attribute__((always_inline)) {
-        if constexpr (DPK) uz::packed_pair(__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1), out[0], out[1]);
-        else {
-            if constexpr (NP == 2) dbad |= uz::bound_violated(v0 * sdy, v1 * sdy);
-            pieces<NP>(v0 * sdy, v1 * sdy, out);
-        }
-    };
-    auto lstore = [&](int t) __attribute__((always_inline)) {
-        const bool left_edge = t % p.tilesX == 0;
-#pragma unroll
-        for (int i = 0; i < DYSLOTS; ++i) {
-            const int e = tid + i * NT9, co = e / DQ, q = e % DQ;
-            char* d = dYl + co * DYROW9 + ((q / DQROW) * TW + (q % DQROW) * 4) * 2;
-            unsigned pa[NP], pb[NP];
-            dpieces(dreg[i][0], dreg[i][1], pa);
-            dpieces(dreg[i][2], dreg[i][3], pb);
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<uint2*>(d + pl * DYPLANE) = make_uint2(pa[pl], pb[pl]);
-        }
-#pragma unroll
-        for (int i = 0; i < XQSLOTS; ++i) {
-            const int e = tid + i * NT9;
-            if (e < CT * PROWS * XQ) {
-                const int q = e % XQ, r = e / XQ, ci = r / PROWS, prow = r - ci * PROWS;
-                char* d = Xl + ci * XCH + prow * XROW + q * 8;
-                unsigned pa[NP], pb[NP];
-                // (left image edge: a zero WORD is a zero value in both formats - split storage holds the two pieces of 0)
-                const f32x4 v = (left_edge && q == 0) ? f32x4{0.f, xq[i][0], xq[i][1], xq[i][2]} : xq[i];
-                xpieces(v[0], v[1], pa);
-                xpieces(v[2], v[3], pb);
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<uint2*>(d + pl * XPLANE) = make_uint2(pa[pl], pb[pl]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < XPSLOTS; ++i) {
-            const int e = tid + i * NT9;
-            if (e < CT * PROWS) {
-                const int ci = e / PROWS, prow = e - ci * PROWS;
-                unsigned pa[NP];
-                xpieces(xp[i][0], xp[i][1], pa);
-                char* d = Xl + ci * XCH + prow * XROW + XQ * 8;
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<unsigned*>(d + pl * XPLANE) = pa[pl];
-            }
-        }
-    };
-
-    const char* Ab = dYl + (wm * 32 + l31) * DYROW9 + h * 16;
-    const char* Bb = Xl + (wn * 32 + l31) * XCH + h * 16;
-
-    f32x16 acc[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-    // No prefetch across the MFMA loop: 144 accumulators + a tile of staging registers do not fit 256 registers (the prefetching build
-    // spilled 42 - 67 dwords per lane).  The load latency of a tile is covered by the OTHER workgroup of the CU, which is in its MFMA
-    // phase meanwhile; the loads are issued ahead of the barrier so that they also fly while the slower waves finish their MFMAs.
-    long long st0 = 0, rt0 = 0, s_wait = 0, s_store = 0, s_mma = 0;
-    if (p.stamps) { st0 = __builtin_amdgcn_s_memtime(); rt0 = __builtin_amdgcn_s_memrealtime(); }
-    for (int t = split; t < p.T; t += p.S) {
-        long long ta = 0, tb = 0, tc = 0;
-        if (p.stamps) ta = __builtin_amdgcn_s_memtime();
-        gload(t, -1);
-        __syncthreads();                   // every wave finished the MFMAs of the previous tile
-        if (p.stamps) { __builtin_amdgcn_s_waitcnt(0); tb = __builtin_amdgcn_s_memtime(); }
-        lstore(t);
-        __syncthreads();
-        if (p.stamps) { tc = __builtin_amdgcn_s_memtime(); s_wait += tb - ta; s_store += tc - tb; }
-#pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            const int srow = s / SROW, scol = (s % SROW) * 16;
-            u32x4 a[NP];
-#pragma unroll
-            for (int q = 0; q < NP; ++q) a[q] = *reinterpret_cast<const u32x4*>(Ab + q * DYPLANE + (srow * TW + scol) * 2);
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                u32x4 v[NP];
-                unsigned v4[NP];
-#pragma unroll
-                for (int q = 0; q < NP; ++q) {
-                    const char* src = Bb + q * XPLANE + (srow + d) * XROW + scol * 2;
-                    v[q] = *reinterpret_cast<const u32x4*>(src);
-                    v4[q] = *reinterpret_cast<const unsigned*>(src + 16);
-                }
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    u32x4 b[NP];
-#pragma unroll
-                    for (int q = 0; q < NP; ++q) {
-                        if (dx == 0) b[q] = v[q];
-                        else if (dx == 2) b[q] = u32x4{v[q].y, v[q].z, v[q].w, v4[q]};
-                        else b[q] = u32x4{__builtin_amdgcn_alignbit(v[q].y, v[q].x, 16), __builtin_amdgcn_alignbit(v[q].z, v[q].y, 16),
-                                          __builtin_amdgcn_alignbit(v[q].w, v[q].z, 16), __builtin_amdgcn_alignbit(v4[q], v[q].w, 16)};
-                    }
-                    acc[d * 3 + dx] = mma<NP>(acc[d * 3 + dx], a, b);
-                }
-            }
-        }
-        if (p.stamps) s_mma += __builtin_amdgcn_s_memtime() - tc;
-    }
-    long long st2 = 0;
-    if (p.stamps) st2 = __builtin_amdgcn_s_memtime();
-    if (NP == 2) { uz::raise_flag(p.flags, xbad, uz::FLAG_X_BOUND); uz::raise_flag(p.flags, dbad, uz::FLAG_DY_BOUND); }
-    float* out = p.slab + (size_t)split * 9 * p.Cout * p.Cin;
-    const int ci = ci0 + wn * 32 + l31;
-    const float inv_dy = NP == 2 ? uz::split_inv_scale(uz::amax_read(p.dy_amax)) : 1.f;
-    const float inv_x = NP == 2 ? uz::split_inv_scale(uz::amax_read((XPK && p.x_amax2 && ci >= p.seg_channels) ? p.x_amax2 : p.x_amax)) : 1.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (co < p.Cout && ci < p.Cin) out[((size_t)k * p.Cout + co) * p.Cin + ci] = acc[k][r] * inv_dy * inv_x;
-        }
-    if (p.stamps) {                        // rows of 8: {start, load-wait sum, staging sum, loop end, end, real-time start, real-time end, tiles}; MFMA sum in the row + 2048
-        __builtin_amdgcn_s_waitcnt(0);
-        const long long st3 = __builtin_amdgcn_s_memtime(), rt1 = __builtin_amdgcn_s_memrealtime();
-        if (tid == 0 && blockIdx.x < 2048) {
-            long long* o = p.stamps + 8 * blockIdx.x;
-            o[0] = st0; o[1] = s_wait; o[2] = s_store; o[3] = st2; o[4] = st3; o[5] = rt0; o[6] = rt1; o[7] = (p.T - split + p.S - 1) / p.S;
-            p.stamps[8 * (blockIdx.x + 2048)] = s_mma;
-        }
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Third form (round 6): the first form's eight waves and tap groups, but TWO LDS images of a 64-pixel tile (2 rows x 32 columns; 2 x 60 KB)
-// and the staging INSIDE the MFMA loop.  In-kernel stamps of the first form (224 -> 128 @ 128 x 128): 38 % of a tile's cycles are the phase
-// between its two barriers in which all eight waves convert and store the next tile while the matrix pipe idles; the MFMA loop itself runs at
-// 92 % of its MFMA cycles.  Here the tile j + 1 is converted and written to the other image in four portions, one per k-step of tile j, the
-// registers a portion frees are reloaded at once with the same portion of tile j + 3 (two register sets in flight: a load has two tiles'
-// time to arrive, as in the first form), and ONE barrier closes a tile.  Same slabs, same split count, same arithmetic.
-constexpr int PTD = 64;
-template <int XF, int DF>
-__global__ __launch_bounds__(NT) void wgrad_db_kernel(const WS p) {
-    constexpr bool XPK = XF == 1, DPK = DF == 1;
-    constexpr int NP = 2, TW = 32, TH = PTD / TW, XROW = (TW + 8) * 2, PROWS = TH + 2, XCHD = PROWS * XROW + 16, DYROWD = PTD * 2 + 16;
-    constexpr int CT = 64, SROW = TW / 16, KSTEPS = PTD / 16;
-    constexpr int DYPLANE = CT * DYROWD, XPLANE = CT * XCHD, IMG = NP * (DYPLANE + XPLANE);
-    constexpr int DQ = PTD / 4, DQROW = TW / 4, XQ = TW / 4;
-    constexpr int DYSLOTS = CT * DQ / NT;                     // 2
-    constexpr int XQSLOTS = CT * PROWS * XQ / NT;             // 4
-    static_assert(CT * DQ % NT == 0 && CT * PROWS * XQ % NT == 0 && CT * PROWS <= NT, "staging slots");
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tg = (wave ^ (wave >> 2)) & 1;
-    const int wn = (wave >> 1) & 1, wm = wave >> 2;
-    const int wid = uz::xcd_remap(blockIdx.x, gridDim.x);
-    const int nTile = p.nCoT * p.nCiT;
-    const int split = wid / nTile, tl = wid - split * nTile;
-    const int co0 = (tl / p.nCiT) * CT, ci0 = (tl % p.nCiT) * CT;
-
-    for (int i = tid * 16; i < 2 * IMG; i += NT * 16) *reinterpret_cast<u32x4*>(lds + i) = u32x4{0u, 0u, 0u, 0u};
-
-    const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.dy), 0, (unsigned)(((size_t)(p.N - 1) * p.CoutTot + p.Cout) * p.HW * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rxx = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x), 0, (unsigned)(((size_t)(p.N - 1) * p.CinTot + p.Cin) * p.HW * 4u), 0x00020000);
-
-    struct RS { f32x4 d[DYSLOTS]; f32x4 x[XQSLOTS]; float xp[2]; };
-    // slot numbering for the portions: dY slots 0 .. 1, X quads 2 .. 5, the pair slot 6; portion = slot % KSTEPS (part < 0: all)
-    auto gload = [&](RS& r, int t, int part) __attribute__((always_inline)) {
-        const unsigned tm = t < p.T ? 0u : 0xFFFFFFFFu;          // past the last tile: every load fails the range check (returns 0)
-        const int txi = t % p.tilesX, t2 = t / p.tilesX;
-        const int x0 = txi * TW, y0 = (t2 % p.tilesY) * TH, b0 = t2 / p.tilesY;
-        const unsigned dbase = 4u * (unsigned)((b0 * p.CoutTot + co0) * p.HW + y0 * p.W + x0);
-#pragma unroll
-        for (int i = 0; i < DYSLOTS; ++i) {
-            if (part >= 0 && i % KSTEPS != part) continue;
-            const int e = tid + i * NT, co = e / DQ, q = e % DQ, row = q / DQROW, c4 = (q % DQROW) * 4;
-            const unsigned m = ((y0 + row) < p.H && (co0 + co) < p.Cout) ? tm : 0xFFFFFFFFu;
-            r.d[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rdy, (dbase + 4u * (unsigned)(co * p.HW + row * p.W + c4)) | m, 0, 0));
-        }
-        const int xbase = (b0 * p.CinTot + ci0) * p.HW + y0 * p.W + x0;
-#pragma unroll
-        for (int i = 0; i < XQSLOTS; ++i) {
-            if (part >= 0 && (i + DYSLOTS) % KSTEPS != part) continue;
-            const int e = tid + i * NT;
-            const int q = e % XQ, rr = e / XQ, ci = rr / PROWS, prow = rr - ci * PROWS;
-            const int yy = y0 + prow - 1;
-            const bool rowok = (ci0 + ci) < p.Cin && yy >= 0 && yy < p.H;
-            const int sh = (q == 0 && x0 == 0) ? 1 : 0;
-            const int off = xbase + ci * p.HW + (prow - 1) * p.W + 4 * q - 1 + sh;
-            r.x[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rxx, (rowok ? 4u * (unsigned)off : 0xFFFFFFFFu) | tm, 0, 0));
-        }
-        if (part < 0 || (DYSLOTS + XQSLOTS) % KSTEPS == part) {
-            const int e = tid;
-            const int ci = e / PROWS, prow = e - ci * PROWS;
-            const int yy = y0 + prow - 1;
-            const bool rowok = e < CT * PROWS && (ci0 + ci) < p.Cin && yy >= 0 && yy < p.H;
-            const int off = xbase + ci * p.HW + (prow - 1) * p.W + TW - 1;
-            r.xp[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxx, (rowok ? 4u * (unsigned)off : 0xFFFFFFFFu) | tm, 0, 0));
-            r.xp[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxx, ((rowok && x0 + TW < p.W) ? 4u * (unsigned)(off + 1) : 0xFFFFFFFFu) | tm, 0, 0));
-        }
-    };
-    const float sdy = uz::split_scale(uz::amax_read(p.dy_amax)), sx = uz::split_scale(uz::amax_read(p.x_amax));
-    bool xbad = false, dbad = false;
-    auto xpieces = [&](float v0, float v1, unsigned (&out)[NP]) __attribute__((always_inline)) {
-        if constexpr (XPK) uz::packed_pair(__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1), out[0], out[1]);
-        else { xbad |= uz::bound_violated(v0 * sx, v1 * sx); pieces<NP>(v0 * sx, v1 * sx, out); }
-    };
-    auto dpieces = [&](float v0, float v1, unsigned (&out)[NP]) __attribute__((always_inline)) {
-        if constexpr (DPK) uz::packed_pair(__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1), out[0], out[1]);
-        else { dbad |= uz::bound_violated(v0 * sdy, v1 * sdy); pieces<NP>(v0 * sdy, v1 * sdy, out); }
-    };
-    auto lstore = [&](const RS& r, int t, char* img, int part) __attribute__((always_inline)) {
-        char* dYl = img;
-        char* Xl = img + NP * DYPLANE;
-        const bool left_edge = t % p.tilesX == 0;
-#pragma unroll
-        for (int i = 0; i < DYSLOTS; ++i) {
-            if (part >= 0 && i % KSTEPS != part) continue;
-            const int e = tid + i * NT, co = e / DQ, q = e % DQ;
-            char* d = dYl + co * DYROWD + ((q / DQROW) * TW + (q % DQROW) * 4) * 2;
-            unsigned pa[NP], pb[NP];
-            dpieces(r.d[i][0], r.d[i][1], pa);
-            dpieces(r.d[i][2], r.d[i][3], pb);
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<uint2*>(d + pl * DYPLANE) = make_uint2(pa[pl], pb[pl]);
-        }
-#pragma unroll
-        for (int i = 0; i < XQSLOTS; ++i) {
-            if (part >= 0 && (i + DYSLOTS) % KSTEPS != part) continue;
-            const int e = tid + i * NT;
-            const int q = e % XQ, rr = e / XQ, ci = rr / PROWS, prow = rr - ci * PROWS;
-            char* d = Xl + ci * XCHD + prow * XROW + q * 8;
-            unsigned pa[NP], pb[NP];
-            const f32x4 v = (left_edge && q == 0) ? f32x4{0.f, r.x[i][0], r.x[i][1], r.x[i][2]} : r.x[i];
-            xpieces(v[0], v[1], pa);
-            xpieces(v[2], v[3], pb);
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<uint2*>(d + pl * XPLANE) = make_uint2(pa[pl], pb[pl]);
-        }
-        if (part < 0 || (DYSLOTS + XQSLOTS) % KSTEPS == part) {
-            if (tid < CT * PROWS) {
-                const int ci = tid / PROWS, prow = tid - ci * PROWS;
-                unsigned pa[NP];
-                xpieces(r.xp[0], r.xp[1], pa);
-                char* d = Xl + ci * XCHD + prow * XROW + XQ * 8;
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<unsigned*>(d + pl * XPLANE) = pa[pl];
-            }
-        }
-    };
-
-    auto run = [&](auto ntap_c, auto tap0_c) __attribute__((always_inline)) {
-        constexpr int NTAP = decltype(ntap_c)::value, TAP0 = decltype(tap0_c)::value;
-        constexpr int DY0 = TAP0 / 3;
-        f32x16 acc[NTAP];
-#pragma unroll
-        for (int k = 0; k < NTAP; ++k)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-        const int aoff = (wm * 32 + l31) * DYROWD + h * 16;
-        const int boff = NP * DYPLANE + (wn * 32 + l31) * XCHD + h * 16;
-        // one tile: the MFMAs of tile j out of `rd`, tile j + 1 (registers r) converted into `wr`, r reloaded with tile j + 3
-        auto step = [&](const char* rd, char* wr, RS& r, int t_store, int t_load) __attribute__((always_inline)) {
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) {
-                lstore(r, t_store, wr, s);
-                gload(r, t_load, s);
-                const int srow = s / SROW, scol = (s % SROW) * 16;
-                u32x4 a[NP];
-#pragma unroll
-                for (int q = 0; q < NP; ++q) a[q] = *reinterpret_cast<const u32x4*>(rd + aoff + q * DYPLANE + (srow * TW + scol) * 2);
-#pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    u32x4 v[NP];
-                    unsigned v4[NP];
-#pragma unroll
-                    for (int q = 0; q < NP; ++q) {
-                        const char* src = rd + boff + q * XPLANE + (srow + DY0 + d) * XROW + scol * 2;
-                        v[q] = *reinterpret_cast<const u32x4*>(src);
-                        v4[q] = *reinterpret_cast<const unsigned*>(src + 16);
-                    }
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) {
-                        const int tap = (DY0 + d) * 3 + dx, k = tap - TAP0;
-                        if (k >= 0 && k < NTAP) {
-                            u32x4 b[NP];
-#pragma unroll
-                            for (int q = 0; q < NP; ++q) {
-                                if (dx == 0) b[q] = v[q];
-                                else if (dx == 2) b[q] = u32x4{v[q].y, v[q].z, v[q].w, v4[q]};
-                                else b[q] = u32x4{__builtin_amdgcn_alignbit(v[q].y, v[q].x, 16), __builtin_amdgcn_alignbit(v[q].z, v[q].y, 16),
-                                                  __builtin_amdgcn_alignbit(v[q].w, v[q].z, 16), __builtin_amdgcn_alignbit(v4[q], v[q].w, 16)};
-                            }
-                            const int kc = k < 0 ? 0 : (k >= NTAP ? NTAP - 1 : k);
-                            acc[kc] = mma<NP>(acc[kc], a, b);
-                        }
-                    }
-                }
-            }
-        };
-        const int J = (p.T - split + p.S - 1) / p.S;          // tiles of this workgroup: split, split + S, ...
-        RS r0, r1;
-        gload(r0, split, -1);
-        gload(r1, split + p.S, -1);
-        lstore(r0, split, lds, -1);
-        gload(r0, split + 2 * p.S, -1);
-        __syncthreads();
-        for (int j = 0; j < J; j += 2) {
-            step(lds, lds + IMG, r1, split + (j + 1) * p.S, split + (j + 3) * p.S);
-            __syncthreads();
-            if (j + 1 >= J) break;
-            step(lds + IMG, lds, r0, split + (j + 2) * p.S, split + (j + 4) * p.S);
-            __syncthreads();
-        }
-        uz::raise_flag(p.flags, xbad, uz::FLAG_X_BOUND); uz::raise_flag(p.flags, dbad, uz::FLAG_DY_BOUND);
-        float* out = p.slab + (size_t)split * 9 * p.Cout * p.Cin;
-        const int ci = ci0 + wn * 32 + l31;
-        const float inv_dy = uz::split_inv_scale(uz::amax_read(p.dy_amax));
-        const float inv_x = uz::split_inv_scale(uz::amax_read((XPK && p.x_amax2 && ci >= p.seg_channels) ? p.x_amax2 : p.x_amax));
-#pragma unroll
-        for (int k = 0; k < NTAP; ++k)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (co < p.Cout && ci < p.Cin) out[((size_t)(TAP0 + k) * p.Cout + co) * p.Cin + ci] = acc[k][r] * inv_dy * inv_x;
-            }
-    };
-    if (tg == 0) run(std::integral_constant<int, 5>{}, std::integral_constant<int, 0>{});
-    else run(std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{});
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------------------
-// Fourth form (round 6): HALF a workgroup of the first form.  256 threads = one wave per SIMD, a 64 x 32 (co x ci) tile of all nine taps
-// (waves = co half x tap group 5 + 4), the first form's 128-pixel tile, single LDS image (66.5 KB) and one-tile register prefetch.  Same
-// split count, twice the workgroups: two INDEPENDENT workgroups fit a CU (<= 256 VGPRs, 133 KB of LDS), so while one waits at its
-// barriers for a tile that was requested ~10 k cycles earlier on a 12 - 13 k-cycle round trip (what the first form's "staging phase"
-// consists of, NOTES_r6 section 8) the other one has the matrix pipe - and with one of them per CU the other half of EVERY CU stays free
-// for the other lanes' kernels (the first form keeps half the CUs whole).  Price: dY is fetched once per 32 input channels instead of
-// once per 64.  This is the form the last review asked for (256 threads, one wave per SIMD, 32 x 64 tile).
-// Measured (NOTES_r6 section 8): with PHiSeg's target of 128 its 256 workgroups spread over ALL CUs and an isolated launch is 25 - 31 % faster
-// (224 -> 128 @ 128 x 128: 1 218 -> 836 us); with two per CU (target 256) it equals the first form (the clock limit); the STEP is 0 - 1.5 % slower at every target
-// (64 ... 256) - what one lane's launch gains by taking the whole chip the other lanes' launches lose.  OFF.
-constexpr int NTH = 256;
-template <int XF, int DF>
-__global__ __launch_bounds__(NTH, 2) void wgrad_half_kernel(const WS p) {
-    constexpr bool XPK = XF == 1, DPK = DF == 1;
-    constexpr int NP = 2;
-    using GEO = WGeo<32>;
-    constexpr int TW = GEO::TW, XROW = GEO::XROW, QROWX = GEO::QROWX, PROWS = GEO::PROWS;
-    constexpr int SROW = TW / 16;
-    constexpr int COT = 64, CIT = 32;
-    constexpr int DYPLANE = COT * DYROW, XPLANE = CIT * XCH;
-    constexpr int DQ = PT / 4, DQROW = TW / 4, XQ = TW / 4;
-    constexpr int DYSLOTS = COT * DQ / NTH;                       // 8
-    constexpr int XQSLOTS = CIT * PROWS * XQ / NTH;               // 6
-    static_assert(COT * DQ % NTH == 0 && CIT * PROWS * XQ % NTH == 0 && CIT * PROWS <= NTH, "staging slots");
-    constexpr int NPARTS = PT / 16;                               // 8 k-steps per tile
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    char* dYl = lds;
-    char* Xl = lds + NP * DYPLANE;
-
-    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tg = (wave ^ (int)blockIdx.x) & 1;                  // two workgroups share a SIMD: neighbours take opposite tap groups
-    const int wm = wave >> 1;
-    const int wid = uz::xcd_remap(blockIdx.x, gridDim.x);
-    const int nTile = p.nCoT * p.nCiT;
-    const int split = wid / nTile, tl = wid - split * nTile;
-    const int co0 = (tl / p.nCiT) * COT, ci0 = (tl % p.nCiT) * CIT;
-
-    for (int i = tid * 16; i < NP * DYPLANE + NP * XPLANE; i += NTH * 16) *reinterpret_cast<u32x4*>(lds + i) = u32x4{0u, 0u, 0u, 0u};
-
-    const __amdgpu_buffer_rsrc_t rdy = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.dy), 0, (unsigned)(((size_t)(p.N - 1) * p.CoutTot + p.Cout) * p.HW * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rxx = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x), 0, (unsigned)(((size_t)(p.N - 1) * p.CinTot + p.Cin) * p.HW * 4u), 0x00020000);
-
-    f32x4 dreg[DYSLOTS];
-    f32x4 xq[XQSLOTS];
-    float xp[2];
-    auto gload = [&](int t, int part) __attribute__((always_inline)) {
-        const int txi = t % p.tilesX, t2 = t / p.tilesX;
-        const int x0 = txi * TW, y0 = (t2 % p.tilesY) * (PT / TW), b0 = t2 / p.tilesY;
-        const unsigned dbase = 4u * (unsigned)((b0 * p.CoutTot + co0) * p.HW + y0 * p.W + x0);
-#pragma unroll
-        for (int i = 0; i < DYSLOTS; ++i) {
-            if (part >= 0 && i % NPARTS != part) continue;
-            const int e = tid + i * NTH, co = e / DQ, q = e % DQ, row = q / DQROW, c4 = (q % DQROW) * 4;
-            const unsigned m = ((y0 + row) < p.H && (co0 + co) < p.Cout) ? 0u : 0xFFFFFFFFu;
-            dreg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rdy, (dbase + 4u * (unsigned)(co * p.HW + row * p.W + c4)) | m, 0, 0));
-        }
-        const int xbase = (b0 * p.CinTot + ci0) * p.HW + y0 * p.W + x0;
-#pragma unroll
-        for (int i = 0; i < XQSLOTS; ++i) {
-            if (part >= 0 && (i + DYSLOTS) % NPARTS != part) continue;
-            const int e = tid + i * NTH;
-            const int q = e % XQ, r = e / XQ, ci = r / PROWS, prow = r - ci * PROWS;
-            const int yy = y0 + prow - 1;
-            const bool rowok = (ci0 + ci) < p.Cin && yy >= 0 && yy < p.H;
-            const int sh = (q == 0 && x0 == 0) ? 1 : 0;
-            const int off = xbase + ci * p.HW + (prow - 1) * p.W + 4 * q - 1 + sh;
-            xq[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rxx, rowok ? 4u * (unsigned)off : 0xFFFFFFFFu, 0, 0));
-        }
-        if (part < 0 || (DYSLOTS + XQSLOTS) % NPARTS == part) {
-            const int ci = tid / PROWS, prow = tid - ci * PROWS;
-            const int yy = y0 + prow - 1;
-            const bool rowok = tid < CIT * PROWS && (ci0 + ci) < p.Cin && yy >= 0 && yy < p.H;
-            const int off = xbase + ci * p.HW + (prow - 1) * p.W + TW - 1;
-            xp[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxx, rowok ? 4u * (unsigned)off : 0xFFFFFFFFu, 0, 0));
-            xp[1] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxx, (rowok && x0 + TW < p.W) ? 4u * (unsigned)(off + 1) : 0xFFFFFFFFu, 0, 0));
-        }
-    };
-    const float sdy = uz::split_scale(uz::amax_read(p.dy_amax)), sx = uz::split_scale(uz::amax_read(p.x_amax));
-    bool xbad = false, dbad = false;
-    auto xpieces = [&](float v0, float v1, unsigned (&out)[NP]) __attribute__((always_inline)) {
-        if constexpr (XPK) uz::packed_pair(__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1), out[0], out[1]);
-        else { xbad |= uz::bound_violated(v0 * sx, v1 * sx); pieces<NP>(v0 * sx, v1 * sx, out); }
-    };
-    auto dpieces = [&](float v0, float v1, unsigned (&out)[NP]) __attribute__((always_inline)) {
-        if constexpr (DPK) uz::packed_pair(__builtin_bit_cast(unsigned, v0), __builtin_bit_cast(unsigned, v1), out[0], out[1]);
-        else { dbad |= uz::bound_violated(v0 * sdy, v1 * sdy); pieces<NP>(v0 * sdy, v1 * sdy, out); }
-    };
-    auto lstore = [&](int t) __attribute__((always_inline)) {
-        const bool left_edge = t % p.tilesX == 0;
-#pragma unroll
-        for (int i = 0; i < DYSLOTS; ++i) {
-            const int e = tid + i * NTH, co = e / DQ, q = e % DQ;
-            char* d = dYl + co * DYROW + ((q / DQROW) * TW + (q % DQROW) * 4) * 2;
-            unsigned pa[NP], pb[NP];
-            dpieces(dreg[i][0], dreg[i][1], pa);
-            dpieces(dreg[i][2], dreg[i][3], pb);
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<uint2*>(d + pl * DYPLANE) = make_uint2(pa[pl], pb[pl]);
-        }
-#pragma unroll
-        for (int i = 0; i < XQSLOTS; ++i) {
-            const int e = tid + i * NTH;
-            const int q = e % XQ, r = e / XQ, ci = r / PROWS, prow = r - ci * PROWS;
-            char* d = Xl + ci * XCH + prow * XROW + q * 8;
-            unsigned pa[NP], pb[NP];
-            const f32x4 v = (left_edge && q == 0) ? f32x4{0.f, xq[i][0], xq[i][1], xq[i][2]} : xq[i];
-            xpieces(v[0], v[1], pa);
-            xpieces(v[2], v[3], pb);
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<uint2*>(d + pl * XPLANE) = make_uint2(pa[pl], pb[pl]);
-        }
-        if (tid < CIT * PROWS) {
-            const int ci = tid / PROWS, prow = tid - ci * PROWS;
-            unsigned pa[NP];
-            xpieces(xp[0], xp[1], pa);
-            char* d = Xl + ci * XCH + prow * XROW + QROWX * 8;
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) *reinterpret_cast<unsigned*>(d + pl * XPLANE) = pa[pl];
-        }
-    };
-
-    const char* Ab = dYl + (wm * 32 + l31) * DYROW + h * 16;
-    const char* Bb = Xl + l31 * XCH + h * 16;
-
-    auto run = [&](auto ntap_c, auto tap0_c) __attribute__((always_inline)) {
-        constexpr int NTAP = decltype(ntap_c)::value, TAP0 = decltype(tap0_c)::value;
-        constexpr int DY0 = TAP0 / 3;
-        f32x16 acc[NTAP];
-#pragma unroll
-        for (int k = 0; k < NTAP; ++k)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
-        int t = split;
-        if (t < p.T) gload(t, -1);
-        for (; t < p.T; t += p.S) {
-            __syncthreads();
-            lstore(t);
-            __syncthreads();
-#pragma unroll
-            for (int si = 0; si < NPARTS; ++si) {
-                gload(t + p.S, si);                  // unconditional: behind the last tile the image index is >= N and every offset fails the range check
-                const int srow = si / SROW, scol = (si % SROW) * 16;
-                u32x4 a[NP];
-#pragma unroll
-                for (int q = 0; q < NP; ++q) a[q] = *reinterpret_cast<const u32x4*>(Ab + q * DYPLANE + (srow * TW + scol) * 2);
-#pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    u32x4 v[NP];
-                    unsigned v4[NP];
-#pragma unroll
-                    for (int q = 0; q < NP; ++q) {
-                        const char* src = Bb + q * XPLANE + (srow + DY0 + d) * XROW + scol * 2;
-                        v[q] = *reinterpret_cast<const u32x4*>(src);
-                        v4[q] = *reinterpret_cast<const unsigned*>(src + 16);
-                    }
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) {
-                        const int tap = (DY0 + d) * 3 + dx, k = tap - TAP0;
-                        if (k >= 0 && k < NTAP) {
-                            u32x4 b[NP];
-#pragma unroll
-                            for (int q = 0; q < NP; ++q) {
-                                if (dx == 0) b[q] = v[q];
-                                else if (dx == 2) b[q] = u32x4{v[q].y, v[q].z, v[q].w, v4[q]};
-                                else b[q] = u32x4{__builtin_amdgcn_alignbit(v[q].y, v[q].x, 16), __builtin_amdgcn_alignbit(v[q].z, v[q].y, 16),
-                                                  __builtin_amdgcn_alignbit(v[q].w, v[q].z, 16), __builtin_amdgcn_alignbit(v4[q], v[q].w, 16)};
-                            }
-                            const int kc = k < 0 ? 0 : (k >= NTAP ? NTAP - 1 : k);
-                            acc[kc] = mma<NP>(acc[kc], a, b);
-                        }
-                    }
-                }
-            }
-        }
-        uz::raise_flag(p.flags, xbad, uz::FLAG_X_BOUND); uz::raise_flag(p.flags, dbad, uz::FLAG_DY_BOUND);
-        float* out = p.slab + (size_t)split * 9 * p.Cout * p.Cin;
-        const int ci = ci0 + l31;
-        const float inv_dy = uz::split_inv_scale(uz::amax_read(p.dy_amax));
-        const float inv_x = uz::split_inv_scale(uz::amax_read((XPK && p.x_amax2 && ci >= p.seg_channels) ? p.x_amax2 : p.x_amax));
-#pragma unroll
-        for (int k = 0; k < NTAP; ++k)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (co < p.Cout && ci < p.Cin) out[((size_t)(TAP0 + k) * p.Cout + co) * p.Cin + ci] = acc[k][r] * inv_dy * inv_x;
-            }
     };
     if (tg == 0) run(std::integral_constant<int, 5>{}, std::integral_constant<int, 0>{});
     else run(std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{});
@@ -1110,35 +405,8 @@ extern "C" int uz_get_wgrad_target(void) {
     static const int env = getenv("UZ_WGS_TARGET") ? atoi(getenv("UZ_WGS_TARGET")) : 0;
     return env > 0 ? env : (g_wgs_target > 0 ? g_wgs_target : 256);
 }
-// The nine-taps-per-wave form (wgrad9_kernel) serves the 64-channel tiles of the two-piece mode.  UZ_WG9=0: first form everywhere.
-static bool wgrad9_on(int Cin, int Cout) {
-    static const int on = getenv("UZ_WG9") ? atoi(getenv("UZ_WG9")) : 0;
-    return on && conv_np() == 2 && chan_tile(Cin, Cout) == 64;
-}
-// its workgroups are half the first form's (four waves, two per CU): UZ_WG9_MULT workgroups per unit of the target; slabs may outweigh
-// the operands by 1 / UZ_WG9_K
-static int wgrad9_splits(int Cin, int Cout, int N, int H, int W) {
-    static const int mult = getenv("UZ_WG9_MULT") ? atoi(getenv("UZ_WG9_MULT")) : 2;
-    static const double kslab = getenv("UZ_WG9_K") ? atof(getenv("UZ_WG9_K")) : 1.0;
-    static const int smin_wg = getenv("UZ_WG9_MINWG") ? atoi(getenv("UZ_WG9_MINWG")) : 256;
-    const int nt = ceil_div(Cout, 64) * ceil_div(Cin, 64);
-    const int tw = tile_w(W);
-    const int T = N * ceil_div(H, PT9 / tw) * (W / tw);
-    int s = mult * uz_get_wgrad_target() / nt;
-    if (kslab > 0.0) {
-        const double operands = 4.0 * (double)N * H * W * ((double)Cin + Cout), slab = 2.0 * 4.0 * 9.0 * (double)Cin * Cout;
-        int cap = (int)(operands / (kslab * slab));
-        const int floor_s = ceil_div(smin_wg, nt);
-        if (cap < floor_s) cap = floor_s;
-        if (s > cap) s = cap;
-    }
-    if (s < 1) s = 1;
-    if (s > T) s = T;
-    return s;
-}
 // number of pixel splits: at most one split per pixel tile
 int wgrad_split_splits(int Cin, int Cout, int N, int H, int W) {
-    if (wgrad9_on(Cin, Cout)) return wgrad9_splits(Cin, Cout, N, H, W);
     const int ct = chan_tile(Cin, Cout);
     const int nt = ceil_div(Cout, ct) * ceil_div(Cin, ct);
     const int tw = tile_w(W);
@@ -1168,70 +436,19 @@ int wgrad_split_splits(int Cin, int Cout, int N, int H, int W) {
     return s;
 }
 
-// UZ_WG_DB=1: the two-image form (wgrad_db_kernel) for the 64-channel tiles of the 32-wide geometry in the two-piece mode
-static bool wgrad_db_on() { static const int on = getenv("UZ_WG_DB") ? atoi(getenv("UZ_WG_DB")) : 0; return on != 0; }
-template <int XF, int DF>
-static int launch_wgrad_db(WS p, int grid, hipStream_t st) {
-    constexpr size_t smem = 2 * 2 * (size_t)(64 * (PTD * 2 + 16) + 64 * (4 * 80 + 16));
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_db_kernel<XF, DF>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return fail("wgrad_split: cannot raise dynamic LDS limit");
-        attr_done = true;
-    }
-    p.tilesY = ceil_div(p.H, PTD / 32); p.T = p.N * p.tilesX * p.tilesY;         // 64-pixel tiles; the split count stays the first form's
-    hipLaunchKernelGGL((wgrad_db_kernel<XF, DF>), dim3(grid), dim3(NT), smem, st, p);
-    return check_launch("wgrad_db_kernel");
-}
-// UZ_WG_HALF=1: the half-workgroup form (wgrad_half_kernel) for the 64-channel tiles of the 32-wide geometry in the two-piece mode
-static bool wgrad_half_on() { static const int on = getenv("UZ_WG_HALF") ? atoi(getenv("UZ_WG_HALF")) : 0; return on != 0; }
-template <int XF, int DF>
-static int launch_wgrad_half(WS p, hipStream_t st) {
-    constexpr size_t smem = 2 * (size_t)(64 * DYROW) + 2 * (size_t)(32 * XCH);
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_half_kernel<XF, DF>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return fail("wgrad_split: cannot raise dynamic LDS limit");
-        attr_done = true;
-    }
-    p.nCiT = ceil_div(p.Cin, 32);                                     // 64 x 32 tiles; the split count stays the first form's
-    hipLaunchKernelGGL((wgrad_half_kernel<XF, DF>), dim3(p.nCoT * p.nCiT * p.S), dim3(NTH), smem, st, p);
-    return check_launch("wgrad_half_kernel");
-}
-template <int TWv, int CT, int NP, int XPK = 0, int DPK = 0, int M16 = 0>
+template <int TWv, int CT, int NP, int XPK = 0, int DPK = 0>
 static int launch_wgrad_np(const WS& p, int grid, hipStream_t st) {
-    if constexpr (!M16 && TWv == 32 && CT == 64 && NP == 2 && XPK == 1 && DPK == 1) {
-        if (wgrad_half_on()) return launch_wgrad_half<XPK, DPK>(p, st);
-    }
-    if constexpr (!M16 && TWv == 32 && CT == 64 && NP == 2 && XPK == 1 && DPK == 1) {       // (fp32 operands: their conversion spills 40 - 50 registers in this form)
-        if (wgrad_db_on()) return launch_wgrad_db<XPK, DPK>(p, grid, st);
-    }
-    if constexpr (!M16 && TWv == 32 && CT == 64 && NP == 2) {
-        static const int m16 = getenv("UZ_WG_M16") ? atoi(getenv("UZ_WG_M16")) : 0;
-        if (m16) return launch_wgrad_np<TWv, CT, NP, XPK, DPK, 1>(p, grid, st);
-    }
     // (the 32-channel kernel folds its pixel quarters through this LDS at the end: three taps x 16 x 64 floats per wave pair)
     constexpr size_t stage = NP * (size_t)(CT * DYROW) + NP * (size_t)(CT * XCH), fold = CT == 32 ? (size_t)4 * 3 * 16 * 64 * 4 : 0;
     constexpr size_t smem = stage > fold ? stage : fold;
     static bool attr_done = false;
     if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_split_kernel<TWv, CT, NP, XPK, DPK, M16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_split_kernel<TWv, CT, NP, XPK, DPK>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             return fail("wgrad_split: cannot raise dynamic LDS limit");
         attr_done = true;
     }
-    hipLaunchKernelGGL((wgrad_split_kernel<TWv, CT, NP, XPK, DPK, M16>), dim3(grid), dim3(NT), smem, st, p);
+    hipLaunchKernelGGL((wgrad_split_kernel<TWv, CT, NP, XPK, DPK>), dim3(grid), dim3(NT), smem, st, p);
     return check_launch("wgrad_split_kernel");
-}
-template <int TWv, int XF, int DF>
-static int launch_wgrad9(const WS& p, int grid, hipStream_t st) {
-    constexpr size_t smem = 2 * (size_t)(64 * DYROW9) + 2 * (size_t)(64 * WGeo9<TWv>::XCH);
-    hipLaunchKernelGGL((wgrad9_kernel<TWv, 2, XF, DF>), dim3(grid), dim3(NT9), smem, st, p);
-    return check_launch("wgrad9_kernel");
-}
-template <int TWv>
-static int launch_wgrad9_f(const WS& p, int grid, hipStream_t st, int xpk, int dpk) {
-    if (xpk) return dpk ? launch_wgrad9<TWv, 1, 1>(p, grid, st) : launch_wgrad9<TWv, 1, 0>(p, grid, st);
-    return dpk ? launch_wgrad9<TWv, 0, 1>(p, grid, st) : launch_wgrad9<TWv, 0, 0>(p, grid, st);
 }
 template <int TWv, int CT>
 static int launch_wgrad(const WS& p, int grid, hipStream_t st, int xpk, int dpk, int xb16, int db16) {
@@ -1257,15 +474,10 @@ int wgrad_split(const float* x, int Cin, int CinTot, const float* dy, int Cout, 
     p.x = x; p.dy = dy; p.slab = slab; p.x_amax = x_amax; p.dy_amax = dy_amax; p.stamps = debug_stamps; p.flags = dev_flags_ptr();
     p.N = N; p.H = H; p.W = W; p.HW = H * W; p.Cin = Cin; p.CinTot = CinTot; p.Cout = Cout; p.CoutTot = CoutTot;
     const int tw = tile_w(W), ct = chan_tile(Cin, Cout);
-    const bool nine = wgrad9_on(Cin, Cout);
-    p.tilesX = W / tw; p.tilesY = ceil_div(H, (nine ? PT9 : PT) / tw); p.T = N * p.tilesX * p.tilesY; p.S = S;
+    p.tilesX = W / tw; p.tilesY = ceil_div(H, PT / tw); p.T = N * p.tilesX * p.tilesY; p.S = S;
     p.nCoT = ceil_div(Cout, ct); p.nCiT = ceil_div(Cin, ct);
     UZ_REQUIRE((size_t)N * CinTot * p.HW < (1ull << 30) && (size_t)N * CoutTot * p.HW < (1ull << 30), "wgrad_split: tensor too large for 32-bit offsets (the dispatcher routes such tensors to the fp32 kernel)");
     const int grid = p.nCoT * p.nCiT * S;
-    if (nine) {
-        UZ_REQUIRE(!x_b16 && !dy_b16, "wgrad_split: bf16 storage needs the single-piece bf16 mode");
-        return tw == 16 ? launch_wgrad9_f<16>(p, grid, st, x_packed, dy_packed) : launch_wgrad9_f<32>(p, grid, st, x_packed, dy_packed);
-    }
     if (ct == 32) return tw == 16 ? launch_wgrad<16, 32>(p, grid, st, x_packed, dy_packed, x_b16, dy_b16) : launch_wgrad<32, 32>(p, grid, st, x_packed, dy_packed, x_b16, dy_b16);
     return tw == 16 ? launch_wgrad<16, 64>(p, grid, st, x_packed, dy_packed, x_b16, dy_b16) : launch_wgrad<32, 64>(p, grid, st, x_packed, dy_packed, x_b16, dy_b16);
 }
