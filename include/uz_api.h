@@ -302,6 +302,15 @@ int uz_spatial_mean_fwd(const float* x, int C, int CtotX, float* y, int N, int H
 int uz_spatial_mean_bwd(const float* dy, int C, float* dx, int CtotDx, int N, int H, int W,
                         int accumulate, void* stream);
 
+/* The kernel a streaming call takes, answered on the host from the very predicates the entry points dispatch through (the
+ * library loads without a GPU).  op: 0 uz_avgpool2_fwd, 1 uz_avgpool2_bwd(_relu), 2 uz_bilinear2x_fwd, 3 uz_bilinear2x_bwd(_relu),
+ * 4 uz_nearest_bwd, 5 uz_add_views.  C, N, H, W as the entry point takes them; arg = the factor of op 4 (unused elsewhere);
+ * align_* = byte alignment (16, 8 or 4) of the views the dispatch inspects: src = x / dy / a, dst = y / dx, aux = the activation
+ * of op 1's _relu form / b of op 5 (16 when absent).  Returns 0 generic / scalar kernel, 1 vector or band kernel (float4 / float2
+ * pooling, forward band, backward pair band, float4 add), 2 float4 backward band, 3 one wave per element.  Honours
+ * UZ_BILINEAR_BWD_PAIR as the dispatch does.  The band kernels' workgroups per plane: uz_resample_bwd_relu_rows(1, ...) / N. */
+int uz_stream_route(int op, int C, int N, int H, int W, int arg, int align_src, int align_dst, int align_aux);
+
 /* ---------------------------------------------------------------- latent heads / losses
  * mask (N,1,H,W) float {0,1,..} -> cat([patch, onehot(mask)-0.5], 1): utils.py:289-311,
  * phiseg.py:178-183, probabilistic_unet.py:103-109.  out has in_ch + nlabels channels. */
@@ -345,6 +354,8 @@ int uz_kl_fwd(const float* mu0, const float* s0, const float* mu1, const float* 
  * sample of 2 M elements) are summed by up to 64 workgroups + an ordered final pass instead of one workgroup. */
 int uz_kl_fwd_ws(const float* mu0, const float* s0, const float* mu1, const float* s1, int N, int per_sample, float weight,
                  float* loss_out, void* workspace, void* stream);
+/* partial workgroups uz_kl_fwd_ws sums (N, per_sample) with, given a workspace: 1 = the single-workgroup kernel of uz_kl_fwd */
+int uz_kl_fwd_parts(int N, int per_sample);
 int uz_kl_bwd(const float* mu0, const float* s0, const float* mu1, const float* s1,
               int N, int per_sample, float weight, const float* loss_scale,
               float* dmu0, float* ds0, float* dmu1, float* ds1, void* stream);

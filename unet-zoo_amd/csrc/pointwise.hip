@@ -376,16 +376,28 @@ extern "C" int uz_kl_fwd(const float* mu0, const float* s0, const float* mu1, co
     hipLaunchKernelGGL(kl_fwd_k, dim3(1), dim3(1024), 0, uz::S(stream), mu0, s0, mu1, s1, N * per_sample, N, weight, loss_out);
     return uz::check_launch("kl_fwd_k");
 }
+// partial workgroups of the two-stage sum over `total` elements and their chunk; 1 = the single-workgroup kernel
+static int kl_parts(long long total, int& ck) {
+    const int chunk = 65536;
+    ck = chunk;
+    if (total <= 131072) return 1;
+    const int G = (int)((total + chunk - 1) / chunk);
+    if (G > 64) ck = (int)(((total + 63) / 64 + 1023) / 1024 * 1024);      // at most 64 partials (512 bytes of workspace)
+    return (int)((total + ck - 1) / ck);
+}
+extern "C" int uz_kl_fwd_parts(int N, int per_sample) {
+    UZ_REQUIRE(N > 0 && per_sample > 0, "kl_fwd: empty tensor");
+    int ck;
+    return kl_parts((long long)N * per_sample, ck);
+}
 extern "C" int uz_kl_fwd_ws(const float* mu0, const float* s0, const float* mu1, const float* s1, int N, int per_sample, float weight,
                             float* loss_out, void* workspace, void* stream) {
     UZ_REQUIRE(N > 0 && per_sample > 0, "kl_fwd: empty tensor");
     const long long total = (long long)N * per_sample;
     UZ_REQUIRE(total < (1ll << 31), "kl_fwd: tensor too large");
-    if (!workspace || total <= 131072) return uz_kl_fwd(mu0, s0, mu1, s1, N, per_sample, weight, loss_out, stream);
-    const int chunk = 65536;
-    int G = (int)((total + chunk - 1) / chunk);
-    const int ck = G > 64 ? (int)(((total + 63) / 64 + 1023) / 1024 * 1024) : chunk;      // at most 64 partials (512 bytes of workspace)
-    G = (int)((total + ck - 1) / ck);
+    int ck;
+    const int G = kl_parts(total, ck);
+    if (!workspace || G == 1) return uz_kl_fwd(mu0, s0, mu1, s1, N, per_sample, weight, loss_out, stream);
     double* part = static_cast<double*>(workspace);
     hipLaunchKernelGGL(kl_fwd_part_k, dim3(G), dim3(1024), 0, uz::S(stream), mu0, s0, mu1, s1, (int)total, ck, part);
     if (int rc = uz::check_launch("kl_fwd_part_k")) return rc;
@@ -460,14 +472,17 @@ extern "C" int uz_adam_step(float* params, const float* grads, float* exp_avg, f
                        (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), beta1, beta2, eps, weight_decay, grad_scale);
     return uz::check_launch("adam_k");
 }
+// kernel of uz_add_views: 0 scalar, 1 float4 (planes of whole float4, three 16-byte views; an absent b aligns as 16)
+static int add_views_route(int HW, int al_a, int al_b, int al_y) { return HW % 4 == 0 && al_a >= 16 && al_b >= 16 && al_y >= 16 ? 1 : 0; }
+// uz_stream_route's answer for uz_add_views (resample.hip holds the query; the predicate stays in this file)
+int uz::add_views_stream_route(int H, int W, int al_a, int al_y, int al_b) { return add_views_route(H * W, al_a, al_b, al_y); }
 extern "C" int uz_add_views(const float* a, int CtotA, const float* b, int CtotB, float* y, int CtotY, int C, int N, int H, int W,
                             float alpha, int accumulate, const float* a_amax, const float* b_amax, float* y_amax, void* stream) {
     UZ_REQUIRE(a && y && C > 0 && N > 0 && H > 0 && W > 0, "add_views: bad arguments");
     UZ_REQUIRE(N <= 65535, "add_views: N exceeds grid limits");
     const int HW = H * W;
     const size_t per = (size_t)C * HW;
-    auto al = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool v4 = HW % 4 == 0 && al(a) && al(b) && al(y);
+    const bool v4 = add_views_route(HW, uz::align_of(a), uz::align_of(b), uz::align_of(y)) == 1;
     int gx = (int)((per / (v4 ? 4 : 1) + 255) / 256);
     gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
     if (v4) hipLaunchKernelGGL(add_views_k<4>, dim3(gx, N), dim3(256), 0, uz::S(stream), a, CtotA, b, CtotB, y, CtotY, C, HW, alpha, accumulate, a_amax, b_amax, y_amax);

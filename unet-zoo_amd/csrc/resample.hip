@@ -487,6 +487,37 @@ int check_dims(const char* op, int C, int N, int H, int W) {
     return 0;
 }
 
+// ---- kernel choice.  Every entry point below and the host-side query uz_stream_route decide through these predicates and nothing
+// else (tests/_stream_routes.py pins each clause from both sides).  Alignments are uz::align_of values: 16, 8 or 4 bytes.
+enum { RT_GENERIC = 0, RT_VEC = 1, RT_QUAD = 2, RT_WAVE = 3 };
+// H x W: the high-resolution plane.  Even rows, float4 columns, a 16-byte wide side and an 8-byte narrow side.
+int avgpool_fwd_route(int H, int W, int al_x, int al_y) {
+    return H % 2 == 0 && W % 4 == 0 && al_x >= 16 && al_y >= 8 ? RT_VEC : RT_GENERIC;
+}
+int avgpool_bwd_route(int H, int W, int al_dy, int al_dx, int al_a) {
+    return H % 2 == 0 && W % 4 == 0 && al_dx >= 16 && al_dy >= 8 && al_a >= 16 ? RT_VEC : RT_GENERIC;
+}
+// H x W: the low-resolution plane.  W % 4 == 0 keeps every (image, channel) plane of both sides float4-aligned.
+int bilinear_fwd_route(int H, int W, int al_x, int al_y) {
+    return W % 4 == 0 && W <= FWMAX && H >= 4 && al_x >= 16 && al_y >= 16 ? RT_VEC : RT_GENERIC;
+}
+bool bilinear_bwd_band_shape(int H, int W) { return 2 * W <= BWMAX && H >= 4 && 256 % W == 0; }
+// 16 x 16 planes: one or two band rows per thread, the pair kernel is 3 us quicker
+bool bilinear_bwd_quad_shape(int W) { return W >= 32 && 64 % (W / 2) == 0; }
+bool bilinear_bwd_quad_enabled() { static const bool quad = !getenv("UZ_BILINEAR_BWD_PAIR"); return quad; }
+// Wo is even: an 8-byte aligned view keeps every float2 of every row aligned
+int bilinear_bwd_route(int H, int W, int al_dy, int al_dx) {
+    if (!(bilinear_bwd_band_shape(H, W) && al_dy >= 8)) return RT_GENERIC;
+    return bilinear_bwd_quad_enabled() && bilinear_bwd_quad_shape(W) && al_dy >= 16 && al_dx >= 8 ? RT_QUAD : RT_VEC;
+}
+// workgroups per plane of the band kernels.  Enough planes to fill the chip: one workgroup per plane walks its bands
+// (2.8 -> 3.3 TB/s on 192 ch 64^2 -> 128^2, 3.1 -> 3.75 on 32^2)
+int bilinear_bwd_band_gx(int C, int N, int H) { return (long long)C * N >= 2048 ? 1 : uz::ceil_div(H, LB); }
+// H x W: the low-resolution plane
+int nearest_bwd_route(int H, int W, int factor) {
+    return factor * factor >= 64 && (H * W + 3) / 4 <= 65535 ? RT_WAVE : RT_GENERIC;
+}
+
 }  // namespace
 
 #define RS_LAUNCH(kern, nplane)                                                                      \
@@ -503,7 +534,7 @@ extern "C" int uz_avgpool2_fwd_ex(const float* x, int C, int CtotX, float* y, in
     UZ_REQUIRE(!out_packed || (x_amax && y_amax), "avgpool2_fwd_ex: split storage needs the input's bound and the output's slot");
     RsP p = {}; p.src = x; p.dst = y; p.C = C; p.CtotS = CtotX; p.CtotD = CtotY; p.N = N; p.x_amax = x_amax; p.y_amax = y_amax; p.pack = out_packed; p.flags = uz::dev_flags_ptr();
     p.Ho = H; p.Wo = W; p.H = (H + 1) / 2; p.W = (W + 1) / 2;
-    if (H % 2 == 0 && W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0) {
+    if (avgpool_fwd_route(H, W, uz::align_of(x), uz::align_of(y)) == RT_VEC) {
         // (the grid's x extent stays ceil(H W / 4 / PCH) workgroups per plane: PCH / 2 float2 outputs each)
         hipLaunchKernelGGL(avgpool_fwd_v4, dim3(uz::ceil_div(p.H * p.W, PCH), C, N), dim3(256), 0, uz::S(stream), p);
         return uz::check_launch("avgpool_fwd_v4");
@@ -516,7 +547,7 @@ static int avgpool2_bwd_impl(const float* dy, int C, int CtotDy, float* dx, int 
     RsP p = {}; p.src = dy; p.dst = dx; p.C = C; p.CtotS = CtotDy; p.CtotD = CtotDx; p.N = N;
     p.Ho = H; p.Wo = W; p.H = (H + 1) / 2; p.W = (W + 1) / 2; p.accumulate = accumulate;
     p.mask = a; p.CtotM = CtotA; p.part = part; p.m_amax = dx_amax;
-    if (H % 2 == 0 && W % 4 == 0 && (reinterpret_cast<uintptr_t>(dx) & 15) == 0 && (reinterpret_cast<uintptr_t>(dy) & 7) == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0) {
+    if (avgpool_bwd_route(H, W, uz::align_of(dy), uz::align_of(dx), uz::align_of(a)) == RT_VEC) {
         // same grid as the scalar kernel (uz_resample_bwd_relu_rows counts its x extent): PCH / 4 float4 of dx per workgroup
         hipLaunchKernelGGL(avgpool_bwd_v4, dim3(uz::ceil_div(H * W, PCH), C, N), dim3(256), 0, uz::S(stream), p);
         return uz::check_launch("avgpool_bwd_v4");
@@ -530,7 +561,7 @@ extern "C" int uz_avgpool2_bwd(const float* dy, int C, int CtotDy, float* dx, in
 // HIGH-resolution plane; kind 1: bilinear2x, H x W = the LOW-resolution plane)
 static int resample_bwd_gx(int kind, int C, int N, int H, int W) {
     if (kind == 0) return uz::ceil_div(H * W, PCH);
-    if (2 * W <= BWMAX && H >= 4 && 256 % W == 0) return (long long)C * N >= 2048 ? 1 : uz::ceil_div(H, LB);
+    if (bilinear_bwd_band_shape(H, W)) return bilinear_bwd_band_gx(C, N, H);
     return uz::ceil_div(H * W, PCH);
 }
 extern "C" int uz_resample_bwd_relu_rows(int kind, int C, int N, int H, int W) { return N * resample_bwd_gx(kind, C, N, H, W); }
@@ -553,8 +584,7 @@ extern "C" int uz_bilinear2x_fwd_ex(const float* x, int C, int CtotX, float* y, 
     UZ_REQUIRE(!out_packed || (x_amax && y_amax), "bilinear2x_fwd_ex: split storage needs the input's bound and the output's slot");
     RsP p = {}; p.src = x; p.dst = y; p.C = C; p.CtotS = CtotX; p.CtotD = CtotY; p.N = N; p.x_amax = x_amax; p.y_amax = y_amax; p.pack = out_packed; p.flags = uz::dev_flags_ptr();
     p.H = H; p.W = W; p.Ho = 2 * H; p.Wo = 2 * W; p.ac = align_corners; bil_scales(p);
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (W % 4 == 0 && W <= FWMAX && H >= 4 && al16(x) && al16(y)) {     // W % 4 == 0 keeps every (image, channel) plane of both sides float4-aligned
+    if (bilinear_fwd_route(H, W, uz::align_of(x), uz::align_of(y)) == RT_VEC) {
         hipLaunchKernelGGL(bilinear_fwd_band_k, dim3(uz::ceil_div(p.Ho, OB), C, N), dim3(256), 0, uz::S(stream), p);
         return uz::check_launch("bilinear_fwd_band_k");
     }
@@ -568,7 +598,7 @@ extern "C" int uz_bilinear2x_bwd(const float* dy, int C, int CtotDy, float* dx, 
 extern "C" int uz_bilinear2x_bwd_relu(const float* dy, int C, int CtotDy, float* dx, int CtotDx, int N, int H, int W, int align_corners, int accumulate,
                                       const float* a, int CtotA, double* partials, float* dx_amax, void* stream) {
     UZ_REQUIRE(a && partials, "bilinear2x_bwd_relu: needs the activation and the partial-sum rows");
-    UZ_REQUIRE((reinterpret_cast<uintptr_t>(dy) & 7) == 0, "bilinear2x_bwd_relu: dy must be 8-byte aligned");      // (keeps the kernel choice = uz_resample_bwd_relu_rows)
+    UZ_REQUIRE(uz::align_of(dy) >= 8, "bilinear2x_bwd_relu: dy must be 8-byte aligned");      // (keeps the kernel choice = uz_resample_bwd_relu_rows)
     return bilinear2x_bwd_impl(dy, C, CtotDy, dx, CtotDx, N, H, W, align_corners, accumulate, a, CtotA, partials, dx_amax, stream);
 }
 static int bilinear2x_bwd_impl(const float* dy, int C, int CtotDy, float* dx, int CtotDx, int N, int H, int W, int align_corners, int accumulate,
@@ -577,13 +607,10 @@ static int bilinear2x_bwd_impl(const float* dy, int C, int CtotDy, float* dx, in
     RsP p = {}; p.src = dy; p.dst = dx; p.C = C; p.CtotS = CtotDy; p.CtotD = CtotDx; p.N = N;
     p.H = H; p.W = W; p.Ho = 2 * H; p.Wo = 2 * W; p.ac = align_corners; p.accumulate = accumulate; bil_scales(p);
     p.mask = a; p.CtotM = CtotA; p.part = part; p.m_amax = dx_amax;
-    if (p.Wo <= BWMAX && p.H >= 4 && 256 % p.W == 0 && (reinterpret_cast<uintptr_t>(dy) & 7) == 0) {
-        // Wo is even: an 8-byte aligned view keeps every float2 of every row aligned
-        // enough planes to fill the chip: one workgroup per plane walks its bands (2.8 -> 3.3 TB/s on 192 ch 64^2 -> 128^2, 3.1 -> 3.75 on 32^2)
-        const dim3 grid((long long)C * N >= 2048 ? 1 : uz::ceil_div(H, LB), C, N);
-        static const bool quad = !getenv("UZ_BILINEAR_BWD_PAIR");
-        if (quad && W >= 32 && 64 % (W / 2) == 0 &&       // 16 x 16 planes: one or two band rows per thread, the pair kernel is 3 us quicker
-            (reinterpret_cast<uintptr_t>(dy) & 15) == 0 && (reinterpret_cast<uintptr_t>(dx) & 7) == 0) {
+    const int route = bilinear_bwd_route(H, W, uz::align_of(dy), uz::align_of(dx));
+    if (route != RT_GENERIC) {
+        const dim3 grid(bilinear_bwd_band_gx(C, N, H), C, N);
+        if (route == RT_QUAD) {
             hipLaunchKernelGGL(bilinear_bwd_sep4_k, grid, dim3(256), 0, uz::S(stream), p);
             return uz::check_launch("bilinear_bwd_sep4_k");
         }
@@ -597,8 +624,7 @@ static int bilinear2x_bwd_impl(const float* dy, int C, int CtotDy, float* dx, in
 // side stays fp32.  Band kernels only: W % 4 == 0, W <= 128 / 2 W <= 128, H >= 4, 256 % W == 0 (backward), 16-byte aligned views.
 extern "C" int uz_bilinear2x_fwd_b16(const float* x, int C, int CtotX, void* y, int CtotY, int N, int H, int W, int align_corners, int y_b16, void* stream) {
     if (int rc = check_dims("bilinear2x_fwd_b16", C, N, H, W)) return rc;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    UZ_REQUIRE(W % 4 == 0 && W <= FWMAX && H >= 4 && al16(x) && al16(y), "bilinear2x_fwd_b16: shape not served by the band kernel (W %% 4 == 0, W <= 128, H >= 4, 16-byte aligned views)");
+    UZ_REQUIRE(bilinear_fwd_route(H, W, uz::align_of(x), uz::align_of(y)) == RT_VEC, "bilinear2x_fwd_b16: shape not served by the band kernel (W %% 4 == 0, W <= 128, H >= 4, 16-byte aligned views)");
     RsP p = {}; p.src = x; p.dst = static_cast<float*>(y); p.C = C; p.CtotS = CtotX; p.CtotD = CtotY; p.N = N; p.hb16 = y_b16 != 0;
     p.H = H; p.W = W; p.Ho = 2 * H; p.Wo = 2 * W; p.ac = align_corners; bil_scales(p);
     hipLaunchKernelGGL(bilinear_fwd_band_k, dim3(uz::ceil_div(p.Ho, OB), C, N), dim3(256), 0, uz::S(stream), p);
@@ -606,12 +632,12 @@ extern "C" int uz_bilinear2x_fwd_b16(const float* x, int C, int CtotX, void* y, 
 }
 extern "C" int uz_bilinear2x_bwd_b16(const void* dy, int C, int CtotDy, float* dx, int CtotDx, int N, int H, int W, int align_corners, int accumulate, int dy_b16, void* stream) {
     if (int rc = check_dims("bilinear2x_bwd_b16", C, N, H, W)) return rc;
-    UZ_REQUIRE(2 * W <= BWMAX && H >= 4 && 256 % W == 0 && (reinterpret_cast<uintptr_t>(dy) & 7) == 0, "bilinear2x_bwd_b16: shape not served by the band kernel (2 W <= 128, H >= 4, 256 %% W == 0, 8-byte aligned dy)");
+    UZ_REQUIRE(bilinear_bwd_band_shape(H, W) && uz::align_of(dy) >= 8, "bilinear2x_bwd_b16: shape not served by the band kernel (2 W <= 128, H >= 4, 256 %% W == 0, 8-byte aligned dy)");
     RsP p = {}; p.src = static_cast<const float*>(dy); p.dst = dx; p.C = C; p.CtotS = CtotDy; p.CtotD = CtotDx; p.N = N; p.hb16 = dy_b16 != 0;
     p.H = H; p.W = W; p.Ho = 2 * H; p.Wo = 2 * W; p.ac = align_corners; p.accumulate = accumulate; bil_scales(p);
-    const dim3 grid((long long)C * N >= 2048 ? 1 : uz::ceil_div(H, LB), C, N);
-    if (W >= 32 && 64 % (W / 2) == 0 && (reinterpret_cast<uintptr_t>(dx) & 7) == 0) {        // (8-byte aligned dy: four bf16 columns or, in fp32, checked below)
-        if (dy_b16 || (reinterpret_cast<uintptr_t>(dy) & 15) == 0) {
+    const dim3 grid(bilinear_bwd_band_gx(C, N, H), C, N);
+    if (bilinear_bwd_quad_shape(W) && uz::align_of(dx) >= 8) {        // (8-byte aligned dy: four bf16 columns or, in fp32, checked below)
+        if (dy_b16 || uz::align_of(dy) >= 16) {
             hipLaunchKernelGGL(bilinear_bwd_sep4_k, grid, dim3(256), 0, uz::S(stream), p);
             return uz::check_launch("bilinear_bwd_sep4_k");
         }
@@ -655,7 +681,7 @@ extern "C" int uz_nearest_bwd(const float* dy, int C, int CtotDy, float* dx, int
     UZ_REQUIRE(factor >= 1, "nearest_bwd: factor must be >= 1");
     RsP p = {}; p.src = dy; p.dst = dx; p.C = C; p.CtotS = CtotDy; p.CtotD = CtotDx; p.N = N;
     p.H = H; p.W = W; p.Ho = H * factor; p.Wo = W * factor; p.factor = factor; p.accumulate = accumulate;
-    if (factor * factor >= 64 && (H * W + 3) / 4 <= 65535) {
+    if (nearest_bwd_route(H, W, factor) == RT_WAVE) {
         hipLaunchKernelGGL(nearest_bwd_wave_k, dim3((H * W + 3) / 4, C, N), dim3(256), 0, uz::S(stream), p);
         return uz::check_launch("nearest_bwd_wave_k");
     }
@@ -680,4 +706,18 @@ extern "C" int uz_bcast_channels_bwd(const float* dy, int CtotDy, int L, float* 
     if (int rc = check_dims("bcast_channels_bwd", L, N, H, W)) return rc;
     hipLaunchKernelGGL(bcast_bwd_k, dim3(L, N), dim3(256), 0, uz::S(stream), dy, CtotDy, L, dz, H * W);
     return uz::check_launch("bcast_bwd_k");
+}
+
+// The kernel a call takes, answered on the host from the predicates the entry points themselves use (include/uz_api.h).
+extern "C" int uz_stream_route(int op, int C, int N, int H, int W, int arg, int align_src, int align_dst, int align_aux) {
+    (void)C; (void)N;
+    switch (op) {
+        case 0: return avgpool_fwd_route(H, W, align_src, align_dst);
+        case 1: return avgpool_bwd_route(H, W, align_src, align_dst, align_aux);
+        case 2: return bilinear_fwd_route(H, W, align_src, align_dst);
+        case 3: return bilinear_bwd_route(H, W, align_src, align_dst);
+        case 4: return nearest_bwd_route(H, W, arg);
+        case 5: return uz::add_views_stream_route(H, W, align_src, align_dst, align_aux);
+        default: return uz::fail("stream_route: unknown op %d", op);
+    }
 }

@@ -18,6 +18,8 @@ static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int pow2_ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 static inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+// byte alignment of a float view as the streaming dispatch sees it: 16, 8 or 4 (NULL, an absent operand, constrains nothing: 16)
+static inline int align_of(const void* p) { const uintptr_t a = reinterpret_cast<uintptr_t>(p); return (a & 15) == 0 ? 16 : (a & 7) == 0 ? 8 : 4; }
 
 // The dispatcher deals consecutive workgroup ids round-robin over the 8 XCDs (each with a
 // private L2).  Remap so that every XCD walks a contiguous chunk of the work list: blocks that
@@ -105,6 +107,9 @@ int conv1x1_small_bwd_data(const float* dy, int Cout, int CoutTot, const float* 
 size_t conv1x1_small_bwd_weight_ws(int Cin, int Cout, int N, int H, int W);
 int conv1x1_small_bwd_weight(const float* x, int Cin, int CinTot, const float* dy, int Cout, int CoutTot, float* dw, float* db,
                              int N, int H, int W, void* ws, hipStream_t st, int x_b16 = 0);
+
+// pointwise.hip: what uz_stream_route answers for uz_add_views (op 5), from the file-local predicate uz_add_views dispatches with
+int add_views_stream_route(int H, int W, int al_a, int al_y, int al_b);
 
 }  // namespace uz
 
