@@ -243,6 +243,18 @@ int uz_bn_relu_fwd_phase(const float* y, int C, int CtotY, const float* gamma, c
 int uz_bn_fwd_fused_limit(int H, int W);         /* N*H*W up to which the training-mode uz_bn_relu_fwd(_ex) WITHOUT conv_partials is one launch (statistics + apply from registers) */
 int uz_bn_bwd_fused_limit(int H, int W);         /* N*H*W up to which uz_bn_relu_bwd(_ex) is one launch with the channel's batch on chip: no out_packed / dbias_partials there */
 int uz_bn_bwd_dbias_rows(int N, int H, int W);   /* rows of dbias_partials ([rows][C] doubles, summed by uz_chan_sum_table); 0: small-plane path */
+/* What a BatchNorm call launches, answered on the host by the very function the entry points dispatch on (the library loads without a
+ * GPU).  direction: 0 = uz_bn_relu_fwd / _pre / _ex / _phase / _slabs / _b16, 1 = uz_bn_relu_bwd / _ex / _b16; N, C, H, W, training as the
+ * call takes them; vec != 0: every view the call inspects (y and a; da, y and dy) is 16-byte aligned; flags: 1 conv_partials given,
+ * 2 out_packed, 4 dbias_partials given, 8 slabs / da_slabs given, 16 a *_b16 (bf16 storage) entry point.  out6 receives
+ *   [0] path: 0 small (one 256-thread workgroup per channel), 1 mid (one 512- / 1024-thread workgroup per channel), 2 large
+ *       (statistics or reduction pass + apply pass), 3 large with bf16 storage;
+ *   [1] instance: small - elements per thread 2 / 8 / 16; mid - threads per workgroup 512 / 1024; large - 0;
+ *   [2] parts: chunks of 16 384 elements per plane;   [3] nb, [4] ngrp: images per reduction workgroup and the number of image
+ *       groups of the large paths (0 elsewhere);   [5] 1 where the float4 instance runs.
+ * Honours UZ_BN_MID, UZ_BN_MID_FWD and UZ_BN_MID_HALF as the dispatch does (each read once per process).  Returns 0, or -1 for
+ * arguments no entry point accepts (empty tensor, unknown flag bits, bf16 storage outside N*H*W > 32 768 with H*W % 4 == 0).       */
+int uz_bn_route(int direction, int N, int C, int H, int W, int training, int vec, int flags, int* out6);
 int uz_avgpool2_fwd_ex(const float* x, int C, int CtotX, float* y, int CtotY, int N, int H, int W,
                        const float* x_amax, float* y_amax, int out_packed, void* stream);
 int uz_bilinear2x_fwd_ex(const float* x, int C, int CtotX, float* y, int CtotY, int N, int H, int W, int align_corners,

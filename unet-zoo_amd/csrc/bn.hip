@@ -1045,9 +1045,65 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__
     }
 }
 
-inline bool vec_ok(int HW, const void* a, const void* b, const void* c) {
+// ---- kernel choice.  Every entry point below and the host-side query uz_bn_route decide through bn_route() and the predicates it
+// is made of, and through nothing else: the query cannot drift from the dispatch (tests/_bn_routes.py states the route of a case on
+// each side of every threshold through it).
+inline bool views_aligned(const void* a, const void* b, const void* c) {
     auto al = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    return (HW % 4 == 0) && al(a) && al(b) && al(c);
+    return al(a) && al(b) && al(c);
+}
+inline bool vec_ok(int HW, bool aligned) { return (HW % 4 == 0) && aligned; }
+// UZ_BN_MID_FWD=0 / UZ_BN_MID=0: no one-launch mid path in the forward / backward pass (A/B only; read once per process)
+bool mid_fwd_on() {
+    static const bool on = !(getenv("UZ_BN_MID_FWD") && atoi(getenv("UZ_BN_MID_FWD")) == 0);
+    return on;
+}
+bool mid_bwd_on() {
+    static const bool on = !(getenv("UZ_BN_MID") && atoi(getenv("UZ_BN_MID")) == 0);
+    return on;
+}
+inline bool small_plane(size_t total) { return total <= (size_t)SMALL_LIMIT; }
+inline int fused_limit(bool mid_on, int HW) { return (mid_on && HW % 4 == 0) ? MID_LIMIT : SMALL_LIMIT; }
+inline bool mid_half(size_t total) { return total <= (size_t)MID_HALF_LIMIT && mid_half_on(); }
+inline bool b16_plane(size_t total, int HW) { return total > (size_t)MID_LIMIT && HW % 4 == 0; }
+// images per reduction workgroup: keep about 2048 workgroups (8 per CU) so that the fp64 block reduction is
+// amortised over several planes without starving the chip
+inline void reduction_groups(int N, int parts, int C, int& nb_out, int& ngrp_out) {
+    long long nb = (long long)N * parts * C / 2048;
+    if (nb < 1) nb = 1;
+    if (nb > 8) nb = 8;
+    nb_out = (int)nb;
+    ngrp_out = uz::ceil_div(N, nb_out);
+}
+
+enum { BN_SMALL = 0, BN_MID = 1, BN_LARGE = 2, BN_LARGE_ST = 3 };                                       // BnRoute::path
+enum { BN_F_CONV_PARTIALS = 1, BN_F_OUT_PACKED = 2, BN_F_DBIAS_PARTIALS = 4, BN_F_SLABS = 8, BN_F_B16 = 16 };   // the flag word of bn_route
+struct BnRoute {
+    int path;           // BN_SMALL / BN_MID / BN_LARGE, or BN_LARGE_ST for the bf16-storage entry points
+    int inst;           // small: elements per thread (2 / 8 / 16); mid: threads per workgroup (512 / 1024); large: 0
+    int parts;          // plane chunks of CHUNK elements
+    int nb, ngrp;       // large paths: images per reduction workgroup, number of image groups (0 elsewhere)
+    int vec;            // the float4 instance runs (mid and bf16 storage: always)
+};
+// direction 0 forward / 1 backward; aligned: every view the call inspects is 16-byte aligned (views_aligned); flags: BN_F_* of the call
+BnRoute bn_route(int direction, int N, int C, int HW, int training, bool aligned, int flags) {
+    BnRoute r = {};
+    const size_t total = (size_t)N * HW;
+    r.parts = uz::ceil_div(HW, CHUNK);
+    if (flags & BN_F_B16) {
+        r.path = BN_LARGE_ST; r.vec = 1;
+        reduction_groups(N, r.parts, C, r.nb, r.ngrp);
+        return r;
+    }
+    if (small_plane(total)) { r.path = BN_SMALL; r.inst = small_ept((int)total); return r; }
+    const bool vec = vec_ok(HW, aligned);
+    const bool mid = direction == 0
+        ? training && !(flags & (BN_F_CONV_PARTIALS | BN_F_SLABS)) && total <= (size_t)fused_limit(mid_fwd_on(), HW) && vec
+        : !(flags & (BN_F_CONV_PARTIALS | BN_F_OUT_PACKED | BN_F_DBIAS_PARTIALS)) && total <= (size_t)fused_limit(mid_bwd_on(), HW) && vec;
+    if (mid) { r.path = BN_MID; r.inst = mid_half(total) ? 512 : 1024; r.vec = 1; return r; }
+    r.path = BN_LARGE; r.vec = vec;
+    reduction_groups(N, r.parts, C, r.nb, r.ngrp);
+    return r;
 }
 
 }  // namespace
@@ -1059,15 +1115,6 @@ extern "C" size_t uz_bn_workspace(int C, int N, int H, int W) {
 }
 
 namespace {
-// images per reduction workgroup: keep about 2048 workgroups (8 per CU) so that the fp64 block reduction is
-// amortised over several planes without starving the chip
-void reduction_groups(BnP& p) {
-    long long nb = (long long)p.N * p.parts * p.C / 2048;
-    if (nb < 1) nb = 1;
-    if (nb > 8) nb = 8;
-    p.nb = (int)nb;
-    p.ngrp = uz::ceil_div(p.N, p.nb);
-}
 // images per workgroup of the *_st apply kernels.  Measured on 96 ch x 128 x (128 x 64) in bf16: groups of 6 - 8 planes (64 k elements
 // per workgroup) ran the apply launches 4 - 8 % SLOWER than one 16 KB plane per workgroup (4.17 vs 4.35 TB/s forward, 4.39 vs 4.76
 // backward) - the planes are not prologue-bound, and a 4x unroll of the 8-wide loops changed nothing either: what is left is the fixed cost of the 2 - 3 launches per unit
@@ -1096,26 +1143,28 @@ static int bn_relu_fwd_impl(const float* y, int C, int CtotY, const float* gamma
                             const float* conv_partials, int n_partials, const float* slabs, int n_slabs, const float* conv_bias, void* stream,
                             int save4 = 0, int out_packed = 0, int phase = 0) {
     UZ_REQUIRE(C > 0 && N > 0 && H > 0 && W > 0, "bn_relu_fwd: empty tensor");
-    const bool mid = training && !conv_partials && !slabs && (size_t)N * H * W > SMALL_LIMIT && (size_t)N * H * W <= (size_t)uz_bn_fwd_fused_limit(H, W) &&
-                     vec_ok(H * W, y, a, nullptr);
-    UZ_REQUIRE(!out_packed || (training && (conv_partials || mid || phase == 2) && a_amax && (size_t)N * H * W > SMALL_LIMIT),
+    const size_t total = (size_t)N * H * W;
+    const BnRoute r = bn_route(0, N, C, H * W, training, views_aligned(y, a, nullptr),
+                               (conv_partials ? BN_F_CONV_PARTIALS : 0) | (out_packed ? BN_F_OUT_PACKED : 0) | (slabs ? BN_F_SLABS : 0));
+    const bool mid = r.path == BN_MID;
+    UZ_REQUIRE(!out_packed || (training && (conv_partials || mid || phase == 2) && a_amax && !small_plane(total)),
                "bn_relu_fwd_ex: split storage needs the output's bound before the apply pass - training mode, a bound slot, and statistics from the convolution's partials (or the one-launch mid path)");
-    UZ_REQUIRE(!conv_partials || (training && n_partials > 0 && (size_t)N * H * W > SMALL_LIMIT), "bn_relu_fwd: convolution partials only serve the training-mode large-plane path");
+    UZ_REQUIRE(!conv_partials || (training && n_partials > 0 && !small_plane(total)), "bn_relu_fwd: convolution partials only serve the training-mode large-plane path");
     UZ_REQUIRE(N <= 65535 && C <= 65535, "bn_relu_fwd: N or C exceeds grid limits");
     UZ_REQUIRE(!training || save_mean_rstd, "bn_relu_fwd: training needs save_mean_rstd");
     UZ_REQUIRE(training || (running_mean && running_var), "bn_relu_fwd: eval needs running statistics");
-    UZ_REQUIRE(!training || (size_t)N * H * W > 1, "bn_relu_fwd: Expected more than 1 value per channel when training");
+    UZ_REQUIRE(!training || total > 1, "bn_relu_fwd: Expected more than 1 value per channel when training");
     hipStream_t st = uz::S(stream);
     BnP p = {}; p.flags = uz::dev_flags_ptr();
     p.y = y; p.gamma = gamma; p.beta = beta; p.rmean = running_mean; p.rvar = running_var; p.save = save_mean_rstd;
     p.out = a; p.C = C; p.CtotY = CtotY; p.CtotOut = CtotA; p.N = N; p.HW = H * W;
-    p.parts = uz::ceil_div(p.HW, CHUNK);
+    p.parts = r.parts; p.nb = r.nb; p.ngrp = r.ngrp;
     p.eps = eps; p.momentum = momentum; p.training = training; p.relu = relu; p.amax = a_amax;
     p.save4 = save4; p.out_packed = out_packed;
-    UZ_REQUIRE(!slabs || (n_slabs > 1 && (size_t)N * p.HW <= SMALL_LIMIT), "bn_relu_fwd_slabs: split-K slabs only serve the small-plane path (N*H*W <= 4096)");
-    if ((size_t)N * p.HW <= SMALL_LIMIT) {
+    UZ_REQUIRE(!slabs || (n_slabs > 1 && r.path == BN_SMALL), "bn_relu_fwd_slabs: split-K slabs only serve the small-plane path (N*H*W <= 4096)");
+    if (r.path == BN_SMALL) {
         p.slab = slabs; p.nslab = n_slabs; p.cbias = conv_bias; p.ywr = const_cast<float*>(y);
-        switch (small_ept(N * H * W)) {
+        switch (r.inst) {
             case 2: hipLaunchKernelGGL(bn_fused_small_fwd<2>, dim3(C), dim3(256), 0, st, p); break;
             case 8: hipLaunchKernelGGL(bn_fused_small_fwd<8>, dim3(C), dim3(256), 0, st, p); break;
             default: hipLaunchKernelGGL(bn_fused_small_fwd<SMALL_LIMIT / 256>, dim3(C), dim3(256), 0, st, p);
@@ -1123,8 +1172,7 @@ static int bn_relu_fwd_impl(const float* y, int C, int CtotY, const float* gamma
         return uz::check_launch("bn_fused_small_fwd");
     }
     if (mid) {
-        const bool half = (size_t)N * p.HW <= MID_HALF_LIMIT && mid_half_on();
-        if (half) {
+        if (r.inst == 512) {
             if (out_packed) hipLaunchKernelGGL((bn_fused_mid_fwd<true, 512, 4>), dim3(C), dim3(512), 0, st, p);
             else hipLaunchKernelGGL((bn_fused_mid_fwd<false, 512, 4>), dim3(C), dim3(512), 0, st, p);
         } else {
@@ -1133,9 +1181,8 @@ static int bn_relu_fwd_impl(const float* y, int C, int CtotY, const float* gamma
         }
         return uz::check_launch("bn_fused_mid_fwd");
     }
-    const bool vec = vec_ok(p.HW, y, a, nullptr);
+    const bool vec = r.vec != 0;
     const dim3 grid(p.parts, C, N);
-    reduction_groups(p);
     const dim3 rgrid(p.parts, C, p.ngrp);
     // phase (uz_bn_relu_fwd_phase): 1 = the statistics launch only (table + bound; y and a are not touched), 2 = the apply pass only (the table holds
     // this step's statistics already), 0 = both
@@ -1231,9 +1278,10 @@ extern "C" int uz_bn_relu_bwd_ex(const float* da, int CtotDa, const float* y, in
                                  const float* conv_partials, int n_partials, int out_packed, double* dbias_partials,
                                  const float* da_slabs, int n_da_slabs, void* stream) {
     UZ_REQUIRE(C > 0 && N > 0 && H > 0 && W > 0, "bn_relu_bwd: empty tensor");
-    UZ_REQUIRE(!da_slabs || (n_da_slabs > 1 && (size_t)N * H * W <= SMALL_LIMIT), "bn_relu_bwd_ex: da_slabs only serve the small-plane path (N*H*W <= 4096)");
-    UZ_REQUIRE(!dbias_partials || (!dbias && (size_t)N * H * W > SMALL_LIMIT), "bn_relu_bwd_ex: dbias_partials replaces dbias on the large-plane path");
-    UZ_REQUIRE(!(conv_partials || out_packed) || (size_t)N * H * W > SMALL_LIMIT, "bn_relu_bwd_ex: folded statistics / split storage only serve the large-plane path");
+    const size_t total = (size_t)N * H * W;
+    UZ_REQUIRE(!da_slabs || (n_da_slabs > 1 && small_plane(total)), "bn_relu_bwd_ex: da_slabs only serve the small-plane path (N*H*W <= 4096)");
+    UZ_REQUIRE(!dbias_partials || (!dbias && !small_plane(total)), "bn_relu_bwd_ex: dbias_partials replaces dbias on the large-plane path");
+    UZ_REQUIRE(!(conv_partials || out_packed) || !small_plane(total), "bn_relu_bwd_ex: folded statistics / split storage only serve the large-plane path");
     UZ_REQUIRE(!conv_partials || n_partials > 0, "bn_relu_bwd_ex: conv_partials without rows");
     UZ_REQUIRE(!out_packed || dy_amax, "bn_relu_bwd_ex: split storage needs the bound slot");
     UZ_REQUIRE(N <= 65535 && C <= 65535, "bn_relu_bwd: N or C exceeds grid limits");
@@ -1243,20 +1291,21 @@ extern "C" int uz_bn_relu_bwd_ex(const float* da, int CtotDa, const float* y, in
     p.y = y; p.da = da; p.gamma = gamma; p.beta = beta; p.save = const_cast<float*>(save_mean_rstd);
     p.out = dy; p.dgamma = dgamma; p.dbeta = dbeta; p.dbias = dbias;
     p.C = C; p.CtotY = CtotY; p.CtotDa = CtotDa; p.CtotOut = CtotDy; p.N = N; p.HW = H * W;
-    p.parts = uz::ceil_div(p.HW, CHUNK);
+    const BnRoute r = bn_route(1, N, C, H * W, 1, views_aligned(y, da, dy),
+                               (conv_partials ? BN_F_CONV_PARTIALS : 0) | (out_packed ? BN_F_OUT_PACKED : 0) | (dbias_partials ? BN_F_DBIAS_PARTIALS : 0) | (da_slabs ? BN_F_SLABS : 0));
+    p.parts = r.parts; p.nb = r.nb; p.ngrp = r.ngrp;
     p.training = 1; p.relu = relu; p.amax = dy_amax;
-    if ((size_t)N * p.HW <= SMALL_LIMIT) {
+    if (r.path == BN_SMALL) {
         p.slab = da_slabs; p.nslab = n_da_slabs;
-        switch (small_ept(N * H * W)) {
+        switch (r.inst) {
             case 2: hipLaunchKernelGGL(bn_fused_small_bwd<2>, dim3(C), dim3(256), 0, st, p); break;
             case 8: hipLaunchKernelGGL(bn_fused_small_bwd<8>, dim3(C), dim3(256), 0, st, p); break;
             default: hipLaunchKernelGGL(bn_fused_small_bwd<SMALL_LIMIT / 256>, dim3(C), dim3(256), 0, st, p);
         }
         return uz::check_launch("bn_fused_small_bwd");
     }
-    static const bool mid_on = !(getenv("UZ_BN_MID") && atoi(getenv("UZ_BN_MID")) == 0);
-    if (mid_on && !conv_partials && !out_packed && !dbias_partials && (size_t)N * p.HW <= MID_LIMIT && vec_ok(p.HW, y, da, dy)) {
-        if ((size_t)N * p.HW <= MID_HALF_LIMIT && mid_half_on()) hipLaunchKernelGGL((bn_fused_mid_bwd<512, 4>), dim3(C), dim3(512), 0, st, p);
+    if (r.path == BN_MID) {
+        if (r.inst == 512) hipLaunchKernelGGL((bn_fused_mid_bwd<512, 4>), dim3(C), dim3(512), 0, st, p);
         else hipLaunchKernelGGL((bn_fused_mid_bwd<1024, 8>), dim3(C), dim3(1024), 0, st, p);
         return uz::check_launch("bn_fused_mid_bwd");
     }
@@ -1266,9 +1315,8 @@ extern "C" int uz_bn_relu_bwd_ex(const float* da, int CtotDa, const float* y, in
         p.part2 = dbias_partials;
         p.dbias = reinterpret_cast<float*>(dbias_partials);      // (non-null: "write the partials")
     }
-    const bool vec = vec_ok(p.HW, y, da, dy);
+    const bool vec = r.vec != 0;
     const dim3 grid(p.parts, C, N);
-    reduction_groups(p);
     const dim3 rgrid(p.parts, C, p.ngrp);
     const bool pre = conv_partials || out_packed;
     p.cpart = conv_partials; p.ncpart = n_partials; p.out_packed = out_packed;
@@ -1296,18 +1344,23 @@ extern "C" int uz_bn_relu_bwd_ex(const float* da, int CtotDa, const float* y, in
     return 0;
 }
 // rows of dbias_partials a large-plane uz_bn_relu_bwd_ex call writes ([rows][C] doubles)
-extern "C" int uz_bn_bwd_dbias_rows(int N, int H, int W) { return (size_t)N * H * W > (size_t)uz_bn_bwd_fused_limit(H, W) ? N * uz::ceil_div(H * W, CHUNK) : 0; }
+extern "C" int uz_bn_bwd_dbias_rows(int N, int H, int W) { return (size_t)N * H * W > (size_t)fused_limit(mid_bwd_on(), H * W) ? N * uz::ceil_div(H * W, CHUNK) : 0; }
 // largest N*H*W whose training-mode FORWARD runs as one launch (small or mid path; the plans ask the convolution for no statistics
 // partials there)
-extern "C" int uz_bn_fwd_fused_limit(int H, int W) {
-    static const bool mid_on = !(getenv("UZ_BN_MID_FWD") && atoi(getenv("UZ_BN_MID_FWD")) == 0);
-    return (mid_on && (H * W) % 4 == 0) ? MID_LIMIT : SMALL_LIMIT;
-}
+extern "C" int uz_bn_fwd_fused_limit(int H, int W) { return fused_limit(mid_fwd_on(), H * W); }
 // largest N*H*W whose backward runs as ONE launch with the channel's batch held on chip (no tensor-wide bound before the first
 // write: dy of such a unit is fp32, never split storage): the small path's limit, or the mid path's where H*W allows float4 rows
-extern "C" int uz_bn_bwd_fused_limit(int H, int W) {
-    static const bool mid_on = !(getenv("UZ_BN_MID") && atoi(getenv("UZ_BN_MID")) == 0);
-    return (mid_on && (H * W) % 4 == 0) ? MID_LIMIT : SMALL_LIMIT;
+extern "C" int uz_bn_bwd_fused_limit(int H, int W) { return fused_limit(mid_bwd_on(), H * W); }
+// What uz_bn_relu_fwd* (direction 0) / uz_bn_relu_bwd* (direction 1) launch for a call (include/uz_api.h): bn_route()'s answer, which
+// is what the entry points themselves dispatch on.
+extern "C" int uz_bn_route(int direction, int N, int C, int H, int W, int training, int vec, int flags, int* out6) {
+    UZ_REQUIRE(out6 && (direction == 0 || direction == 1), "bn_route: direction 0 (forward) or 1 (backward), and six ints to answer into");
+    UZ_REQUIRE(C > 0 && N > 0 && H > 0 && W > 0, "bn_route: empty tensor");
+    UZ_REQUIRE(!(flags & ~(BN_F_CONV_PARTIALS | BN_F_OUT_PACKED | BN_F_DBIAS_PARTIALS | BN_F_SLABS | BN_F_B16)), "bn_route: unknown flag bits");
+    UZ_REQUIRE(!(flags & BN_F_B16) || (b16_plane((size_t)N * H * W, H * W) && vec), "bn_route: the bf16-storage entry points serve N*H*W > 32768, H*W %% 4 == 0 and 16-byte aligned views only");
+    const BnRoute r = bn_route(direction, N, C, H * W, training, vec != 0, flags);
+    out6[0] = r.path; out6[1] = r.inst; out6[2] = r.parts; out6[3] = r.nb; out6[4] = r.ngrp; out6[5] = r.vec;
+    return 0;
 }
 
 // ---- bf16 STORAGE entry points (include/uz_api.h, "bf16 storage").  y / a / da / dy each either fp32 or bf16 (flags), large-plane
@@ -1317,7 +1370,7 @@ extern "C" int uz_bn_relu_fwd_b16(const void* y, int C, int CtotY, const float* 
                                   void* a, int CtotA, int N, int H, int W, float eps, float momentum, int training, int relu,
                                   void* workspace, const float* conv_partials, int n_partials, int y_b16, int a_b16, void* stream) {
     UZ_REQUIRE(C > 0 && N > 0 && H > 0 && W > 0, "bn_relu_fwd_b16: empty tensor");
-    UZ_REQUIRE((size_t)N * H * W > MID_LIMIT && (H * W) % 4 == 0, "bn_relu_fwd_b16: the bf16-storage kernels serve the large-plane path (N*H*W > 32768, H*W %% 4 == 0)");
+    UZ_REQUIRE(b16_plane((size_t)N * H * W, H * W), "bn_relu_fwd_b16: the bf16-storage kernels serve the large-plane path (N*H*W > 32768, H*W %% 4 == 0)");
     UZ_REQUIRE((reinterpret_cast<uintptr_t>(y) & 15) == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0, "bn_relu_fwd_b16: views must be 16-byte aligned");
     UZ_REQUIRE(N <= 65535 && C <= 65535, "bn_relu_fwd_b16: N or C exceeds grid limits");
     UZ_REQUIRE(!training || save_mean_rstd, "bn_relu_fwd_b16: training needs save_mean_rstd");
@@ -1327,12 +1380,12 @@ extern "C" int uz_bn_relu_fwd_b16(const void* y, int C, int CtotY, const float* 
     BnP p = {}; p.flags = uz::dev_flags_ptr();
     p.y = static_cast<const float*>(y); p.gamma = gamma; p.beta = beta; p.rmean = running_mean; p.rvar = running_var; p.save = save_mean_rstd;
     p.out = static_cast<float*>(a); p.C = C; p.CtotY = CtotY; p.CtotOut = CtotA; p.N = N; p.HW = H * W;
-    p.parts = uz::ceil_div(p.HW, CHUNK);
+    const BnRoute r = bn_route(0, N, C, H * W, training, true, BN_F_B16 | (conv_partials ? BN_F_CONV_PARTIALS : 0));
+    p.parts = r.parts; p.nb = r.nb; p.ngrp = r.ngrp;
     p.eps = eps; p.momentum = momentum; p.training = training; p.relu = relu;
     p.yb = y_b16 != 0; p.outb = a_b16 != 0;
     p.nba = apply_group(p);
     const dim3 grid(p.parts, C, uz::ceil_div(N, p.nba));
-    reduction_groups(p);
     if (training && conv_partials) {
         p.pre = 1; p.cpart = conv_partials; p.ncpart = n_partials;
         hipLaunchKernelGGL(bn_finalize_conv_partials, dim3(C), dim3(256), 0, st, p);
@@ -1351,7 +1404,7 @@ extern "C" int uz_bn_relu_bwd_b16(const void* da, int CtotDa, const void* y, int
                                   void* dy, int CtotDy, float* dgamma, float* dbeta, float* dbias,
                                   int N, int H, int W, int relu, void* workspace, int da_b16, int y_b16, int dy_b16, void* stream) {
     UZ_REQUIRE(C > 0 && N > 0 && H > 0 && W > 0, "bn_relu_bwd_b16: empty tensor");
-    UZ_REQUIRE((size_t)N * H * W > MID_LIMIT && (H * W) % 4 == 0, "bn_relu_bwd_b16: the bf16-storage kernels serve the large-plane path (N*H*W > 32768, H*W %% 4 == 0)");
+    UZ_REQUIRE(b16_plane((size_t)N * H * W, H * W), "bn_relu_bwd_b16: the bf16-storage kernels serve the large-plane path (N*H*W > 32768, H*W %% 4 == 0)");
     UZ_REQUIRE((reinterpret_cast<uintptr_t>(y) & 15) == 0 && (reinterpret_cast<uintptr_t>(da) & 15) == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0, "bn_relu_bwd_b16: views must be 16-byte aligned");
     UZ_REQUIRE(N <= 65535 && C <= 65535, "bn_relu_bwd_b16: N or C exceeds grid limits");
     UZ_REQUIRE(save_mean_rstd && workspace, "bn_relu_bwd_b16: needs the saved statistics and a workspace");
@@ -1360,11 +1413,11 @@ extern "C" int uz_bn_relu_bwd_b16(const void* da, int CtotDa, const void* y, int
     p.y = static_cast<const float*>(y); p.da = static_cast<const float*>(da); p.gamma = gamma; p.beta = beta; p.save = const_cast<float*>(save_mean_rstd);
     p.out = static_cast<float*>(dy); p.dgamma = dgamma; p.dbeta = dbeta; p.dbias = dbias;
     p.C = C; p.CtotY = CtotY; p.CtotDa = CtotDa; p.CtotOut = CtotDy; p.N = N; p.HW = H * W;
-    p.parts = uz::ceil_div(p.HW, CHUNK);
+    const BnRoute r = bn_route(1, N, C, H * W, 1, true, BN_F_B16);
+    p.parts = r.parts; p.nb = r.nb; p.ngrp = r.ngrp;
     p.training = 1; p.relu = relu;
     p.yb = y_b16 != 0; p.dab = da_b16 != 0; p.outb = dy_b16 != 0;
     carve(p, workspace);
-    reduction_groups(p);
     hipLaunchKernelGGL(bn_bwd_reduce_partial_st, dim3(p.parts, C, p.ngrp), dim3(256), 0, st, p);
     if (int rc = uz::check_launch("bn_bwd_reduce_partial_st")) return rc;
     p.nba = apply_group(p);
@@ -1387,7 +1440,7 @@ extern "C" int uz_relu_bwd(const float* da, int CtotDa, const float* a, int C, i
     const int HW = H * W, parts = uz::ceil_div(HW, CHUNK);
     double* part2 = dbias ? static_cast<double*>(workspace) : nullptr;
     const dim3 grid(parts, C, N);
-    if (vec_ok(HW, da, a, dy)) hipLaunchKernelGGL(relu_bwd_kernel<true>, grid, dim3(256), 0, st, da, CtotDa, a, CtotA, dy, CtotDy, part2, C, HW, parts, dy_amax);
+    if (vec_ok(HW, views_aligned(da, a, dy))) hipLaunchKernelGGL(relu_bwd_kernel<true>, grid, dim3(256), 0, st, da, CtotDa, a, CtotA, dy, CtotDy, part2, C, HW, parts, dy_amax);
     else hipLaunchKernelGGL(relu_bwd_kernel<false>, grid, dim3(256), 0, st, da, CtotDa, a, CtotA, dy, CtotDy, part2, C, HW, parts, dy_amax);
     if (int rc = uz::check_launch("relu_bwd_kernel")) return rc;
     if (dbias) {
