@@ -62,7 +62,7 @@ int         uz_device_info(int* n_cu, char* name, int name_cap);
 int uz_set_conv_math(int mode);
 int uz_get_conv_math(void);
 /* kernel family a call takes under the current mode: kind 0 fwd / 1 bwd_data / 2 bwd_weight -> 0 fp32 MFMA, 1 split-fp16 MFMA,
- * 2 streaming VALU (1x1 heads with <= 8 outputs).  Used by bench.py to price each op against the roof it runs on.          */
+ * 2 streaming VALU (1x1 heads with 1, 2, 3, 4, 6 or 8 outputs and Cin <= 512: uz_heads_route).  Used by bench.py to price each op. */
 int uz_conv_route(int kind, int Cin, int Cout, int N, int H, int W, int ks);
 size_t uz_conv_workspace(int Cin, int Cout, int N, int H, int W, int ks);   /* covers fwd and bwd_data */
 /* Magnitude bounds (`*_amax`, all nullable): device scalars holding an UPPER BOUND of max|tensor| (any bound within ~2^10 of
@@ -357,6 +357,20 @@ size_t uz_latent_heads_bwd_weight_workspace(int Cin, int L, int N, int H, int W)
 int uz_latent_heads_bwd_weight(const float* h, int Cin, int CinTot, const float* dy_a, const float* dy_b, int L,
                                float* dw_a, float* db_a, float* dw_b, float* db_b, int N, int H, int W,
                                void* workspace, size_t workspace_bytes, void* stream);
+/* What a 1x1 head (ks = 1, at most 8 outputs) or a latent-heads call launches, answered on the host from the very predicates the
+ * entry points dispatch through (the library loads without a GPU).  op: 0 the 1x1 forward (uz_conv_fwd* with relu = 0,
+ * uz_conv1x1_fwd_b16), 1 its data gradient, 2 its weight gradient, 3 uz_latent_heads_fwd, 4 uz_latent_heads_bwd_data,
+ * 5 uz_latent_heads_bwd_weight.  Cout: the output channels of ops 0 - 2, L of ops 3 - 5; Cin, N, H, W as the call takes them;
+ * aligned != 0: every view the call inspects is 16-byte aligned (x and y; dy and dx; x and dy; h, mu, pre_sigma, sigma and - when
+ * given - z and eps; dy_a, dy_b and dh; h, dy_a and dy_b).  out5 receives
+ *   [0] form: 0 scalar, 1 float4, 2 channel-parallel forward (op 3 only), 3 not covered by the streaming kernels (ops 0 - 2 with
+ *       Cout outside {1, 2, 3, 4, 6, 8} or Cin > 512: the call runs the MFMA kernels, [1] .. [4] stay 0);
+ *   [1] workgroups of 1 024 pixels per image (ops 0, 1, 3, 4), or QPB, the pixel quads per workgroup, of form 2;
+ *   [2] channel groups (grid.z) and [3] channels per group of the data gradients (ops 1, 4), the last group may be ragged;
+ *   [4] chunks of the weight gradients (ops 2, 5): ceil(N*H*W / 16 384), at most 64.
+ * Honours UZ_HEADS_PAR as the dispatch does.  Returns 0, or -1 for arguments no entry point accepts (empty tensor, latent heads
+ * outside 1 <= L <= 4, Cin <= 512).                                                                                              */
+int uz_heads_route(int op, int Cin, int Cout, int N, int H, int W, int aligned, int* out5);
 /* KL_two_gauss_with_diag_cov with the reference's sigma1*sigma0 quirk (phiseg.py:436-453),
  * times `weight` (4**level, phiseg.py:463).  Tensors are (N, per_sample) contiguous.
  * fwd writes loss_out[0] (single block, ordered); bwd writes the four gradients * scale. */
@@ -616,6 +630,17 @@ int uz_depth_lerp2x_fwd(const float* x, int C, int CtotX, float* y, int CtotY, i
 int uz_depth_lerp2x_bwd(const float* dy, int C, int CtotDy, float* dx, int CtotDx, int D, int H, int W, int accumulate, void* stream);
 int uz_nearest3d_fwd(const float* x, int C, int CtotX, float* y, int CtotY, int D, int H, int W, int f, int fz, void* stream);
 int uz_nearest3d_bwd(const float* dy, int C, int CtotDy, float* dx, int CtotDx, int D, int H, int W, int f, int fz, int accumulate, void* stream);
+/* What a volume call launches, answered on the host from the very route functions the entry points dispatch through (the library
+ * loads without a GPU).  op: 0 uz_avgpool3d_fwd, 1 uz_avgpool3d_bwd, 2 uz_depth_lerp2x_fwd, 3 uz_depth_lerp2x_bwd, 4 uz_nearest3d_fwd,
+ * 5 uz_nearest3d_bwd, 6 - 9 the *_b16 forms of 0 - 3, 10 uz_w3d_permute (C = Cout, D = Cin), 11 uz_cvt_f32_to_b16 / uz_cvt_b16_to_f32
+ * of C*D*H*W elements.  C, D, H, W as the entry point takes them; f, fz = the factors of ops 4 and 5 (unused elsewhere); align_* =
+ * byte alignment (16, 8 or 4) of the views the dispatch inspects: src = x / dy, dst = y / dx.  out2 receives
+ *   [0] kernel: 0 scalar, 1 float4, 2 bf16 storage (float4 wide), 3 one wave per element (nearest backward from 64 children on);
+ *   [1] workgroups along grid.x: per plane for ops 0 - 9 (256 elements, float4s or float2 pairs per workgroup, capped at 64 - the
+ *       grid-stride loop covers the rest; kernel 3: four elements per workgroup, uncapped), in all for ops 10 (cap 2 048) and 11
+ *       (cap 65 535).
+ * Returns 0, or -1 for arguments no entry point accepts (empty tensor, a *_b16 form off its float4 shape or alignment).            */
+int uz_vol_route(int op, int C, int D, int H, int W, int f, int fz, int align_src, int align_dst, int* out2);
 
 /* ---------------------------------------------------------------- bf16 storage (BASELINE config 5: PHiSeg3D "bf16"; phiseg3D.py:13-35)
  * A tensor in bf16 storage has the same N x C x H x W shape with 2-byte elements (round to nearest even when written, widened exactly

@@ -199,4 +199,12 @@ CASES = [
     R("dgrad", 1, 16, 3, 40, 128, 128, 3, route=1, parts=1, cot=32, relu=1024),             # data gradient onto 3 channels: split kernel, 32-wide tile
     R("fwd", 1, 32, 12, 32, 128, 128, 3, gpu=False, route=1, parts=1, cot=32, bn=2048),                # 12 input channels (one zero-padded chunk)
     R("wgrad", 1, 32, 12, 32, 128, 128, 3, gpu=False, route=1, slabs=256),                             # narrow-side (12) split weight gradient
+    # 1 x 1 kernels with 5 and 7 outputs (conv1x1_small.hip conv1x1_small_ok): between the streaming heads' instances (1, 2, 3, 4, 6, 8;
+    # tests/_head_routes.py), so the matrix kernels run them, with slabs
+    R("fwd", 0, 2, 38, 5, 16, 16, 1, route=0, parts=1, cot=32, bn=0),
+    R("dgrad", 0, 2, 38, 5, 16, 16, 1, route=0, parts=1, cot=32, relu=0),
+    R("wgrad", 0, 2, 38, 5, 16, 16, 1, route=0, slabs=32),
+    R("fwd", 1, 2, 38, 7, 16, 16, 1, route=0, parts=1, cot=32, bn=0),
+    R("dgrad", 1, 2, 38, 7, 16, 16, 1, route=0, parts=1, cot=32, relu=0),
+    R("wgrad", 1, 2, 38, 7, 16, 16, 1, route=0, slabs=32),
 ]

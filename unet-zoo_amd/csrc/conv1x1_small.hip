@@ -17,6 +17,7 @@ constexpr int PIX = 1024;        // pixels per workgroup (256 threads x float4)
 struct C1P {
     const float* x; const float* w; const float* bias; const float* dy; float* y; float* dx; double* part;
     int Cin, CinTot, Cout, CoutTot, N, HW, nchunk, accumulate, cgroup;
+    int wvec;        // weight gradient: float4 sweep (H*W % 4 == 0 and 16-byte aligned x and dy views, heads_vec below); 0: scalar sweep
     int xb16;        // the many-channel tensor (x; dx in the data gradient) holds 2-byte bf16 elements (float4 paths only); y / dy stay fp32
 };
 
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void c1_bwd_weight_partial(const C1P p) {
 #pragma unroll
     for (int n = 0; n < 2 * NO; ++n) dacc[n] = 0.0;
     // fp32 running sums are flushed into fp64 every 32 steps; (b, q) advance incrementally (no per-step division)
-    if (p.HW % 4 == 0 && per % 4 == 0) {
+    if (p.wvec) {
         float4 acc[NO], bacc[NO];
 #pragma unroll
         for (int n = 0; n < NO; ++n) { acc[n] = make_float4(0.f, 0.f, 0.f, 0.f); bacc[n] = make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -201,15 +202,53 @@ __global__ __launch_bounds__(256) void c1_bwd_weight_final(const double* __restr
         db[i] = (float)s;
     }
 }
-inline bool vec4(int HW, const void* a, const void* b) {
-    return HW % 4 == 0 && (reinterpret_cast<uintptr_t>(a) & 15) == 0 && (reinterpret_cast<uintptr_t>(b) & 15) == 0;
+
+// ---- kernel choice.  Every entry point of this file and the host-side query uz_heads_route decide through the predicates below and
+// through nothing else (tests/_head_routes.py pins each of them from both sides).
+enum { HF_SCALAR = 0, HF_VEC = 1, HF_PAR = 2, HF_MFMA = 3 };
+constexpr int CIN_MAX = 512;            // MAXN * CIN_MAX floats: the weights' LDS image (filled exactly by 8 outputs / L = 4 at 512 channels)
+constexpr int WCHUNK = 16384;           // pixels per weight-gradient chunk
+constexpr int WCHUNK_MAX = 64;
+constexpr int PAR_QUADS_MAX = 16384;    // the channel-parallel forward serves N * quads up to here
+inline bool al16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
+// the instantiated output counts of C1_DISPATCH / C1_W
+inline bool heads_outputs_covered(int Cout) { return Cout == 1 || Cout == 2 || Cout == 3 || Cout == 4 || Cout == 6 || Cout == 8; }
+// float4 form: every plane of every inspected view starts on a 16-byte boundary
+inline bool heads_vec(int HW, bool aligned) { return HW % 4 == 0 && aligned; }
+inline int heads_pixblocks(int HW) { return uz::ceil_div(HW, PIX); }
+// data gradient: low-resolution planes have few pixel blocks - split the input channels over grid.z until ~1024 workgroups exist
+inline void heads_dgrad_groups(int Cin, int N, int HW, int& groups, int& cgroup) {
+    const int pixblk = heads_pixblocks(HW) * N;
+    int g = uz::ceil_div(1024, pixblk);
+    if (g > uz::ceil_div(Cin, 8)) g = uz::ceil_div(Cin, 8);
+    if (g < 1) g = 1;
+    cgroup = uz::ceil_div(Cin, g);
+    groups = uz::ceil_div(Cin, cgroup);
 }
+inline int heads_nchunk(int N, int H, int W) {
+    const long long total = (long long)N * H * W;
+    const int nchunk = (int)((total + WCHUNK - 1) / WCHUNK);
+    return nchunk > WCHUNK_MAX ? WCHUNK_MAX : nchunk;
+}
+// channel-parallel forward of the latent heads: the latent hierarchy's own planes (a power-of-two number of pixel quads, at most 1024
+// pixels per image at moderate batch).  qpb_log2: QPB = min(quads, 64) pixel quads per workgroup
+inline bool heads_par(bool vec, int HW, int N, int& qpb_log2) {
+    const int quads = HW / 4;
+    const char* par_env = getenv("UZ_HEADS_PAR");
+    if (!(vec && quads >= 1 && (quads & (quads - 1)) == 0 && (long long)N * quads <= PAR_QUADS_MAX && !(par_env && atoi(par_env) == 0))) return false;
+    int lg = 0;
+    while ((1 << lg) < quads && lg < 6) ++lg;
+    qpb_log2 = lg;
+    return true;
+}
+inline bool latent_heads_ok(int Cin, int L) { return L >= 1 && L <= 4 && Cin >= 1 && Cin <= CIN_MAX; }
 
 }  // namespace
 
 namespace uz {
 
-bool conv1x1_small_ok(int Cin, int Cout) { return Cout <= MAXN && Cin <= 512; }
+// exactly what C1_DISPATCH / C1_W cover: their -2 default is unreachable behind this check (kept as the guard of the switch)
+bool conv1x1_small_ok(int Cin, int Cout) { return heads_outputs_covered(Cout) && Cin >= 1 && Cin <= CIN_MAX; }
 
 #define C1_DISPATCH(KERN, VECFLAG, GRID)                                                                     \
     switch (p.Cout) {                                                                                        \
@@ -226,9 +265,9 @@ bool conv1x1_small_ok(int Cin, int Cout) { return Cout <= MAXN && Cin <= 512; }
 int conv1x1_small_fwd(const float* x, int Cin, int CinTot, const float* w, const float* bias, float* y, int Cout, int CoutTot,
                       int N, int H, int W, hipStream_t st, int x_b16) {
     C1P p = {}; p.xb16 = x_b16; p.x = x; p.w = w; p.bias = bias; p.y = y; p.Cin = Cin; p.CinTot = CinTot; p.Cout = Cout; p.CoutTot = CoutTot; p.N = N; p.HW = H * W;
-    const bool v = vec4(p.HW, x, y);
+    const bool v = heads_vec(p.HW, al16(x) && al16(y));
     if (x_b16 && !v) return fail("conv1x1 forward: bf16 storage needs H*W %% 4 == 0 and 16-byte aligned views");
-    const dim3 grid(ceil_div(p.HW, PIX), N);
+    const dim3 grid(heads_pixblocks(p.HW), N);
     C1_DISPATCH(c1_fwd, v, grid)
     return check_launch("c1_fwd");
 }
@@ -236,31 +275,24 @@ int conv1x1_small_bwd_data(const float* dy, int Cout, int CoutTot, const float* 
                            int N, int H, int W, int accumulate, hipStream_t st, int dx_b16) {
     C1P p = {}; p.xb16 = dx_b16; p.dy = dy; p.w = w; p.dx = dx; p.Cin = Cin; p.CinTot = CinTot; p.Cout = Cout; p.CoutTot = CoutTot; p.N = N; p.HW = H * W;
     p.accumulate = accumulate;
-    const bool v = vec4(p.HW, dy, dx);
+    const bool v = heads_vec(p.HW, al16(dy) && al16(dx));
     if (dx_b16 && !v) return fail("conv1x1 data gradient: bf16 storage needs H*W %% 4 == 0 and 16-byte aligned views");
-    // low-resolution planes have few pixel blocks: split the input channels over grid.z until ~1024 workgroups exist
-    const int pixblk = ceil_div(p.HW, PIX) * N;
-    int groups = ceil_div(1024, pixblk);
-    if (groups > ceil_div(Cin, 8)) groups = ceil_div(Cin, 8);
-    if (groups < 1) groups = 1;
-    p.cgroup = ceil_div(Cin, groups);
-    const dim3 grid(ceil_div(p.HW, PIX), N, ceil_div(Cin, p.cgroup));
+    int groups;
+    heads_dgrad_groups(Cin, N, p.HW, groups, p.cgroup);
+    const dim3 grid(heads_pixblocks(p.HW), N, groups);
     C1_DISPATCH(c1_bwd_data, v, grid)
     return check_launch("c1_bwd_data");
 }
 size_t conv1x1_small_bwd_weight_ws(int Cin, int Cout, int N, int H, int W) {
-    const long long total = (long long)N * H * W;
-    int nchunk = (int)((total + 16383) / 16384);
-    if (nchunk > 64) nchunk = 64;
+    const int nchunk = heads_nchunk(N, H, W);
     return ((size_t)nchunk * Cout * Cin + (size_t)nchunk * Cout) * sizeof(double);
 }
 int conv1x1_small_bwd_weight(const float* x, int Cin, int CinTot, const float* dy, int Cout, int CoutTot, float* dw, float* db,
                              int N, int H, int W, void* ws, hipStream_t st, int x_b16) {
-    if (x_b16 && ((H * W) % 4 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0)) return fail("conv1x1 weight gradient: bf16 storage needs H*W %% 4 == 0 and a 16-byte aligned view");
     C1P p = {}; p.xb16 = x_b16; p.x = x; p.dy = dy; p.Cin = Cin; p.CinTot = CinTot; p.Cout = Cout; p.CoutTot = CoutTot; p.N = N; p.HW = H * W;
-    const long long total = (long long)N * H * W;
-    p.nchunk = (int)((total + 16383) / 16384);
-    if (p.nchunk > 64) p.nchunk = 64;
+    p.wvec = heads_vec(p.HW, al16(x) && al16(dy));       // a view that starts off a 16-byte boundary takes the scalar sweep
+    if (x_b16 && !p.wvec) return fail("conv1x1 weight gradient: bf16 storage needs H*W %% 4 == 0 and 16-byte aligned views");
+    p.nchunk = heads_nchunk(N, H, W);
     p.part = static_cast<double*>(ws);
     const dim3 grid(Cin, p.nchunk);
     const int fg = ceil_div(Cout * Cin, 256);
@@ -315,7 +347,7 @@ struct HP {
     const float* wA; const float* bA; const float* wB; const float* bB;          // head A's rows come first, then head B's
     const float* eps; float* mu; float* pre; float* sigma; float* z; int act;    // forward: A = mu head, B = sigma head
     const float* dyA; const float* dyB; float* dx; int accumulate, cgroup;       // data gradient: dy of either head, [N][L][HW]
-    double* part; int nchunk;                                                    // weight gradient
+    double* part; int nchunk, wvec;                                              // weight gradient (wvec: float4 sweep, as C1P)
 };
 
 __device__ __forceinline__ float head_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }   // = pointwise.hip softplus_f
@@ -507,7 +539,7 @@ __global__ __launch_bounds__(256) void heads_bwd_weight_partial(const HP p) {
     double dacc[2 * NO];
 #pragma unroll
     for (int n = 0; n < 2 * NO; ++n) dacc[n] = 0.0;
-    if (p.HW % 4 == 0 && per % 4 == 0) {
+    if (p.wvec) {
         float4 acc[NO], bacc[NO];
 #pragma unroll
         for (int n = 0; n < NO; ++n) { acc[n] = make_float4(0.f, 0.f, 0.f, 0.f); bacc[n] = make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -595,13 +627,6 @@ __global__ __launch_bounds__(256) void heads_bwd_weight_final(const double* __re
     }
 }
 
-inline bool al16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
-inline int heads_nchunk(int N, int H, int W) {
-    const long long total = (long long)N * H * W;
-    const int nchunk = (int)((total + 16383) / 16384);
-    return nchunk > 64 ? 64 : nchunk;
-}
-
 #define HEADS_DISPATCH(KERN, VECFLAG, GRID)                                                                                     \
     switch (L) {                                                                                                                 \
         case 1: if (VECFLAG) hipLaunchKernelGGL((KERN<1, true>), GRID, dim3(256), 0, st, p); else hipLaunchKernelGGL((KERN<1, false>), GRID, dim3(256), 0, st, p); break; \
@@ -613,7 +638,7 @@ inline int heads_nchunk(int N, int H, int W) {
 
 }  // namespace
 
-extern "C" int uz_latent_heads_ok(int Cin, int L) { return L >= 1 && L <= 4 && Cin >= 1 && Cin <= 512 ? 1 : 0; }
+extern "C" int uz_latent_heads_ok(int Cin, int L) { return latent_heads_ok(Cin, L) ? 1 : 0; }
 
 extern "C" int uz_latent_heads_fwd(const float* h, int Cin, int CinTot, const float* w_mu, const float* b_mu, const float* w_sigma, const float* b_sigma,
                                    const float* eps, float* mu, float* pre_sigma, float* sigma, float* z, int L, int N, int H, int W, int act, void* stream) {
@@ -623,14 +648,10 @@ extern "C" int uz_latent_heads_fwd(const float* h, int Cin, int CinTot, const fl
     hipStream_t st = uz::S(stream);
     HP p = {}; p.x = h; p.Cin = Cin; p.CinTot = CinTot; p.N = N; p.HW = H * W; p.wA = w_mu; p.bA = b_mu; p.wB = w_sigma; p.bB = b_sigma;
     p.eps = eps; p.mu = mu; p.pre = pre_sigma; p.sigma = sigma; p.z = z; p.act = act;
-    const bool v = p.HW % 4 == 0 && al16(h) && al16(mu) && al16(pre_sigma) && al16(sigma) && (!z || (al16(z) && al16(eps)));
-    // the latent hierarchy's own planes (a power-of-two number of pixel quads, at most 1024 pixels per image at moderate batch): channel-parallel form
-    const int quads = p.HW / 4;
-    const char* par_env = getenv("UZ_HEADS_PAR");
-    if (v && quads >= 1 && (quads & (quads - 1)) == 0 && (long long)N * quads <= 16384 && !(par_env && atoi(par_env) == 0)) {
-        int lg = 0;
-        while ((1 << lg) < quads && lg < 6) ++lg;               // QPB = min(quads, 64)
-        const dim3 gp(quads >> lg, N);
+    const bool v = heads_vec(p.HW, al16(h) && al16(mu) && al16(pre_sigma) && al16(sigma) && (!z || (al16(z) && al16(eps))));
+    int lg;
+    if (heads_par(v, p.HW, N, lg)) {                            // channel-parallel form
+        const dim3 gp((p.HW / 4) >> lg, N);
         switch (L) {
             case 1: hipLaunchKernelGGL(heads_fwd_par<1>, gp, dim3(256), 0, st, p, lg); break;
             case 2: hipLaunchKernelGGL(heads_fwd_par<2>, gp, dim3(256), 0, st, p, lg); break;
@@ -640,7 +661,7 @@ extern "C" int uz_latent_heads_fwd(const float* h, int Cin, int CinTot, const fl
         }
         return uz::check_launch("heads_fwd_par");
     }
-    const dim3 grid(uz::ceil_div(p.HW, PIX), N);
+    const dim3 grid(heads_pixblocks(p.HW), N);
     HEADS_DISPATCH(heads_fwd, v, grid)
     return uz::check_launch("heads_fwd");
 }
@@ -651,13 +672,10 @@ extern "C" int uz_latent_heads_bwd_data(const float* dy_a, const float* dy_b, in
     UZ_REQUIRE(dy_a && dy_b && w_a && w_b && dh, "latent_heads_bwd_data: null operand");
     hipStream_t st = uz::S(stream);
     HP p = {}; p.dyA = dy_a; p.dyB = dy_b; p.wA = w_a; p.wB = w_b; p.dx = dh; p.Cin = Cin; p.CinTot = CinTot; p.N = N; p.HW = H * W; p.accumulate = accumulate;
-    const bool v = p.HW % 4 == 0 && al16(dy_a) && al16(dy_b) && al16(dh);
-    const int pixblk = uz::ceil_div(p.HW, PIX) * N;            // as conv1x1_small_bwd_data: channel groups over grid.z on the small planes
-    int groups = uz::ceil_div(1024, pixblk);
-    if (groups > uz::ceil_div(Cin, 8)) groups = uz::ceil_div(Cin, 8);
-    if (groups < 1) groups = 1;
-    p.cgroup = uz::ceil_div(Cin, groups);
-    const dim3 grid(uz::ceil_div(p.HW, PIX), N, uz::ceil_div(Cin, p.cgroup));
+    const bool v = heads_vec(p.HW, al16(dy_a) && al16(dy_b) && al16(dh));
+    int groups;
+    heads_dgrad_groups(Cin, N, p.HW, groups, p.cgroup);         // as conv1x1_small_bwd_data: channel groups over grid.z on the small planes
+    const dim3 grid(heads_pixblocks(p.HW), N, groups);
     HEADS_DISPATCH(heads_bwd_data, v, grid)
     return uz::check_launch("heads_bwd_data");
 }
@@ -675,6 +693,7 @@ extern "C" int uz_latent_heads_bwd_weight(const float* h, int Cin, int CinTot, c
     hipStream_t st = uz::S(stream);
     HP p = {}; p.x = h; p.dyA = dy_a; p.dyB = dy_b; p.Cin = Cin; p.CinTot = CinTot; p.N = N; p.HW = H * W;
     p.nchunk = heads_nchunk(N, H, W);
+    p.wvec = heads_vec(p.HW, al16(h) && al16(dy_a) && al16(dy_b));
     p.part = static_cast<double*>(workspace);
     const dim3 grid(Cin, p.nchunk);
     const int fg = uz::ceil_div(2 * L * Cin, 256);
@@ -688,4 +707,23 @@ extern "C" int uz_latent_heads_bwd_weight(const float* h, int Cin, int CinTot, c
         default: return uz::fail("latent_heads_bwd_weight: %d latent channels per head not covered", L);
     }
     return uz::check_launch("heads_bwd_weight");
+}
+
+// What a heads call launches (include/uz_api.h): the answers of the predicates the entry points above dispatch through.
+extern "C" int uz_heads_route(int op, int Cin, int Cout, int N, int H, int W, int aligned, int* out5) {
+    UZ_REQUIRE(out5 && op >= 0 && op <= 5, "heads_route: op 0 .. 5 and five ints to answer into");
+    UZ_REQUIRE(Cin > 0 && Cout > 0 && N > 0 && H > 0 && W > 0, "heads_route: empty tensor");
+    const bool latent = op >= 3;
+    UZ_REQUIRE(!latent || latent_heads_ok(Cin, Cout), "heads_route: latent heads cover 1 <= L <= 4, Cin <= 512");
+    for (int i = 0; i < 5; ++i) out5[i] = 0;
+    if (!latent && !uz::conv1x1_small_ok(Cin, Cout)) { out5[0] = HF_MFMA; return 0; }
+    const int HW = H * W, kind = op % 3;
+    const bool v = heads_vec(HW, aligned != 0);
+    out5[0] = v ? HF_VEC : HF_SCALAR;
+    if (kind == 2) { out5[4] = heads_nchunk(N, H, W); return 0; }
+    out5[1] = heads_pixblocks(HW);
+    int lg;
+    if (op == 3 && heads_par(v, HW, N, lg)) { out5[0] = HF_PAR; out5[1] = 1 << lg; }
+    if (kind == 1) heads_dgrad_groups(Cin, N, HW, out5[2], out5[3]);
+    return 0;
 }

@@ -536,7 +536,7 @@ extern "C" int uz_conv_fwd_bnstats(const float* x, int Cin, int CinTot, const fl
                                    const float* x_amax, const float* w_amax, float* y_amax,
                                    void* workspace, size_t workspace_bytes, const void* packed_w, float* bn_partials, void* stream) {
     UZ_REQUIRE(!bn_partials || uz_conv_bn_partials(Cin, Cout, N, H, W, ks) > 0, "conv_fwd_bnstats: this shape writes no fused statistics (uz_conv_bn_partials() == 0)");
-    if (ks == 1 && !relu && uz::conv1x1_small_ok(Cin, Cout)) {        // 2..8-output heads: streaming VALU kernel
+    if (ks == 1 && !relu && uz::conv1x1_small_ok(Cin, Cout)) {        // heads with 1, 2, 3, 4, 6 or 8 outputs, Cin <= 512 (conv1x1_small_ok): streaming VALU kernel; -2 cannot come back behind that check
         const int rc = uz::conv1x1_small_fwd(x, Cin, CinTot, w, bias, y, Cout, CoutTot, N, H, W, uz::S(stream));
         if (rc != -2) return rc;
     }

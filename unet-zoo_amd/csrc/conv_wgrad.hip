@@ -733,7 +733,7 @@ static int conv_bwd_weight_impl(const float* x, int Cin, int CinTot, const float
     UZ_REQUIRE((!x_packed || x_amax) && (!dy_packed || dy_amax), "conv_bwd_weight_ex: an operand in split storage needs the bound it was scaled from");
     UZ_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv_bwd_weight: empty tensor");
     UZ_REQUIRE(H < 1024 && W < 1024, "conv_bwd_weight: spatial size too large");
-    if (ks == 1 && uz::conv1x1_small_ok(Cin, Cout)) {                 // 2..8-output heads: streaming VALU kernel
+    if (ks == 1 && uz::conv1x1_small_ok(Cin, Cout)) {                 // heads with 1, 2, 3, 4, 6 or 8 outputs, Cin <= 512 (conv1x1_small_ok): streaming VALU kernel; -2 cannot come back behind that check
         UZ_REQUIRE(workspace && workspace_bytes >= uz::conv1x1_small_bwd_weight_ws(Cin, Cout, N, H, W), "conv_bwd_weight: workspace too small");
         const int rc = uz::conv1x1_small_bwd_weight(x, Cin, CinTot, dy, Cout, CoutTot, dw, db, N, H, W, workspace, uz::S(stream));
         if (rc != -2) return rc;

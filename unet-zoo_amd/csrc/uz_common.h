@@ -98,7 +98,8 @@ int wgrad_split(const float* x, int Cin, int CinTot, const float* dy, int Cout, 
                 int x_packed = 0, const float* x_amax2 = nullptr, int seg_channels = 0, int dy_packed = 0,       // *_packed: operand in split storage
                 int x_b16 = 0, int dy_b16 = 0);                                                                    // *_b16: operand stored as bf16 (single-piece mode)
 
-// conv1x1_small.hip: streaming VALU kernels for 1x1 convolutions with <= 8 outputs (-2 = shape not covered)
+// conv1x1_small.hip: streaming VALU kernels for 1x1 convolutions with 1, 2, 3, 4, 6 or 8 outputs (conv1x1_small_ok says exactly which
+// shapes; -2 = output count not instantiated, unreachable behind that check)
 bool conv1x1_small_ok(int Cin, int Cout);
 int conv1x1_small_fwd(const float* x, int Cin, int CinTot, const float* w, const float* bias, float* y, int Cout, int CoutTot,
                       int N, int H, int W, hipStream_t st, int x_b16 = 0);

@@ -294,7 +294,45 @@ __global__ __launch_bounds__(256) void depth_lerp_bwd_st(const float* __restrict
 }
 
 inline int gx(int n) { int g = (n + 255) / 256; return g < 1 ? 1 : (g > 64 ? 64 : g); }
-inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- kernel choice.  Every entry point below and the host-side query uz_vol_route decide through these functions and through nothing
+// else (tests/_vol_routes.py pins each clause from both sides).  Alignments are uz::align_of values: 16, 8 or 4 bytes.  A route is the
+// kernel and its workgroups per plane (grid.x; the grid-stride loops cover what the gx() cap leaves).
+enum { VK_SCALAR = 0, VK_VEC = 1, VK_ST = 2, VK_WAVE = 3 };
+struct VolRoute { int kernel, gx; };
+constexpr int WAVE_CHILDREN = 64;       // nearest backward: from this many children per element on, one wave per element
+constexpr int W3D_GRID_MAX = 2048, CVT_GRID_MAX = 65535;
+// H x W: the high-resolution plane.  W % 4 == 0 makes Wo even and H W a multiple of 4: every float4 of x / dx and every float2 of y / dy
+// is aligned in every plane of a 16-byte aligned view, whatever the parity of H and D
+VolRoute pool_fwd_route(int H, int W, int al_x, int al_y) {
+    const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+    if (W % 4 == 0 && al_x >= 16 && al_y >= 16 && (H * W) % 4 == 0 && (Ho * Wo) % 2 == 0) return {VK_VEC, gx(Ho * W / 4)};
+    return {VK_SCALAR, gx(Ho * Wo)};
+}
+VolRoute pool_bwd_route(int H, int W, int al_dy, int al_dx) {
+    const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+    if (W % 4 == 0 && al_dx >= 16 && al_dy >= 16 && (Ho * Wo) % 2 == 0) return {VK_VEC, gx(H * W / 4)};
+    return {VK_SCALAR, gx(H * W)};
+}
+VolRoute lerp_route(int HW, int al_src, int al_dst) {
+    if (HW % 4 == 0 && al_src >= 16 && al_dst >= 16) return {VK_VEC, gx(HW / 4)};
+    return {VK_SCALAR, gx(HW)};
+}
+// the bf16-storage entry points serve the float4 shapes only (and, pooling, even H)
+bool pool_st_ok(int H, int W, int al_a, int al_b) { return W % 4 == 0 && H % 2 == 0 && al_a >= 16 && al_b >= 16; }
+bool lerp_st_ok(int HW, int al_a, int al_b) { return HW % 4 == 0 && al_a >= 16 && al_b >= 16; }
+VolRoute pool_fwd_st_route(int H, int W) { return {VK_ST, gx((H + 1) / 2 * W / 4)}; }
+VolRoute pool_bwd_st_route(int H, int W) { return {VK_ST, gx(H * W / 4)}; }
+VolRoute lerp_st_route(int HW) { return {VK_ST, gx(HW / 4)}; }
+// H x W: the low-resolution plane
+VolRoute nearest_fwd_route(int H, int W, int f) { return {VK_SCALAR, gx(H * f * W * f)}; }
+VolRoute nearest_bwd_route(int H, int W, int f, int fz) {
+    if (f * f * fz >= WAVE_CHILDREN && (H * W + 3) / 4 <= 65535) return {VK_WAVE, (H * W + 3) / 4};
+    return {VK_SCALAR, gx(H * W)};
+}
+// (up to 27 x 256 x 256 elements: a grid capped at 64 workgroups walked 64 elements per thread and took 26 us a launch, 72 launches a step)
+int w3d_grid(int Cout, int Cin) { const int g = (Cout * Cin * 27 + 255) / 256; return g < 1 ? 1 : (g > W3D_GRID_MAX ? W3D_GRID_MAX : g); }
+size_t cvt_grid(size_t n) { const size_t g = (n + 255) / 256; return g > CVT_GRID_MAX ? CVT_GRID_MAX : g; }
 
 }  // namespace
 
@@ -305,86 +343,88 @@ extern "C" int uz_absmax_copy(const float* src_slot, float* dst_slot, void* stre
 }
 extern "C" int uz_w3d_permute(const float* src, float* dst, int Cout, int Cin, int mode, void* stream) {
     UZ_REQUIRE(src && dst && Cout > 0 && Cin > 0 && mode >= 0 && mode <= 2, "w3d_permute: bad arguments");
-    // (up to 27 x 256 x 256 elements: a grid capped at 64 workgroups walked 64 elements per thread and took 26 us a launch, 72 launches a step)
-    int g = (Cout * Cin * 27 + 255) / 256;
-    g = g < 1 ? 1 : (g > 2048 ? 2048 : g);
-    hipLaunchKernelGGL(w3d_permute_k, dim3(g), dim3(256), 0, uz::S(stream), src, dst, Cout, Cin, mode);
+    hipLaunchKernelGGL(w3d_permute_k, dim3(w3d_grid(Cout, Cin)), dim3(256), 0, uz::S(stream), src, dst, Cout, Cin, mode);
     return uz::check_launch("w3d_permute_k");
 }
 extern "C" int uz_avgpool3d_fwd(const float* x, int C, int CtotX, float* y, int CtotY, int D, int H, int W, void* stream) {
     UZ_REQUIRE(C > 0 && D > 0 && H > 0 && W > 0 && C <= 65535 && D <= 65535, "avgpool3d_fwd: bad sizes");
     const int Do = (D + 1) / 2, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    if (W % 4 == 0 && a16(x) && a16(y) && (H * W) % 4 == 0 && (Ho * Wo) % 2 == 0)
-        hipLaunchKernelGGL(avgpool3d_fwd_v4, dim3(gx(Ho * W / 4), C, Do), dim3(256), 0, uz::S(stream), x, CtotX, y, CtotY, C, D, H, W, Do, Ho, Wo);
+    const VolRoute r = pool_fwd_route(H, W, uz::align_of(x), uz::align_of(y));
+    if (r.kernel == VK_VEC)
+        hipLaunchKernelGGL(avgpool3d_fwd_v4, dim3(r.gx, C, Do), dim3(256), 0, uz::S(stream), x, CtotX, y, CtotY, C, D, H, W, Do, Ho, Wo);
     else
-        hipLaunchKernelGGL(avgpool3d_fwd_k, dim3(gx(Ho * Wo), C, Do), dim3(256), 0, uz::S(stream), x, CtotX, y, CtotY, C, D, H, W, Do, Ho, Wo);
+        hipLaunchKernelGGL(avgpool3d_fwd_k, dim3(r.gx, C, Do), dim3(256), 0, uz::S(stream), x, CtotX, y, CtotY, C, D, H, W, Do, Ho, Wo);
     return uz::check_launch("avgpool3d_fwd_k");
 }
 extern "C" int uz_avgpool3d_bwd(const float* dy, int C, int CtotDy, float* dx, int CtotDx, int D, int H, int W, int accumulate, void* stream) {
     UZ_REQUIRE(C > 0 && D > 0 && H > 0 && W > 0 && C <= 65535 && D <= 65535, "avgpool3d_bwd: bad sizes");
     const int Do = (D + 1) / 2, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    if (W % 4 == 0 && a16(dx) && a16(dy) && (Ho * Wo) % 2 == 0)
-        hipLaunchKernelGGL(avgpool3d_bwd_v4, dim3(gx(H * W / 4), C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, C, D, H, W, Do, Ho, Wo, accumulate);
+    const VolRoute r = pool_bwd_route(H, W, uz::align_of(dy), uz::align_of(dx));
+    if (r.kernel == VK_VEC)
+        hipLaunchKernelGGL(avgpool3d_bwd_v4, dim3(r.gx, C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, C, D, H, W, Do, Ho, Wo, accumulate);
     else
-        hipLaunchKernelGGL(avgpool3d_bwd_k, dim3(gx(H * W), C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, C, D, H, W, Do, Ho, Wo, accumulate);
+        hipLaunchKernelGGL(avgpool3d_bwd_k, dim3(r.gx, C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, C, D, H, W, Do, Ho, Wo, accumulate);
     return uz::check_launch("avgpool3d_bwd_k");
 }
 // bf16 STORAGE variants: x / y (dy / dx) each fp32 or bf16; W % 4 == 0 (pooling) or H*W % 4 == 0 (depth stage), 16-byte aligned views
 extern "C" int uz_avgpool3d_fwd_b16(const void* x, int C, int CtotX, void* y, int CtotY, int D, int H, int W, int x_b16, int y_b16, void* stream) {
     UZ_REQUIRE(C > 0 && D > 0 && H > 0 && W > 0 && C <= 65535 && D <= 65535, "avgpool3d_fwd_b16: bad sizes");
-    UZ_REQUIRE(W % 4 == 0 && H % 2 == 0 && a16(x) && a16(y), "avgpool3d_fwd_b16: needs W %% 4 == 0, even H and 16-byte aligned views");
+    UZ_REQUIRE(pool_st_ok(H, W, uz::align_of(x), uz::align_of(y)), "avgpool3d_fwd_b16: needs W %% 4 == 0, even H and 16-byte aligned views");
     const int Do = (D + 1) / 2, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    hipLaunchKernelGGL(avgpool3d_fwd_st, dim3(gx(Ho * W / 4), C, Do), dim3(256), 0, uz::S(stream), static_cast<const float*>(x), CtotX, static_cast<float*>(y), CtotY,
+    hipLaunchKernelGGL(avgpool3d_fwd_st, dim3(pool_fwd_st_route(H, W).gx, C, Do), dim3(256), 0, uz::S(stream), static_cast<const float*>(x), CtotX, static_cast<float*>(y), CtotY,
                        C, D, H, W, Do, Ho, Wo, x_b16, y_b16);
     return uz::check_launch("avgpool3d_fwd_st");
 }
 extern "C" int uz_avgpool3d_bwd_b16(const void* dy, int C, int CtotDy, void* dx, int CtotDx, int D, int H, int W, int accumulate, int dy_b16, int dx_b16, void* stream) {
     UZ_REQUIRE(C > 0 && D > 0 && H > 0 && W > 0 && C <= 65535 && D <= 65535, "avgpool3d_bwd_b16: bad sizes");
-    UZ_REQUIRE(W % 4 == 0 && H % 2 == 0 && a16(dx) && a16(dy), "avgpool3d_bwd_b16: needs W %% 4 == 0, even H and 16-byte aligned views");
+    UZ_REQUIRE(pool_st_ok(H, W, uz::align_of(dy), uz::align_of(dx)), "avgpool3d_bwd_b16: needs W %% 4 == 0, even H and 16-byte aligned views");
     const int Do = (D + 1) / 2, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    hipLaunchKernelGGL(avgpool3d_bwd_st, dim3(gx(H * W / 4), C, D), dim3(256), 0, uz::S(stream), static_cast<const float*>(dy), CtotDy, static_cast<float*>(dx), CtotDx,
+    hipLaunchKernelGGL(avgpool3d_bwd_st, dim3(pool_bwd_st_route(H, W).gx, C, D), dim3(256), 0, uz::S(stream), static_cast<const float*>(dy), CtotDy, static_cast<float*>(dx), CtotDx,
                        C, D, H, W, Do, Ho, Wo, accumulate, dy_b16, dx_b16);
     return uz::check_launch("avgpool3d_bwd_st");
 }
 extern "C" int uz_depth_lerp2x_fwd_b16(const void* x, int C, int CtotX, void* y, int CtotY, int D, int H, int W, int x_b16, int y_b16, void* stream) {
     UZ_REQUIRE(C > 0 && D > 0 && H > 0 && W > 0 && C <= 65535 && 2 * D <= 65535, "depth_lerp2x_fwd_b16: bad sizes");
-    UZ_REQUIRE((H * W) % 4 == 0 && a16(x) && a16(y), "depth_lerp2x_fwd_b16: needs H*W %% 4 == 0 and 16-byte aligned views");
-    hipLaunchKernelGGL(depth_lerp_fwd_st, dim3(gx(H * W / 4), C, 2 * D), dim3(256), 0, uz::S(stream), static_cast<const float*>(x), CtotX, static_cast<float*>(y), CtotY, C, D, H * W, x_b16, y_b16);
+    UZ_REQUIRE(lerp_st_ok(H * W, uz::align_of(x), uz::align_of(y)), "depth_lerp2x_fwd_b16: needs H*W %% 4 == 0 and 16-byte aligned views");
+    hipLaunchKernelGGL(depth_lerp_fwd_st, dim3(lerp_st_route(H * W).gx, C, 2 * D), dim3(256), 0, uz::S(stream), static_cast<const float*>(x), CtotX, static_cast<float*>(y), CtotY, C, D, H * W, x_b16, y_b16);
     return uz::check_launch("depth_lerp_fwd_st");
 }
 extern "C" int uz_depth_lerp2x_bwd_b16(const void* dy, int C, int CtotDy, void* dx, int CtotDx, int D, int H, int W, int accumulate, int dy_b16, int dx_b16, void* stream) {
     UZ_REQUIRE(C > 0 && D > 0 && H > 0 && W > 0 && C <= 65535 && D <= 65535, "depth_lerp2x_bwd_b16: bad sizes");
-    UZ_REQUIRE((H * W) % 4 == 0 && a16(dx) && a16(dy), "depth_lerp2x_bwd_b16: needs H*W %% 4 == 0 and 16-byte aligned views");
-    hipLaunchKernelGGL(depth_lerp_bwd_st, dim3(gx(H * W / 4), C, D), dim3(256), 0, uz::S(stream), static_cast<const float*>(dy), CtotDy, static_cast<float*>(dx), CtotDx, C, D, H * W, accumulate, dy_b16, dx_b16);
+    UZ_REQUIRE(lerp_st_ok(H * W, uz::align_of(dy), uz::align_of(dx)), "depth_lerp2x_bwd_b16: needs H*W %% 4 == 0 and 16-byte aligned views");
+    hipLaunchKernelGGL(depth_lerp_bwd_st, dim3(lerp_st_route(H * W).gx, C, D), dim3(256), 0, uz::S(stream), static_cast<const float*>(dy), CtotDy, static_cast<float*>(dx), CtotDx, C, D, H * W, accumulate, dy_b16, dx_b16);
     return uz::check_launch("depth_lerp_bwd_st");
 }
 extern "C" int uz_depth_lerp2x_fwd(const float* x, int C, int CtotX, float* y, int CtotY, int D, int H, int W, void* stream) {
     UZ_REQUIRE(C > 0 && D > 0 && H > 0 && W > 0 && C <= 65535 && 2 * D <= 65535, "depth_lerp2x_fwd: bad sizes");
-    if ((H * W) % 4 == 0 && a16(x) && a16(y))
-        hipLaunchKernelGGL(depth_lerp_fwd_v4, dim3(gx(H * W / 4), C, 2 * D), dim3(256), 0, uz::S(stream), x, CtotX, y, CtotY, C, D, H * W);
+    const VolRoute r = lerp_route(H * W, uz::align_of(x), uz::align_of(y));
+    if (r.kernel == VK_VEC)
+        hipLaunchKernelGGL(depth_lerp_fwd_v4, dim3(r.gx, C, 2 * D), dim3(256), 0, uz::S(stream), x, CtotX, y, CtotY, C, D, H * W);
     else
-        hipLaunchKernelGGL(depth_lerp_fwd_k, dim3(gx(H * W), C, 2 * D), dim3(256), 0, uz::S(stream), x, CtotX, y, CtotY, C, D, H * W);
+        hipLaunchKernelGGL(depth_lerp_fwd_k, dim3(r.gx, C, 2 * D), dim3(256), 0, uz::S(stream), x, CtotX, y, CtotY, C, D, H * W);
     return uz::check_launch("depth_lerp_fwd_k");
 }
 extern "C" int uz_depth_lerp2x_bwd(const float* dy, int C, int CtotDy, float* dx, int CtotDx, int D, int H, int W, int accumulate, void* stream) {
     UZ_REQUIRE(C > 0 && D > 0 && H > 0 && W > 0 && C <= 65535 && D <= 65535, "depth_lerp2x_bwd: bad sizes");
-    if ((H * W) % 4 == 0 && a16(dx) && a16(dy))
-        hipLaunchKernelGGL(depth_lerp_bwd_v4, dim3(gx(H * W / 4), C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, C, D, H * W, accumulate);
+    const VolRoute r = lerp_route(H * W, uz::align_of(dy), uz::align_of(dx));
+    if (r.kernel == VK_VEC)
+        hipLaunchKernelGGL(depth_lerp_bwd_v4, dim3(r.gx, C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, C, D, H * W, accumulate);
     else
-        hipLaunchKernelGGL(depth_lerp_bwd_k, dim3(gx(H * W), C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, C, D, H * W, accumulate);
+        hipLaunchKernelGGL(depth_lerp_bwd_k, dim3(r.gx, C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, C, D, H * W, accumulate);
     return uz::check_launch("depth_lerp_bwd_k");
 }
 extern "C" int uz_nearest3d_fwd(const float* x, int C, int CtotX, float* y, int CtotY, int D, int H, int W, int f, int fz, void* stream) {
     UZ_REQUIRE(C > 0 && D > 0 && f >= 1 && fz >= 1 && C <= 65535 && D * fz <= 65535, "nearest3d_fwd: bad sizes");
-    hipLaunchKernelGGL(nearest3d_fwd_k, dim3(gx(H * f * W * f), C, D * fz), dim3(256), 0, uz::S(stream), x, CtotX, y, CtotY, H, W, f, fz);
+    hipLaunchKernelGGL(nearest3d_fwd_k, dim3(nearest_fwd_route(H, W, f).gx, C, D * fz), dim3(256), 0, uz::S(stream), x, CtotX, y, CtotY, H, W, f, fz);
     return uz::check_launch("nearest3d_fwd_k");
 }
 extern "C" int uz_nearest3d_bwd(const float* dy, int C, int CtotDy, float* dx, int CtotDx, int D, int H, int W, int f, int fz, int accumulate, void* stream) {
     UZ_REQUIRE(C > 0 && D > 0 && f >= 1 && fz >= 1 && C <= 65535 && D <= 65535, "nearest3d_bwd: bad sizes");
-    if (f * f * fz >= 64 && (H * W + 3) / 4 <= 65535)
-        hipLaunchKernelGGL(nearest3d_bwd_wave_k, dim3((H * W + 3) / 4, C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, H, W, f, fz, accumulate);
+    const VolRoute r = nearest_bwd_route(H, W, f, fz);
+    if (r.kernel == VK_WAVE)
+        hipLaunchKernelGGL(nearest3d_bwd_wave_k, dim3(r.gx, C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, H, W, f, fz, accumulate);
     else
-        hipLaunchKernelGGL(nearest3d_bwd_k, dim3(gx(H * W), C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, H, W, f, fz, accumulate);
+        hipLaunchKernelGGL(nearest3d_bwd_k, dim3(r.gx, C, D), dim3(256), 0, uz::S(stream), dy, CtotDy, dx, CtotDx, H, W, f, fz, accumulate);
     return uz::check_launch("nearest3d_bwd_k");
 }
 
@@ -400,14 +440,36 @@ __global__ __launch_bounds__(256) void cvt_b16_f32_k(const unsigned short* __res
 extern "C" int uz_cvt_f32_to_b16(const float* src, void* dst, size_t n, void* stream) {
     UZ_REQUIRE(src && dst, "cvt_f32_to_b16: null argument");
     if (n == 0) return 0;
-    size_t g = (n + 255) / 256; if (g > 65535) g = 65535;
-    hipLaunchKernelGGL(cvt_f32_b16_k, dim3((unsigned)g), dim3(256), 0, uz::S(stream), src, static_cast<unsigned short*>(dst), n);
+    hipLaunchKernelGGL(cvt_f32_b16_k, dim3((unsigned)cvt_grid(n)), dim3(256), 0, uz::S(stream), src, static_cast<unsigned short*>(dst), n);
     return uz::check_launch("cvt_f32_b16_k");
 }
 extern "C" int uz_cvt_b16_to_f32(const void* src, float* dst, size_t n, void* stream) {
     UZ_REQUIRE(src && dst, "cvt_b16_to_f32: null argument");
     if (n == 0) return 0;
-    size_t g = (n + 255) / 256; if (g > 65535) g = 65535;
-    hipLaunchKernelGGL(cvt_b16_f32_k, dim3((unsigned)g), dim3(256), 0, uz::S(stream), static_cast<const unsigned short*>(src), dst, n);
+    hipLaunchKernelGGL(cvt_b16_f32_k, dim3((unsigned)cvt_grid(n)), dim3(256), 0, uz::S(stream), static_cast<const unsigned short*>(src), dst, n);
     return uz::check_launch("cvt_b16_f32_k");
+}
+
+// What a volume call launches (include/uz_api.h): the answers of the route functions the entry points above dispatch through.
+extern "C" int uz_vol_route(int op, int C, int D, int H, int W, int f, int fz, int align_src, int align_dst, int* out2) {
+    UZ_REQUIRE(out2 && op >= 0 && op <= 11, "vol_route: op 0 .. 11 and two ints to answer into");
+    UZ_REQUIRE(C > 0 && D > 0 && H > 0 && W > 0, "vol_route: empty tensor");
+    VolRoute r;
+    switch (op) {
+        case 0: r = pool_fwd_route(H, W, align_src, align_dst); break;
+        case 1: r = pool_bwd_route(H, W, align_src, align_dst); break;
+        case 2: case 3: r = lerp_route(H * W, align_src, align_dst); break;
+        case 4: UZ_REQUIRE(f >= 1 && fz >= 1, "vol_route: factors"); r = nearest_fwd_route(H, W, f); break;
+        case 5: UZ_REQUIRE(f >= 1 && fz >= 1, "vol_route: factors"); r = nearest_bwd_route(H, W, f, fz); break;
+        case 6: case 7:
+            UZ_REQUIRE(pool_st_ok(H, W, align_src, align_dst), "vol_route: bf16-storage pooling needs W %% 4 == 0, even H and 16-byte aligned views");
+            r = op == 6 ? pool_fwd_st_route(H, W) : pool_bwd_st_route(H, W); break;
+        case 8: case 9:
+            UZ_REQUIRE(lerp_st_ok(H * W, align_src, align_dst), "vol_route: bf16-storage depth stage needs H*W %% 4 == 0 and 16-byte aligned views");
+            r = lerp_st_route(H * W); break;
+        case 10: r = {VK_SCALAR, w3d_grid(C, D)}; break;                                            /* C = Cout, D = Cin */
+        default: r = {VK_SCALAR, (int)cvt_grid((size_t)C * D * H * W)}; break;                        /* n = C D H W contiguous elements */
+    }
+    out2[0] = r.kernel; out2[1] = r.gx;
+    return 0;
 }
