@@ -401,6 +401,22 @@ int uz_sum_terms(const float* terms, int n, float* total, void* stream);
 int uz_accumulate_softmax_argmax(const float* const* s_ptrs, int L, int K, int N, int H, int W,
                                  float* acc, float* soft, uint8_t* label, void* stream);
 
+/* ---------------------------------------------------------------- mask-free inference (PHISeg.predict; csrc/predict.hip)
+ * patch.repeat(S, 1, 1, 1) of a channel slice: y[s*B + b, c] = x[b, c] for s < S.  x / y are C-channel slices of buffers with
+ * CtotX / CtotY channels (the convention of uz_nearest_fwd); x holds B images, y S*B.  Every source element is read once and
+ * written S times; 16-byte accesses where H*W % 4 == 0 and both slices start 16-byte aligned, 4-byte ones otherwise.          */
+int uz_batch_repeat_fwd(const float* x, int C, int CtotX, float* y, int CtotY,
+                        int B, int S, int H, int W, void* stream);
+/* S samples of B images in one pass over the L level logits (S*B,K,H,W), row s*B + b = sample s of image b (s_ptrs: L device
+ * pointers held in DEVICE memory; the inputs are not written):  acc = sum_l s_l in fp32, in the level order of
+ * uz_accumulate_softmax_argmax; soft = softmax_K(acc); labels = argmax_K(acc); mean_soft[b] = (sum_s soft[s*B + b]) / S, added
+ * in the order s = 0 .. S-1 by the one thread that owns the pixel (bit-repeatable); mean_label = argmax_K(mean_soft);
+ * entropy = -sum_k p_k ln p_k of p = mean_soft (a term with p_k = 0 is 0).  Softmax, mean and entropy are evaluated in fp64 and
+ * rounded to fp32 once, when they are stored; mean_label is decided on the unrounded means.  Both argmax take the first maximum,
+ * as np.argmax does.  1 <= K <= 8.  soft (S*B,K,H,W), labels (S*B,H,W), mean_label (B,H,W) and entropy (B,H,W) are nullable.   */
+int uz_sample_stats(const float* const* s_ptrs, int L, int K, int B, int S, int H, int W,
+                    float* soft, uint8_t* labels, float* mean_soft, uint8_t* mean_label, float* entropy, void* stream);
+
 /* ---------------------------------------------------------------- validation metrics (train_model.py:186-230)
  * out[i][j][0..2] = |a_i==label & b_j==label|, |a_i==label|, |b_j==label| over HW pixels (int32, exact): the integer core of
  * utils.generalised_energy_distance (utils.py:148-200; IoU = medpy.metric.jc, MedPy 0.4.0) and of the per-label Dice

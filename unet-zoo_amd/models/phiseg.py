@@ -11,6 +11,7 @@ the standard filter list) and the same quirks:
     ``grad is None`` (phiseg.py:161-164,198-199);
   * ``accumulate_output`` sums the levels in place into ``output_list[-1]`` (phiseg.py:428-434).
 The forward/backward arithmetic itself runs in libuz_hip.so (see _plan.py for the op tape).
+Beyond the reference: predict(patch, n_samples) - samples, mean probabilities and an uncertainty map without a label mask.
 """
 import ctypes as C
 
@@ -90,6 +91,17 @@ def phiseg_spec(input_channels, num_classes, num_filters, reversible=False):
             + _encoder_spec("prior", input_channels, nf, reversible))
 
 
+class Prediction:
+    """What PHISeg.predict returns for S samples of B images: labels (S, B, H, W) uint8, mean_soft (B, K, H, W) - the mean class
+    probabilities over the samples -, mean_label (B, H, W) uint8 = argmax of mean_soft, entropy (B, H, W) of mean_soft (natural log),
+    levels - the five level logits (S * B, K, H, W) as views of the plan's buffers, valid until the next predict() of that shape -
+    and soft (S, B, K, H, W), the per-sample probabilities, or None unless asked for."""
+    __slots__ = ("labels", "mean_soft", "mean_label", "entropy", "levels", "soft")
+
+    def __init__(self, labels, mean_soft, mean_label, entropy, levels, soft=None):
+        self.labels, self.mean_soft, self.mean_label, self.entropy, self.levels, self.soft = labels, mean_soft, mean_label, entropy, levels, soft
+
+
 class PHISeg(NativeModel):
     wgrad_workgroups = 128                     # NativeModel.wgrad_workgroups: 256 -> 1 907, 192 -> 1 946, 128 -> 1 970, 96 -> 1 916, 64 -> 1 778 images/s (one box)
     default_lanes_by_mode = {"lanes": 3}     # host-issued lane replay: 2 lanes 17.7 ms, 3: 16.3, 4: 16.2 (one box, round 5)
@@ -117,6 +129,12 @@ class PHISeg(NativeModel):
 
     # ------------------------------------------------------------------ plan construction
     def _encoder(self, plan, root, x, eps, z_override, want_z):
+        skips, pre = self._contracting(plan, root, x)
+        return self._latent_path(plan, root, skips, pre, eps, z_override, want_z)
+
+    def _contracting(self, plan, root, x):
+        """The seven Conv2D stacks of an encoder (phiseg.py:191-194).  Returns the concat buffers of levels 2 .. 5, their skip slice
+        written, and the deepest feature map: what the latent path reads."""
         nf = self.num_filters
         skips = {}
         for i in range(RES_LEVELS):
@@ -134,8 +152,12 @@ class PHISeg(NativeModel):
                 continue
             for j in range(3):
                 x = conv_unit(plan, x, f"{root}.contracting_path.{i}.layers.{base + j}", out=out if j == 2 else None)
+        return skips, x
+
+    def _latent_path(self, plan, root, skips, pre, eps, z_override, want_z):
+        """The five SampleZBlocks and the up path between them (phiseg.py:196-202), deepest level first."""
+        nf = self.num_filters
         lats, zs = [], []
-        pre = x
         for k in range(LAT_LEVELS):
             if k != 0:
                 cat = skips[RES_LEVELS - 1 - k]
@@ -238,6 +260,36 @@ class PHISeg(NativeModel):
         plan.io = io
         return plan
 
+    def _build_predict(self, N, H, W, part):
+        """The two plans of predict(), both with eval-mode BatchNorm and no loss or backward tape.  part = "trunk": patch -> the
+        prior's contracting path at the batch of the images (nothing in it depends on the noise).  part = "draw": the prior's latent
+        path and the likelihood at the batch of images x samples; the skip slices of its concat buffers and the deepest feature map
+        are plan inputs that predict() fills from the trunk plan (no producer of this plan keeps a magnitude bound for them, so
+        Plan.amax_in answers None for the mixed buffers and the split convolutions measure those tensors themselves).
+        io["feats"] lists the five hand-over views, levels 2 .. 5 and the deepest, in the same order in both plans."""
+        if H % 64 or W % 64:
+            raise ValueError("PHISeg needs H and W divisible by 64 (7 resolution levels)")
+        self._H = H
+        nf, root = self.num_filters, "prior"
+        plan = self._new_plan(N, False)
+        plan.bn_prefixes_nbt = []
+        io = {}
+        if part == "trunk":
+            io["patch"] = plan.buf("patch", self.input_channels, H, W, requires_grad=False)
+            skips, pre = self._contracting(plan, root, io["patch"])
+        else:
+            shapes = [(2, H >> (RES_LEVELS - 1 - k), W >> (RES_LEVELS - 1 - k)) for k in range(LAT_LEVELS)]
+            io["eps"] = [plan.buf(f"eps{k}", *shapes[k], requires_grad=False) for k in range(LAT_LEVELS)]
+            skips = {i: plan.buf(f"{root}.cat{i}", 2 * nf[0] + nf[i], H >> i, W >> i, requires_grad=False) for i in range(2, 6)}
+            pre = plan.buf(f"{root}.deepest", nf[RES_LEVELS - 1], H >> (RES_LEVELS - 1), W >> (RES_LEVELS - 1), requires_grad=False)
+            io["prior"], io["prior_z"] = self._latent_path(plan, root, skips, pre, io["eps"], None, True)
+            io["s"] = self._likelihood(plan, io["prior_z"])
+        io["feats"] = [skips[i].slice(2 * nf[0], nf[i]) for i in range(2, 6)] + [pre]
+        plan.total = plan.vec("total", 1)
+        plan.finalize(want_backward=False)
+        plan.io = io
+        return plan
+
     # ------------------------------------------------------------------ reference API
     def forward(self, patch, mask, training=True, eps=None):
         """PHISeg.forward (phiseg.py:414-426).  `eps` (optional, list of 10 tensors: 5 posterior draws
@@ -275,6 +327,67 @@ class PHISeg(NativeModel):
         self.prior_latent_space = [T(io["prior_z"][k]) for k in order]
         self.s_out_list = [T(v) for v in io["s"]]
         return self.s_out_list
+
+    def predict(self, patch, n_samples=1, eps=None, return_soft=False):
+        """Segment `patch` (B, C, H, W) without a label mask: n_samples draws from the prior, from ONE pass of its contracting path.
+        In eval mode BatchNorm is a per-channel affine map of its input, so the contracting path gives every copy of an image in
+        patch.repeat(n_samples, 1, 1, 1) the same feature maps: it runs once, at batch B, and its five outputs are repeated into the
+        plan that draws (uz_batch_repeat_fwd) - the rows of that plan are ordered s * B + b like the repeated patch.  `eps`
+        (optional, 5 tensors, deepest level first, each (n_samples * B, 2, h, w): the prior half of forward()'s eps) injects the
+        noise; default draws it on the device.  Returns a Prediction; also sets prior_mu / prior_sigma / prior_latent_space for
+        the n_samples * B rows, as forward() does."""
+        self._require_gpu()
+        if self.training:
+            raise RuntimeError("predict() needs eval mode: with batch statistics the contracting path of one image is not shared by its samples")
+        if self.reversible:
+            raise NotImplementedError("predict() is not built for the reversible variant")
+        B, _, H, W = patch.shape
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError("predict() needs n_samples >= 1")
+        if H % 64 or W % 64:
+            raise ValueError("PHISeg needs H and W divisible by 64 (7 resolution levels)")
+        trunk = self._plan(("trunk", B, H, W), lambda: self._build_predict(B, H, W, "trunk"))
+        draw = self._plan(("draw", B * S, H, W), lambda: self._build_predict(B * S, H, W, "draw"))
+        L, st = _ffi.lib(), C.c_void_p(self._stream())
+        trunk.tensor(trunk.io["patch"]).copy_(patch)
+        self._run(trunk, "fwd")
+        for src, dst in zip(trunk.io["feats"], draw.io["feats"]):
+            _ffi.check(L.uz_batch_repeat_fwd(trunk._resolve(src), src.C, src.Ctot, draw._resolve(dst), dst.Ctot, B, S, src.H, src.W, st),
+                       "batch_repeat_fwd")
+        io = draw.io
+        if eps is None:
+            flat = draw.__dict__.get("_eps_span", False)
+            if flat is False:
+                flat = draw._eps_span = draw.span(io["eps"])
+            if flat is not None:
+                self._fill_normal(flat)                       # the five noise buffers are neighbours in the arena: one launch
+            else:
+                for e in io["eps"]:
+                    self._fill_normal(draw.tensor(e))
+        else:
+            if len(eps) != LAT_LEVELS:
+                raise ValueError(f"predict() takes {LAT_LEVELS} eps tensors (deepest level first), got {len(eps)}")
+            for e, src in zip(io["eps"], eps):
+                draw.tensor(e).copy_(src)
+        self._run(draw, "fwd")
+        T = draw.tensor
+        order = [LAT_LEVELS - 1 - lvl for lvl in range(LAT_LEVELS)]        # level -> draw index
+        self.prior_mu = [T(io["prior"][k].mu) for k in order]
+        self.prior_sigma = [T(io["prior"][k].sigma) for k in order]
+        self.prior_latent_space = [T(io["prior_z"][k]) for k in order]
+        levels = [T(v) for v in io["s"]]
+        tab = draw.__dict__.get("_s_tab")
+        if tab is None:
+            tab = draw._s_tab = torch.tensor([t.data_ptr() for t in levels], dtype=torch.int64, device=self.device)
+        K, dev = self.num_classes, self.device
+        out = Prediction(labels=torch.empty(S, B, H, W, dtype=torch.uint8, device=dev), mean_soft=torch.empty(B, K, H, W, device=dev),
+                         mean_label=torch.empty(B, H, W, dtype=torch.uint8, device=dev), entropy=torch.empty(B, H, W, device=dev),
+                         levels=levels, soft=torch.empty(S, B, K, H, W, device=dev) if return_soft else None)
+        _ffi.check(L.uz_sample_stats(tab.data_ptr(), len(levels), K, B, S, H, W, out.soft.data_ptr() if return_soft else None,
+                                     out.labels.data_ptr(), out.mean_soft.data_ptr(), out.mean_label.data_ptr(), out.entropy.data_ptr(), st),
+                   "sample_stats")
+        return out
 
     def loss(self, segm):
         return self.elbo(segm)

@@ -305,6 +305,18 @@ class UNetModel:
         return dict(dice=self.avg_dice, foreground_dice=self.foreground_dice, elbo=self.val_elbo, ged=self.avg_ged, ncc=self.avg_ncc)
 
     @torch.no_grad()
+    def predict(self, images, n_samples=1):
+        """Segment unlabelled images: a numpy or torch batch (B, H, W) or (B, C, H, W) -> the net's Prediction (models/phiseg.py) of
+        `n_samples` prior samples per image.  No mask, no loss: validate() and test() keep the reference's loop."""
+        if not hasattr(self.net, "predict"):
+            raise NotImplementedError(f"{type(self.net).__name__} has no mask-free predict()")
+        self.net.eval()
+        patch = torch.as_tensor(images, dtype=torch.float32).to(self.device)
+        if patch.dim() == 3:
+            patch = patch.unsqueeze(1)
+        return self.net.predict(patch.contiguous(), n_samples=n_samples)
+
+    @torch.no_grad()
     def test(self, data, sys_config=None, rounds=10, n_samples=10):
         """UNetModel.test (train_model.py:333-475): load `<experiment>_best_loss.pth`, then `rounds` passes over the
         test split with `n_samples` prior samples per image; GED / NCC arrays are dumped as
