@@ -416,6 +416,26 @@ int uz_batch_repeat_fwd(const float* x, int C, int CtotX, float* y, int CtotY,
  * as np.argmax does.  1 <= K <= 8.  soft (S*B,K,H,W), labels (S*B,H,W), mean_label (B,H,W) and entropy (B,H,W) are nullable.   */
 int uz_sample_stats(const float* const* s_ptrs, int L, int K, int B, int S, int H, int W,
                     float* soft, uint8_t* labels, float* mean_soft, uint8_t* mean_label, float* entropy, void* stream);
+/* Fcomb (probabilistic_unet.py:185-199) in eval mode for S latent draws per image, features read once (ProbabilisticUnet.predict;
+ * csrc/fcomb.hip).
+ *   feat      (B, C of CtotF, H, W), C == 32
+ *   mu, sigma (B, L); eps (S*B, L), row s*B + b
+ *   z         out (S*B, L):  z = mu[b] + sigma[b] * eps[s*B + b]   (one fused multiply-add)
+ *   params    table of pointers in DEVICE memory: per unit u < n_units {w, bias, gamma, beta, running_mean, running_var}, then
+ *             {w_last, bias_last}; w of unit 0 is (32, 32 + L) - its columns 32 .. address z -, of the others (32, 32), w_last (K, 32).
+ *             The tensors behind the table are read through the constant address space: nothing may write them while the kernel runs.
+ *   logits    out (S*B, K, H, W), row s*B + b
+ * Every unit is conv 1x1 -> (y - running_mean) * (1 / sqrtf(running_var + bn_eps)) * gamma + beta -> ReLU, the head a bare 1x1
+ * convolution; fp32 multiply-adds in a fixed order in every UZ_CONV_MATH mode, no atomics.  C == 32, 1 <= L, K, n_units <= 8;
+ * anything else is refused before a launch.                                                                                       */
+int uz_fcomb_sample_fwd(const float* feat, int C, int CtotF, const float* mu, const float* sigma, const float* eps,
+                        const float* const* params, int n_units, float bn_eps, int L, int K, int B, int S, int H, int W,
+                        float* z, float* logits, void* stream);
+/* What uz_fcomb_sample_fwd launches for these sizes, from the predicate it launches with (answered on the host).  out5 receives
+ * [0] pixels per workgroup (256 or 512: one or two per thread), [1] samples per workgroup, [2] [3] [4] the grid: pixel blocks,
+ * images, sample groups (the last group may be ragged).  Honours UZ_FCOMB_PX (1 | 2) as the launch does.  0, or -1 for sizes
+ * uz_fcomb_sample_fwd refuses.                                                                                                    */
+int uz_fcomb_sample_route(int L, int K, int n_units, int B, int S, int H, int W, int* out5);
 
 /* ---------------------------------------------------------------- validation metrics (train_model.py:186-230)
  * out[i][j][0..2] = |a_i==label & b_j==label|, |a_i==label|, |b_j==label| over HW pixels (int32, exact): the integer core of

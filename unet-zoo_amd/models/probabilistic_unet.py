@@ -14,15 +14,22 @@ Structure restated for the op tape:
     fcomb.layers parameters (:365-370).
   * ``last_conv`` (:244,255) is computed in forward but never reaches the loss: its parameters keep
     ``grad is None`` exactly as in the reference.
+
+Beyond the reference: predict(patch, n_samples) - S distinct prior samples, their mean probabilities and an uncertainty map from one
+pass of U-Net and prior encoder and one Fcomb launch for all samples (csrc/fcomb.hip).
 """
+import ctypes as C
 import math
 
 import torch
 import torch.nn as nn
 from torch.distributions import Independent, Normal
 
+from .. import _ffi
 from .._engine import NativeModel, conv_unit
 from .._modtree import conv_unit_spec, plain_conv_spec
+from .._plan import BN_EPS
+from .phiseg import Prediction
 from .unet import unet_spec, init_unet_weights, build_unet_graph
 
 
@@ -204,6 +211,71 @@ class ProbabilisticUnet(NativeModel):
         z_prior = self.prior_latent_space.rsample() if not testing else self.prior_latent_space.sample()
         self.z_prior_sample = z_prior
         return self._decode(z_prior)
+
+    def _fcomb_param_refs(self):
+        """The operand order of uz_fcomb_sample_fwd's pointer table."""
+        refs = []
+        for u in range(self.no_convs_fcomb - 1):
+            p = f"fcomb.layers.{u}.convolution"
+            refs += [("param", p + ".0.weight", 0), ("param", p + ".0.bias", 0), ("param", p + ".1.weight", 0), ("param", p + ".1.bias", 0),
+                     ("buffer", p + ".1.running_mean"), ("buffer", p + ".1.running_var")]
+        return refs + [("param", "fcomb.last_layer.weight", 0), ("param", "fcomb.last_layer.bias", 0)]
+
+    def _fcomb_sample(self, plan, S):
+        """The one uz_fcomb_sample_fwd launch of predict(): features, mu and sigma of the eval plan `plan` (forward has run) and the
+        noise in the plan's predict buffers for S samples -> z and logits in those buffers."""
+        io, bufs = plan.io, plan._predict_bufs[S]
+        feat, mu, sigma = io["fcat"].slice(0, self.num_filters[0]), io["p_mu"], io["p"].sigma
+        if any(v.buf.b16 or v.buf.packed for v in (feat, mu, sigma)):
+            raise _ffi.UzError("predict(): the Fcomb input, mu or sigma is not kept as fp32 in this arithmetic mode")
+        tab = plan.__dict__.get("_fcomb_tab")
+        if tab is None:                                # the parameters never move: built once per plan
+            tab = plan._fcomb_tab = torch.tensor([plan._resolve(r) for r in self._fcomb_param_refs()], dtype=torch.int64, device=self.device)
+        _ffi.check(_ffi.lib().uz_fcomb_sample_fwd(plan._resolve(feat), feat.C, feat.Ctot, plan._resolve(mu), plan._resolve(sigma),
+                                                  bufs["eps"].data_ptr(), tab.data_ptr(), self.no_convs_fcomb - 1, BN_EPS, self.latent_dim,
+                                                  self.num_classes, feat.N, S, feat.H, feat.W, bufs["z"].data_ptr(), bufs["logits"].data_ptr(),
+                                                  C.c_void_p(self._stream())), "fcomb_sample_fwd")
+
+    def predict(self, patch, n_samples=1, eps=None, return_soft=False):
+        """Segment `patch` (B, C, H, W) without a label mask: n_samples draws from the prior on ONE pass of the U-Net and the prior
+        encoder - the eval plan of forward(patch, None).  Fcomb is a per-pixel MLP whose input differs between the samples of an
+        image only by the tiled z: one launch (uz_fcomb_sample_fwd) reads the 32 feature planes once and writes the logits of all
+        n_samples * B rows (row s * B + b), one more (uz_sample_stats) turns them into labels, mean probabilities and entropy.
+        `eps` (optional, (n_samples * B, latent_dim)) injects the noise: z = mu + sigma * eps; default draws it on the device.
+        Returns the Prediction of models/phiseg.py with one level; sets prior_latent_space and unet_features as forward() does
+        and z_prior_sample to the (n_samples * B, latent_dim) draws.  The tensors are buffers kept with the plan: valid until the
+        next predict() of that shape and sample count."""
+        if self.training:
+            raise RuntimeError("predict() needs eval mode: with batch statistics Fcomb's BatchNorm is no fixed map and the features of one image are not shared by its samples")
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError("predict() needs n_samples >= 1")
+        if self.reversible:
+            raise NotImplementedError("predict() is not built for the reversible variant")
+        self.forward(patch, None)
+        plan, dev = self._cur, self.device
+        B, _, H, W = patch.shape
+        L, K = self.latent_dim, self.num_classes
+        bufs = plan.__dict__.setdefault("_predict_bufs", {}).get(S)
+        if bufs is None:
+            logits = torch.empty(S * B, K, H, W, device=dev)
+            bufs = plan._predict_bufs[S] = dict(eps=torch.empty(S * B, L, device=dev), z=torch.empty(S * B, L, device=dev), logits=logits,
+                                                s_tab=torch.tensor([logits.data_ptr()], dtype=torch.int64, device=dev))
+        if eps is None:
+            self._fill_normal(bufs["eps"])
+        else:
+            if tuple(eps.shape) != (S * B, L):
+                raise ValueError(f"predict() takes eps of shape {(S * B, L)} (row s * B + b), got {tuple(eps.shape)}")
+            bufs["eps"].copy_(eps)
+        out = Prediction(labels=torch.empty(S, B, H, W, dtype=torch.uint8, device=dev), mean_soft=torch.empty(B, K, H, W, device=dev),
+                         mean_label=torch.empty(B, H, W, dtype=torch.uint8, device=dev), entropy=torch.empty(B, H, W, device=dev),
+                         levels=[bufs["logits"]], soft=torch.empty(S, B, K, H, W, device=dev) if return_soft else None)
+        self._fcomb_sample(plan, S)
+        _ffi.check(_ffi.lib().uz_sample_stats(bufs["s_tab"].data_ptr(), 1, K, B, S, H, W, out.soft.data_ptr() if return_soft else None,
+                                              out.labels.data_ptr(), out.mean_soft.data_ptr(), out.mean_label.data_ptr(), out.entropy.data_ptr(),
+                                              C.c_void_p(self._stream())), "sample_stats")
+        self.z_prior_sample = bufs["z"]
+        return out
 
     def reconstruct(self, use_posterior_mean=False, calculate_posterior=False, z_posterior=None):
         """:272-283"""
