@@ -54,6 +54,11 @@ class NativeModel(nn.Module):
         self._dp_group = None
         self._use_graphs = False
         self._graphs = {}
+        self._plans_mode = None             # convolution math mode the cached plans were built under (_plan)
+        self._step_snapshot = None          # snapshot_step()
+        self._tune_rec = None               # per-op timings while tune_schedule() runs (_run fills it)
+        self._warned_hwq = False            # the hardware-queue warning of _new_plan was given
+        self._rng_state_t = None            # {seed, offset} of the latent-noise stream on the device (_rng_state)
 
     # ------------------------------------------------------------------ storage
     def _init_storage(self, spec, device=None):
@@ -120,7 +125,7 @@ class NativeModel(nn.Module):
     def restore_step(self):
         """Undo what the forward pass since snapshot_step() did to the BatchNorm buffers / counters and rewind the noise stream,
         so that the repeated step draws the SAME eps and updates the running statistics once."""
-        snap = self.__dict__.get("_step_snapshot")
+        snap = self._step_snapshot
         if snap is None:
             raise RuntimeError("restore_step() without snapshot_step()")
         self._ptab.bflat.copy_(snap[0])
@@ -134,11 +139,11 @@ class NativeModel(nn.Module):
     # ------------------------------------------------------------------ plans
     def _plan(self, key, builder):
         mode = _ffi.lib().uz_get_conv_math()
-        if self._plans and self.__dict__.get("_plans_mode", mode) != mode:      # the process switched its convolution math mode
+        if self._plans and self._plans_mode != mode:      # the process switched its convolution math mode
             self._plans.clear()
             self._drop_graphs()
             self._cur = None
-        self.__dict__["_plans_mode"] = mode
+        self._plans_mode = mode
         p = self._plans.get(key)
         if p is None:
             p = builder()
@@ -162,7 +167,7 @@ class NativeModel(nn.Module):
     # chains no longer carry the weight gradients), Probabilistic U-Net 11.33 -> 11.66 ms (three lanes already interleave its
     # chains) - so it is a per-model default.
     decouple_wgrad_px = 0
-    # Planes (N*H*W pixels) up to which a tape's small-plane ops run as phases of persistent "chain" launches (Plan._chain_pass,
+    # Planes (N*H*W pixels) up to which a tape's small-plane ops run as phases of persistent "chain" launches (_chain_plan._chain_pass,
     # csrc/chain.hip; UZ_CHAIN overrides; 8192 = PHiSeg's 16 x 16 ... 2 x 2 levels at batch 32).  OFF by default: built, parity-green
     # and MEASURED SLOWER than the per-op tape on MI355X (round 6: PHiSeg step 15.7 ms per-op; 17.7 ms with the forward chain, 22.3 ms
     # with forward + backward chains - profiles/NOTES_r6.md says where the time goes).
@@ -207,9 +212,9 @@ class NativeModel(nn.Module):
             hwq = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
         except ValueError:
             hwq = 4
-        if self.replay_mode == "lanes" and plan.n_lanes > 1 and hwq < plan.n_lanes and not self.__dict__.get("_warned_hwq"):
+        if self.replay_mode == "lanes" and plan.n_lanes > 1 and hwq < plan.n_lanes and not self._warned_hwq:
             import warnings
-            self.__dict__["_warned_hwq"] = True
+            self._warned_hwq = True
             warnings.warn(f"GPU_MAX_HW_QUEUES={hwq} < {plan.n_lanes} dependency lanes: lanes share hardware queues and serialise "
                           "(measured: 2 queues 1 741 images/s against 2 035 with 3, PHiSeg)", RuntimeWarning)
         return plan
@@ -269,7 +274,7 @@ class NativeModel(nn.Module):
         if self.replay_mode == "lanes" and plan.n_lanes > 1 and which in plan.scheds:
             # the tape's DAG issued by the host on one stream per lane, one event per cross-lane edge (uz_run_tape_lanes)
             arr, n = plan.tapes[which]
-            rec = self.__dict__.get("_tune_rec")
+            rec = self._tune_rec
             armed = False
             if n and rec is not None:                      # tune_schedule(): one timing event behind every op of this call
                 plan.L.uz_lane_trace(1, n, None, 0)
@@ -290,7 +295,7 @@ class NativeModel(nn.Module):
         key = (id(plan), which)
         g = self._graphs.get(key)
         if g is None:
-            warm = plan.__dict__.setdefault("_warm", set())
+            warm = plan._warm
             if which not in warm:          # first call: eager (also sets kernel attributes)
                 warm.add(which)
                 plan.run(which, self._stream())
@@ -339,12 +344,12 @@ class NativeModel(nn.Module):
                 plan.reschedule(which)
         hist, best, first = {}, {}, {}
         for r in range(rounds + 1):
-            self.__dict__["_tune_rec"] = rec = {}
+            self._tune_rec = rec = {}
             try:
                 for _ in range(samples):
                     step()
             finally:
-                self.__dict__["_tune_rec"] = None
+                self._tune_rec = None
             if r == 0 and not any(plan.n_lanes > 1 for plan, _runs in rec.values()):
                 # single-lane plans (U-Net) have nothing to re-schedule: do not spend (rounds + 1) * samples more steps - with their
                 # data-parallel exchanges - to return "initial" 
@@ -361,7 +366,7 @@ class NativeModel(nn.Module):
                     best[(pid, which)] = (wall, used, plan)
                 if r == rounds:
                     continue
-                cmodel = Plan._op_cost_beside if os.environ.get("UZ_SCHED_COST", plan.__dict__.get("sched_cost", "alone")) == "beside" else Plan._op_cost
+                cmodel = Plan._op_cost_beside if os.environ.get("UZ_SCHED_COST", plan.sched_cost) == "beside" else Plan._op_cost
                 last, dur = {}, [0.0] * len(ops)
                 for e in runs:
                     last.clear()
@@ -443,7 +448,7 @@ class NativeModel(nn.Module):
                 p.grad.add_(g)
 
     def _post_backward(self, plan):
-        if plan.__dict__.get("bn_prefixes_nbt_bwd"):           # reversible blocks re-ran their BatchNorms while recomputing
+        if plan.bn_prefixes_nbt_bwd:           # reversible blocks re-ran their BatchNorms while recomputing
             self._bump_nbt(plan, "bn_prefixes_nbt_bwd")
 
     def zero_grad(self, set_to_none=True):
@@ -456,11 +461,10 @@ class NativeModel(nn.Module):
     def _bump_nbt(self, plan, which="bn_prefixes_nbt"):
         """num_batches_tracked += 1 for every BatchNorm the pass ran (uz_step_counters: one tiny launch of our own, no ATen
         index_add_ in the step)."""
-        idx = plan.__dict__.get("_nbt_idx_" + which)
+        idx = plan._nbt_idx.get(which)
         if idx is None:
-            ks = [self._ptab.nbt_keys.index(k) for k in plan.__dict__.get(which, [])]
-            idx = torch.tensor(ks, dtype=torch.int64, device=self.device)
-            plan.__dict__["_nbt_idx_" + which] = idx
+            ks = [self._ptab.nbt_keys.index(k) for k in getattr(plan, which)]
+            idx = plan._nbt_idx[which] = torch.tensor(ks, dtype=torch.int64, device=self.device)
         if idx.numel():
             _ffi.check(_ffi.lib().uz_step_counters(self._ptab.nbt.data_ptr(), idx.data_ptr(), idx.numel(), None, 0, C.c_void_p(self._stream())),
                        "step_counters")
@@ -469,7 +473,7 @@ class NativeModel(nn.Module):
         """{seed, offset} of the device-side latent-noise stream (uz_randn_fill): seeded from torch's default generator when
         first used, so torch.manual_seed(...) before the first draw makes runs repeatable.  Under data parallelism the rank is
         mixed into the Philox key: ranks that share a torch seed still draw different noise for their different shards."""
-        st = self.__dict__.get("_rng_state_t")
+        st = self._rng_state_t
         if st is None:
             rank = int(os.environ.get("RANK", "0")) if getattr(self, "_dp", None) is not None or int(os.environ.get("WORLD_SIZE", "1")) > 1 else 0
             seed = (torch.initial_seed() ^ (rank << 32) ^ (rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF
@@ -510,5 +514,5 @@ def conv_unit(plan, x, prefix, out=None, relu=True, recompute=False, **kw):
         which = "bn_prefixes_nbt_loss"
     else:
         which = "bn_prefixes_nbt_extra"
-    plan.__dict__.setdefault(which, []).append(prefix + ".convolution.1.num_batches_tracked")
+    getattr(plan, which).append(prefix + ".convolution.1.num_batches_tracked")
     return a

@@ -13,6 +13,11 @@ Design points:
     overwrites, later writers accumulate (no zero-fill passes);
   * branches whose output never reaches the loss are skipped in backward, which reproduces the
     reference's ``grad is None`` parameters.
+
+This module holds the builder proper: the storage classes, the emitters the models call, ``finalize`` with the arena layout,
+the resolution of symbolic operand refs into addresses and the access sets of the ops.  What ``finalize`` runs over the emitted
+tapes lives beside it: ``_passes.py`` (split storage, BatchNorm off-chain, bf16 storage), ``_chain_plan.py`` (the deep-level
+chain, off by default) and ``_sched.py`` (hazard analysis, cost models, the lane scheduler).
 """
 import ctypes as C
 import os
@@ -21,7 +26,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _ffi, _ops
+from . import _ffi, _ops, _sched
 from ._ops import conv_dims
 
 BN_EPS = 1e-3        # reference torchlayers.py:20
@@ -66,6 +71,7 @@ class ParamTable:
         self.gflat = torch.zeros(max(po, 1), dtype=torch.float32, device=device)
         self.bflat = torch.zeros(max(bo, 1), dtype=torch.float32, device=device)
         self.nbt = torch.zeros(max(len(self.nbt_keys), 1), dtype=torch.int64, device=device)
+        self._gviews = {}                   # key -> cached gradient view, filled by gview()
 
     def pview(self, k):
         o = self.poff[k]
@@ -74,7 +80,7 @@ class ParamTable:
     def gview(self, k):
         """View of parameter k's gradient in the flat buffer.  The view OBJECTS are cached (the buffer never moves): a backward pass
         re-attaches ~400 of them and the optimiser compares them by identity - slicing them anew cost 2 ms of host time per step."""
-        cache = self.__dict__.setdefault("_gviews", {})
+        cache = self._gviews
         v = cache.get(k)
         if v is None:
             o = self.poff[k]
@@ -98,8 +104,8 @@ class Buf:
         self.amax, self.amax_cov = None, []      # magnitude-bound slot and the channel ranges whose producers maintain it
         self.alias = None                        # pooled scratch: several differently shaped Bufs share one arena region
         self.relu = None                         # set by Plan.conv_relu: {(c0, C): state} of Conv -> ReLU units writing into this buffer
-        self.packed = False                      # kept in split storage (Plan._split_storage_passes): Plan.tensor() of it is NOT fp32 values
-        self.b16 = False                         # kept in bf16 storage (Plan._b16_pass): 2-byte elements, Plan.tensor() of it is a bfloat16 tensor
+        self.packed = False                      # kept in split storage (_passes._split_storage_passes): Plan.tensor() of it is NOT fp32 values
+        self.b16 = False                         # kept in bf16 storage (_passes._b16_pass): 2-byte elements, Plan.tensor() of it is a bfloat16 tensor
         self.vol = False                         # a volume (Plan.vol): [D + 2][C][H][W]
 
     @property
@@ -190,19 +196,44 @@ class Plan:
         self._packbuf = {}
         self.grad_buckets = []              # [(lo, hi)] float ranges of the flat gradient buffer that get a "final" event (data parallel)
         self.events = []                    # hipEvent_t handles (uz_event_create), one per gradient bucket
-        self._gid = 0                       # scheduling group of the ops being emitted (see _schedule)
+        self._gid = 0                       # scheduling group of the ops being emitted (see _sched.schedule)
         self._gyz = {}                       # zero-bordered dy scratch classes of volume units: (slices, floats per slice) -> floats
         self.n_lanes = max(1, min(int(os.environ.get("UZ_LANES", "2")), 8))
         self.decouple_wgrad_px = 0           # NativeModel.decouple_wgrad_px: planes (N*H*W) up to which weight gradients get a group of their own
         self.decouple_wgrad_prefixes = ()    # NativeModel.decouple_wgrad_prefixes
         self._nclaims = {}                   # backward writers seen per buffer (conv_relu's folded ReLU backward checks it was the last one)
         self._dbias_jobs = []                # folded ReLU backward: bias gradients still to be summed from their partials (one launch at the tape's end)
-        self.chain_px = 0                    # NativeModel.chain_px: planes (N*H*W) up to which a tape's ops run as phases of ONE persistent launch (_chain_pass)
+        self.chain_px = 0                    # NativeModel.chain_px: planes (N*H*W) up to which a tape's ops run as phases of ONE persistent launch (_chain_plan._chain_pass)
         self.chain_wgs = 256                 # workgroups of that launch (forward tape: nothing else runs beside it)
         self.chain_wgs_bwd = 80              # ... of a backward chain (it runs beside the other lanes' device-filling kernels; at most three chains at once)
         self._chains = []                    # per chain op: dict(sub=[...], phases=[...]) -> device tables built on first resolve
         self._chain_imgs = {}                # tape -> {wkey: dict(off, bytes, mc, kc, cin, dgrad)} packed weight images of the chain convolutions
         self._chain_imgbuf = {}
+        self._detached = 0                   # groups of their own handed out so far (_emit(detached=True), _passes._bn_offchain_pass)
+        self._wgrad_jobs = []                # weight-gradient slabs still to be summed (_conv_bwd); finalize() turns them into table launches
+        self._units = []                     # Conv2D units of the forward tape (conv_bn_relu), for _passes._split_storage_passes / _bn_offchain_pass
+        self._vol_units = []                 # backward ops of the volume units sharing a zero-bordered dy scratch (conv_bn_relu), for _passes._b16_pass
+        self._win_of = {}                    # wkey -> the copy a 3x3x3 convolution reads through its depth window (_window_input)
+        self._rev_ctx = None                 # branch of the reversible block being emitted (_rev_block), else None
+        self._vol_depth = None               # depth of the volume a reversible sequence works on (rev_sequence, _rev_block): shapes _pool's scratch
+        self._rev_pool, self._rev_slots = {}, {}   # pooled scratch of the reversible blocks and the arena regions it shares (_pool; laid out by finalize)
+        self.sched_cost = "alone"            # cost model of the lane scheduler (NativeModel._new_plan; UZ_SCHED_COST overrides): "alone" | "beside"
+        self.sched_heavy = "r4"              # its device-filling rule (NativeModel._new_plan; UZ_SCHED_HEAVY overrides): "r4" | "off" | microseconds
+        self.dag = {}                        # id(tape) -> the scheduled DAG, for diagnostics (_schedule)
+        self.round4, self.bn_offchain, self.b16_info = {}, {}, {}   # summaries of _passes._split_storage_passes / _bn_offchain_pass / _b16_pass
+        self.chain_info = {}                 # tape -> summaries of its chains (_chain_plan._chain_pass)
+        # the models' own handles: io (dict of views), total (the loss), bn_prefixes_nbt* (BatchNorm counters a tape bumps: _engine.conv_unit)
+        self.io, self.total = None, None
+        self.bn_prefixes_nbt, self.bn_prefixes_nbt_loss, self.bn_prefixes_nbt_bwd, self.bn_prefixes_nbt_extra = [], [], [], []
+        self._nbt_idx = {}                   # which of those lists -> its counters' indices on the device (NativeModel._bump_nbt)
+        self._warm = set()                   # tapes that had their eager warm-up run before graph capture (NativeModel._run)
+        # filled by finalize(): the loss-scale cell, the bound-slot numbering, the arena and its layout, the pointer tables, the tapes
+        self.loss_scale = self.loss_scale_t = None
+        self._amax_remap = {}
+        self.gy_off, self.scratch_off, self.gyz_off = [], [], []      # per lane
+        self.amax_off = self.arena_floats = self.arena = self.base = None
+        self.ptrtab, self._tab_off = None, []
+        self.tapes, self.scheds, self._program_order = {}, {}, {}     # per tape: (uz_op array, n), uz_sched array, ops in program order
 
     def _newgroup(self):
         self._gid += 1
@@ -287,7 +318,7 @@ class Plan:
         the head of the tape and must not sit in a layer's chain)."""
         gid = self._gid
         if detached:
-            self._detached = getattr(self, "_detached", 0) + 1
+            self._detached += 1
             gid = ("detached", self._detached)
         op = _ops.make(code, p, i, f, n, gid)
         lst.append(op)
@@ -394,7 +425,7 @@ class Plan:
         cin, cout = x.C, gy.C
         if x.nb is not None and ks == 3:                      # volume: see _conv_fwd
             assert isinstance(gy, _ScratchView) and gy.off and db_key is None and wrow0 == 0
-            x, x_orig = self.__dict__.get("_win_of", {}).get(wkey, x), x          # the weight gradient reads the depth window
+            x, x_orig = self._win_of.get(wkey, x), x          # the weight gradient reads the depth window
             ws = self.L.uz_conv_bwd_weight_workspace(3 * cin, cout, x.N, x.H, x.W, 3)
             self.scratch["wgrad"] = max(self.scratch["wgrad"], ws)
             # (a depth-window call - 3 C view channels over a C-channel buffer - writes the Conv3d gradient layout itself:
@@ -402,14 +433,14 @@ class Plan:
             # (slab reductions deferred to the table launch like the 2-D layers': the table row carries the window's C)
             nslab = 0
             if self._tables_ok() and os.environ.get("UZ_WGRAD_TABLE", "1") == "1" and os.environ.get("UZ_WGRAD_TABLE_VOL", "1") == "1" \
-                    and not self.__dict__.get("_in_rev", False) and self.__dict__.get("_rev_ctx") is None:
+                    and self._rev_ctx is None:
                 nslab = self.L.uz_conv_bwd_weight_slabs(3 * cin, cout, x.N, x.H, x.W, 3)
             slabbuf = self.vec(wkey + ":wslabs", nslab * 9 * cout * 3 * cin) if nslab else None
             rec["wgrad"] = self._emit(self.bwd_ops, "UZ_OP_CONV_BWD_WEIGHT",
                        p=[("win", x), gy, self.G(wkey), None, ("scratch", "wgrad"), self.amax_in(x), self.amax_in(gy), None, slabbuf],
                        i=[3 * cin, x.Ctot, cout, gy.Ctot, x.N, x.H, x.W, 3, 0, 0, 0, 1 if nslab else 0, nslab], n=ws)      # nslab: slabs the buffer was sized for
             if nslab:
-                self.__dict__.setdefault("_wgrad_jobs", []).append((slabbuf, wkey, nslab, cout, 3 * cin, 9, cin))
+                self._wgrad_jobs.append((slabbuf, wkey, nslab, cout, 3 * cin, 9, cin))
             x = x_orig
             if x.buf.requires_grad:
                 acc = self._claim(x)
@@ -436,7 +467,7 @@ class Plan:
             # the slabs of every layer (UZ_OP_WGRAD_REDUCE_TABLE) - PHiSeg: 106 + 27 small reduction launches less per step
             nslab = 0
             if ks == 3 and db_key is None and wrow0 == 0 and self._tables_ok() and os.environ.get("UZ_WGRAD_TABLE", "1") == "1" \
-                    and not self.__dict__.get("_in_rev", False) and self.__dict__.get("_rev_ctx") is None:
+                    and self._rev_ctx is None:
                 nslab = self.L.uz_conv_bwd_weight_slabs(cin, cout, x.N, x.H, x.W, ks)
             slabbuf = self.vec(wkey + ":wslabs", nslab * ks * ks * cout * cin) if nslab else None
             rec["wgrad"] = self._emit(self.bwd_ops, "UZ_OP_CONV_BWD_WEIGHT",
@@ -444,7 +475,7 @@ class Plan:
                                          self.amax_in(x), self.amax_in(gy), None, slabbuf],
                                       i=[cin, x.Ctot, cout, gy.Ctot, x.N, x.H, x.W, ks, 0, 0, 0, 1 if nslab else 0, nslab], n=ws)      # nslab: slabs the buffer was sized for (checked at launch: ADVICE r5)
             if nslab:
-                self.__dict__.setdefault("_wgrad_jobs", []).append((slabbuf, wkey, nslab, cout, cin, ks * ks))
+                self._wgrad_jobs.append((slabbuf, wkey, nslab, cout, cin, ks * ks))
         # dy in a buffer of its own (small planes): the data gradient - the only thing the next layer's backward waits for -
         # goes first and the weight gradient becomes a scheduling group of its own, so that the latency-bound chains of the deep
         # levels (BatchNorm backward -> data gradient -> next BatchNorm backward) no longer carry the weight gradients and their
@@ -462,8 +493,7 @@ class Plan:
             # uses grad(x) in place as its dy instead of running uz_relu_bwd over it (conv_relu.bwd checks "last writer")
             fold = None
             st = (x.buf.relu or {}).get((x.c0, x.C)) if x.nb is None else None
-            if st is not None and ks == 3 and wrow0 == 0 and os.environ.get("UZ_FOLD_RELU_BWD", "1") == "1" \
-                    and not self.__dict__.get("_in_rev", False):
+            if st is not None and ks == 3 and wrow0 == 0 and os.environ.get("UZ_FOLD_RELU_BWD", "1") == "1":
                 npart = self.L.uz_conv_bwd_relu_partials(cin, cout, x.N, x.H, x.W, ks)
                 if npart > 0:
                     fold = st["fold"] = dict(part=self.vec(x.buf.name + f":dbpart{x.c0}", 4 * cin * npart), npart=npart,
@@ -507,7 +537,7 @@ class Plan:
         blocks, where the backward tape recomputes it together with everything else."""
         if x.C == x.Ctot:
             return x
-        ctx = self.__dict__.get("_rev_ctx")
+        ctx = self._rev_ctx
         if ctx is not None:
             xc = self._pool((ctx, "win" + ("F" if ".f_block." in wkey else "G")), x.C, x.H, x.W)
             for b0 in (0, x.N + 1):                          # pooled scratch is shared between shapes: re-zero the depth padding
@@ -515,7 +545,7 @@ class Plan:
         else:
             xc = self.vol(wkey + ":win", x.C, x.N, x.H, x.W, requires_grad=False)
         self.add_views(x, None, xc)
-        self.__dict__.setdefault("_win_of", {})[wkey] = xc
+        self._win_of[wkey] = xc
         return xc
 
     def _decouple_wgrad(self, x, ks, name=""):
@@ -523,11 +553,11 @@ class Plan:
         latency-bound planes (decouple_wgrad_px) and in the sub-networks named by decouple_wgrad_prefixes - chains whose backward
         has no independent partner chain for the second lane, so the weight gradient of layer L runs beside BatchNorm backward +
         data gradient of layer L - 1 (PHiSeg's likelihood: +1 %; its posterior / prior nets: -0.5 ... -1 %, they already pair up)."""
-        if x.nb is not None or ks != 3 or self.n_lanes <= 1 or self.__dict__.get("_in_rev", False):
+        if x.nb is not None or ks != 3 or self.n_lanes <= 1:
             return False
         lim = int(os.environ.get("UZ_DECOUPLE_WGRAD", str(self.decouple_wgrad_px)))
         pref = os.environ.get("UZ_DECOUPLE_PREFIX")
-        pref = tuple(q for q in pref.split(",") if q) if pref is not None else tuple(self.__dict__.get("decouple_wgrad_prefixes", ()))
+        pref = tuple(q for q in pref.split(",") if q) if pref is not None else tuple(self.decouple_wgrad_prefixes)
         return x.N * x.H * x.W <= lim or any(name.startswith(q) for q in pref)
 
     def _gy_scratch(self, like):
@@ -546,7 +576,7 @@ class Plan:
         a = out if out is not None else new(name + ":a")
         assert a.C == cout and a.H == x.H and a.W == x.W
         # (4 C floats: mean, rstd and - where the statistics come from the convolution's partials - alpha, beta' for a data gradient
-        # that folds this unit's backward reduction, see _split_storage_passes)
+        # that folds this unit's backward reduction, see _passes._split_storage_passes)
         save = save if save is not None else self.vec(name + ":bnsave", 4 * cout)
         # BatchNorm statistics in the convolution's epilogue (torchlayers.py:18-21: every Conv2d of a unit feeds a BatchNorm2d):
         # where the forward kernel supports it, it leaves per-tile {sum, sum of squares, max, max(-y)} partials and the
@@ -570,12 +600,12 @@ class Plan:
         bnws = self.L.uz_bn_workspace(cout, x.N, x.H, x.W)
         self.scratch["bn"] = max(self.scratch["bn"], bnws)
         gam, bet = bprefix + ".weight", bprefix + ".bias"
-        # unit record for the split-storage passes (finalize -> _split_storage_passes); units inside reversible sequences (shared scratch,
+        # unit record for the split-storage passes (finalize -> _passes._split_storage_passes); units inside reversible sequences (shared scratch,
         # recomputation inside the backward tape) and volume units stay as they are
-        plain = ybuf is None and a_grad is None and x.nb is None and self.__dict__.get("_rev_ctx") is None and self.target is self.fwd_ops
+        plain = ybuf is None and a_grad is None and x.nb is None and self._rev_ctx is None and self.target is self.fwd_ops
         unit = dict(name=name, y=y, a=a, save=save, relu=int(relu), npart=npart, C=cout, N=x.N, H=x.H, W=x.W) if plain else None
         if unit is not None:
-            self.__dict__.setdefault("_units", []).append(unit)
+            self._units.append(unit)
         op_fwd = self._emit(self.target, "UZ_OP_BN_RELU_FWD",
                    p=[y, self.P(gam), self.P(bet), self.B(bprefix + ".running_mean"), self.B(bprefix + ".running_var"),
                       save, a, ("scratch", "bn"), self.amax_out(a), bnpart,
@@ -617,9 +647,9 @@ class Plan:
                 self._dbias_jobs.append((dbpart, bkey, dbrows, cout, 1))
             rec = {}
             self._conv_bwd(x, wkey, gyv, ks, rec=rec)
-            if x.nb is not None and ks == 3 and ybuf is None and a_grad is None and self.__dict__.get("_rev_ctx") is None:
-                # volume unit: its three backward ops share the zero-bordered dy scratch (see _b16_pass)
-                self.__dict__.setdefault("_vol_units", []).append(dict(bn_bwd=op_bwd, gyv=gyv, wgrad=rec.get("wgrad"), dgrad=rec.get("dgrad")))
+            if x.nb is not None and ks == 3 and ybuf is None and a_grad is None and self._rev_ctx is None:
+                # volume unit: its three backward ops share the zero-bordered dy scratch (see _passes._b16_pass)
+                self._vol_units.append(dict(bn_bwd=op_bwd, gyv=gyv, wgrad=rec.get("wgrad"), dgrad=rec.get("dgrad")))
             if unit is not None:
                 unit.update(bn_bwd=op_bwd, ga=ga, ks=ks, cin=x.C, wgrad=rec.get("wgrad"), dgrad=rec.get("dgrad"))
         self._push_bwd(bwd)
@@ -629,12 +659,11 @@ class Plan:
     def _pool(self, key, C, H, W, vec=False):
         """Scratch activations of the reversible blocks: one buffer per (branch, role, shape), re-used by every block that
         needs that role - nothing inside a reversible sequence is kept for the backward pass, it is recomputed."""
-        pool = self.__dict__.setdefault("_rev_pool", {})
-        slots = self.__dict__.setdefault("_rev_slots", {})
+        pool, slots = self._rev_pool, self._rev_slots
         k = (key, C, H, W)
         if k not in pool:
             nm = "revpool:" + "/".join(map(str, k))
-            D = self.__dict__.get("_vol_depth")
+            D = self._vol_depth
             v = self.vec(nm, C) if vec else (self.vol(nm, C, D, H, W) if D else self.buf(nm, C, H, W))
             # all shapes of one (branch, role) share ONE region sized for the largest of them: a reversible sequence's scratch is
             # dead as soon as the next sequence of the branch starts (forward) or has been back-propagated (backward)
@@ -839,8 +868,7 @@ class Plan:
             # (the third unit of every vanilla U-Net block): fold that unit's ReLU backward in, like _conv_bwd does
             fold = None
             st = (x.buf.relu or {}).get((x.c0, x.C)) if x.nb is None else None
-            if st is not None and bcode in ("UZ_OP_AVGPOOL_BWD", "UZ_OP_BILINEAR_BWD") and not self.__dict__.get("_in_rev", False) \
-                    and os.environ.get("UZ_FOLD_RELU_BWD", "1") == "1":
+            if st is not None and bcode in ("UZ_OP_AVGPOOL_BWD", "UZ_OP_BILINEAR_BWD") and os.environ.get("UZ_FOLD_RELU_BWD", "1") == "1":
                 rows = self.L.uz_resample_bwd_relu_rows(0 if bcode == "UZ_OP_AVGPOOL_BWD" else 1, x.C, x.N, x.H, x.W)
                 fold = st["fold"] = dict(part=self.vec(x.buf.name + f":dbpart{x.c0}", 2 * rows * x.C), npart=rows, dbl=1,
                                          amax=self.amax_out(self.gview(x)), claims=self._nclaims[x.buf])
@@ -985,7 +1013,7 @@ class Plan:
         wm, bm, wsg, bsg = mu_prefix + ".weight", mu_prefix + ".bias", sigma_prefix + ".weight", sigma_prefix + ".bias"
         L, cin = self.ptab.shape[wm][0], h.C
         fuse = (os.environ.get("UZ_FUSE_HEADS", "1") == "1" and h.nb is None and self.ptab.shape[wm][2:] == (1, 1) and self.ptab.shape[wsg] == self.ptab.shape[wm]
-                and len(self.ptab.shape[wm]) == 4 and bool(self.L.uz_latent_heads_ok(cin, L)) and not self.__dict__.get("_in_rev", False))
+                and len(self.ptab.shape[wm]) == 4 and bool(self.L.uz_latent_heads_ok(cin, L)))
         if not fuse:
             mu = self.conv_bare(h, mu_prefix)
             ps = self.conv_bare(h, sigma_prefix)
@@ -1077,757 +1105,26 @@ class Plan:
         self.ptr_tables.append(refs)
         return ("ptrtab", len(self.ptr_tables) - 1)
 
-    # ------------------------------------------------------------------ split-storage passes over the emitted ops
+    # ------------------------------------------------------------------ the tape rewrites (_passes.py, _chain_plan.py) as seen from the plan
     def _all_tapes(self):
         return [("fwd", self.fwd_ops), ("loss", self.loss_ops), ("bwd", self.bwd_ops)] + list(self.extra_ops.items())
 
     def _users_of(self, v):
-        """(writers, readers) of the channels of view `v` across all tapes, each a list of (op, slot name, ref)."""
-        writers, readers = [], []
-        for _, ops in self._all_tapes():
-            for o in ops:
-                wr = _ops.writes(o)
-                for j, r in enumerate(o["p"]):
-                    if isinstance(r, View) and r.buf is v.buf and r.c0 < v.c0 + v.C and v.c0 < r.c0 + r.C:
-                        (writers if j in wr else readers).append((o, _ops.SCHEMA[o["code"]].p[j], r))
-        return writers, readers
+        return _passes._users_of(self, v)
 
-    def _sole_dgrad(self, u, tabbed):
-        """The plain data gradient that is the ONLY writer of unit `u`'s dA, which nothing but the unit's BatchNorm backward reads;
-        None when there is no such op."""
-        B, ga = u.get("bn_bwd"), u.get("ga")
-        if B is None or not isinstance(ga, View) or ga.nb is not None or id(ga.buf) in tabbed:
-            return None
-        writers, readers = self._users_of(ga)
-        if len(writers) != 1 or len(readers) != 1 or readers[0][0] is not B:
-            return None
-        W, nm, r = writers[0]
-        if W["code"] != "UZ_OP_CONV_BWD_DATA" or nm != "dx" or (r.c0, r.C, r.nb) != (ga.c0, ga.C, None) or W.p("fold_arg") is not None or W.i("accumulate"):
-            return None
-        return W
-
-    def _split_storage_passes(self):
-        """Plan-time rewrites on the Conv2D units (torchlayers.py:18-21) of the large planes, all decided from the emitted ops:
-          1. folded backward reduction - where the ONLY writer of a unit's dA is an unsplit split-path data gradient, that launch masks
-             dA with the unit's ReLU and leaves the BatchNorm-backward sums in its epilogue; the unit's backward runs a per-channel
-             finalise instead of the reduction pass over dA and y (UZ_FOLD_BN_BWD=0 switches it off);
-          2. dY in split storage - where both consumers of a unit's dy (its weight and data gradient) run on the split path, the
-             BatchNorm-backward apply pass writes the operand pieces instead of fp32 values (UZ_PACK_DY=0);
-          3. activations in split storage - a buffer written only by BatchNorm-apply / pooling / interpolation launches that know
-             their bound beforehand and read only by split-path convolutions (forward + weight gradient) is kept as operand pieces;
-             a concat buffer's (at most two) producers each scale from a slot of their own (UZ_PACK_ACT=0).
-        Returns a summary dict (also kept as self.round4)."""
-        info = dict(folded=0, dy_packed=0, act_packed=0, act_views=0)
-        self.round4 = info
-        units = [u for u in self.__dict__.get("_units", []) if "bn_bwd" in u or "bn_fwd" in u]
-        if self.L.uz_get_conv_math() in (0, 3) or not self.bn_training:
-            return info                              # fp32-only / bf16 modes have no two-piece operands
-        env = lambda k: os.environ.get(k, "1") == "1"
-        large = lambda u: u["N"] * u["H"] * u["W"] > 4096 and (u["H"] * u["W"]) % 4 == 0
-        tabbed = {id(q.buf) for t in self.ptr_tables for q in t if isinstance(q, View)}
-        # ---- 1. folded backward reduction
-        # (off by default: measured on MI355X the epilogue's extra read of y is exposed - the 64-channel-tile kernel keeps ONE
-        #  workgroup per CU, so its memory phase overlaps nothing: data gradient of 128 -> 128 @ 128 x 128 451 -> 573 us against
-        #  269 -> 170 us for the unit's BatchNorm backward; step +-0)
-        if os.environ.get("UZ_FOLD_BN_BWD", "0") == "1" and self.bwd_ops:
-            for u in units:
-                if not large(u) or u["npart"] <= 0:
-                    continue
-                W = self._sole_dgrad(u, tabbed)
-                if W is None:
-                    continue
-                _, cin_w, cout_w, N, H, Wd, ks = conv_dims(W)
-                if ks != 3:
-                    continue
-                rows = self.L.uz_conv_bwd_relu_partials(cin_w, cout_w, N, H, Wd, 3)
-                if rows <= 0 or cin_w != u["C"]:
-                    continue
-                part = self.vec(u["name"] + ":bwdpart", 4 * u["C"] * rows)
-                y = u["y"]
-                W.set(p={"fold_arg": y, "partials": part, "bn_stats": u["save"]}, i={"ctot_fold": y.Ctot, "fold": 2, "fold_relu": u["relu"]})
-                u["bn_bwd"].set(p={"da_partials": part}, i={"npart": rows})
-                info["folded"] += 1
-        # ---- 1b. small planes: the data gradient's split-K reduce folded into the consumer's BatchNorm backward (the mirror of the
-        # forward's uz_conv_fwd_slabs / uz_bn_relu_fwd_slabs): where the ONLY writer of a unit's dA is a split-K fp32 data gradient, that
-        # launch leaves its partial sums in a buffer of the layer's own and the unit's one-workgroup-per-channel backward adds them
-        # itself - one reduction launch less on the backward chains of the 8 x 8 ... 2 x 2 levels (UZ_BN_FOLD_DGRAD=0 switches it off)
-        info["dgrad_folded"] = 0
-        if env("UZ_BN_FOLD_DGRAD") and self.bwd_ops:
-            for u in units:
-                if u["N"] * u["H"] * u["W"] > 4096:
-                    continue
-                W = self._sole_dgrad(u, tabbed)
-                if W is None:
-                    continue
-                _, cin_w, cout_w, N, H, Wd, ksw = conv_dims(W)
-                parts = self.L.uz_conv_bwd_splitk_parts(cin_w, cout_w, N, H, Wd, ksw)
-                if parts <= 1 or cin_w != u["C"]:
-                    continue
-                slabs = self.vec(u["name"] + ":daslabs", parts * N * cin_w * H * Wd)
-                W.set(p={"fold_arg": slabs}, i={"fold": 3})
-                u["bn_bwd"].set(p={"da_partials": slabs}, i={"nslab": parts})
-                info["dgrad_folded"] += 1
-        # ---- 2. dY in split storage
-        if env("UZ_PACK_DY") and self.bwd_ops:
-            for u in units:
-                B, wg, dg = u.get("bn_bwd"), u.get("wgrad"), u.get("dgrad")
-                if B is None or wg is None or not large(u) or u["ks"] != 3 or u["W"] % 4:
-                    continue
-                if u["N"] * u["H"] * u["W"] <= self.L.uz_bn_bwd_fused_limit(u["H"], u["W"]):
-                    continue                         # one-launch backward (channel's batch on chip): no tensor-wide bound before the first write
-                if self.L.uz_conv_route(2, u["cin"], u["C"], u["N"], u["H"], u["W"], 3) != 1:
-                    continue
-                if dg is not None and (self.L.uz_conv_route(1, u["cin"], u["C"], u["N"], u["H"], u["W"], 3) != 1 or dg.i("fold") == 1):
-                    continue
-                for o in (B, wg, dg):
-                    if o is not None:
-                        o.set(i={"dy_packed": 1})
-                info["dy_packed"] += 1
-        # ---- 3. activations in split storage
-        if env("UZ_PACK_ACT") and not self.extra_ops:
-            named = {id(v.buf) for v in self.named.values() if isinstance(v, View)}
-            for b in self.bufs:
-                if b.alias is not None or id(b) in tabbed or id(b) in named or (b.H * b.W) % 4 or b.N * b.H * b.W <= max(4096, self._chain_limit()):
-                    continue                                 # (planes of the deep-level chain stay fp32: its convolutions split on the fly)
-                wr_list, rd_list, ok = [], [], True
-                for tape, ops in self._all_tapes():
-                    for o in ops:
-                        c = o["code"]
-                        writer, reader = _ops.SPLIT_WRITERS.get(c), _ops.SPLIT_READERS.get(c)
-                        for nm, r in zip(_ops.SCHEMA[c].p, o["p"]):
-                            if _buf_of(r) is not b:
-                                continue
-                            if not isinstance(r, View) or r.nb is not None:
-                                ok = False
-                            elif writer and nm == writer[0]:
-                                if c == "UZ_OP_BN_RELU_FWD":
-                                    N, H, W = o.i("N", "H", "W")
-                                    one_launch = 4096 < N * H * W <= self.L.uz_bn_fwd_fused_limit(H, W)      # mid path: a-priori bound from the parameters
-                                    if not (o.i("training") and o.i("nslab") == 0 and (o.i("npart") > 0 or one_launch)):
-                                        ok = False           # needs the bound before the first word is written
-                                elif o.p("x_amax") is None:
-                                    ok = False               # pooling / interpolation forward their INPUT's bound
-                                wr_list.append((o, r))
-                            elif reader and nm == reader[0]:
-                                kind, cin, cout, N, H, W, ks = conv_dims(o)
-                                if ks != 3 or self.L.uz_conv_route(kind, cin, cout, N, H, W, 3) != 1 or (kind == 0 and o.i("slabs_only")):
-                                    ok = False
-                                rd_list.append((o, r))
-                            else:
-                                ok = False
-                if not ok or not wr_list or not rd_list:
-                    continue
-                wr_list.sort(key=lambda t: t[1].c0)
-                segs = [(r.c0, r.c0 + r.C) for _, r in wr_list]
-                if any(a[1] > b2[0] for a, b2 in zip(segs, segs[1:])):
-                    continue                                 # overlapping producers
-                plan_rd = []
-                for o, r in rd_list:
-                    cov = [sg for sg in segs if sg[0] < r.c0 + r.C and r.c0 < sg[1]]
-                    tiled = cov and cov[0][0] <= r.c0 and cov[-1][1] >= r.c0 + r.C and all(a[1] == b2[0] for a, b2 in zip(cov, cov[1:]))
-                    if not tiled or len(cov) > 2 or (len(cov) == 2 and (cov[1][0] - r.c0) % 16):
-                        ok = False
-                        break
-                    plan_rd.append((o, r, cov))
-                if not ok:
-                    continue
-                slot_of = {}
-                for o, r in wr_list:
-                    _, bound, flag = _ops.SPLIT_WRITERS[o["code"]]
-                    slot = slot_of[(r.c0, r.c0 + r.C)] = ("amax", self._new_amax())
-                    o.set(p={bound: slot + ("acc",)}, i={flag: 1})
-                for o, r, cov in plan_rd:
-                    _, bound, bound2, seg2_c0, flag = _ops.SPLIT_READERS[o["code"]]
-                    two = len(cov) == 2
-                    o.set(p={bound: slot_of[cov[0]], bound2: slot_of[cov[1]] if two else None}, i={flag: 1, seg2_c0: cov[1][0] - r.c0 if two else 0})
-                b.packed = True
-                info["act_packed"] += 1
-                info["act_views"] += len(wr_list)
-        return info
-
-    def _bn_offchain_pass(self):
-        """Takes BatchNorm's apply pass out of the forward's dependency chain (round 6; UZ_BN_OFFCHAIN=1, off by default).  For a Conv -> BatchNorm -> ReLU
-        unit on the large planes whose activation is kept in split storage and read, in the forward tape, by exactly ONE 3 x 3 split-path
-        convolution (the middle layers of every three-convolution block; the weight gradient of that convolution reads it too, in the
-        backward tape): the unit's BatchNorm op becomes two - the statistics launch, which stays in the unit's group, and the apply pass, a
-        group of its own - and the consumer reads the unit's PRE-normalisation output with its statistics table and applies BatchNorm +
-        ReLU in its staging (uz_conv_fwd_bn_ex: the same operand pieces the apply pass stores).  The consumer then depends on the
-        statistics launch only; the apply pass still writes the activation for the weight gradient, beside the chain instead of in it."""
-        info = dict(units=0)
-        self.bn_offchain = info
-        if os.environ.get("UZ_BN_OFFCHAIN", "0") != "1" or self.L.uz_get_conv_math() in (0, 3) or not self.bn_training or self.extra_ops:
-            return info
-        ops = self.fwd_ops
-        for u in [u for u in self.__dict__.get("_units", []) if "bn_fwd" in u]:
-            B = u["bn_fwd"]
-            if not (B.i("a_packed") == 1 and B.i("npart") > 0 and B.i("nslab") == 0 and B.i("training") == 1) or B.i("phase") or B.i("b16"):
-                continue                                             # large path, statistics from the convolution's partials, split-storage output
-            N, H, W = B.i("N", "H", "W")
-            if N * H * W <= self.L.uz_bn_fwd_fused_limit(H, W) or not any(o is B for o in ops):
-                continue
-            y, a = B.p("y", "a")
-            if not (isinstance(a, View) and isinstance(y, View)) or a.nb is not None or y.nb is not None or not a.contiguous:
-                continue
-            readers = [(o, nm, r) for o in ops for nm, r in zip(_ops.SCHEMA[o["code"]].p, o["p"]) if o is not B and isinstance(r, View) and r.buf is a.buf]
-            if len(readers) != 1 or any(isinstance(r, View) and r.buf is a.buf for o in self.loss_ops for r in o["p"]):
-                continue
-            R, nm, rv = readers[0]
-            if R["code"] != "UZ_OP_CONV_FWD" or nm != "x" or R.i("ks") != 3 or R.i("x_packed") != 1 or any(R.i("relu", "x_seg2_c0", "slabs_only", "bn_in", "b16")) or \
-                    (rv.c0, rv.C, rv.nb) != (0, a.buf.C, None):
-                continue
-            k = next(n for n, o in enumerate(ops) if o is B)
-            fin = B.clone().set(p={"y": None, "a": None}, i={"phase": 1})
-            self._detached = getattr(self, "_detached", 0) + 1
-            kind, slot, _acc = B.p("a_amax")                         # the apply pass reads the bound the statistics launch published
-            app = B.clone(gid=("bnapply", self._detached)).set(p={"running_mean": None, "running_var": None, "bn_partials": None, "a_amax": (kind, slot)},
-                                                                    i={"phase": 2})
-            ops[k:k + 1] = [fin, app]
-            u["bn_fwd"] = fin
-            R.set(p={"x": y, "x_amax2": None, "bn_stats": B.p("save")}, i={"ctot_x": y.Ctot, "x_packed": 0, "bn_in": 1 | (B.i("relu") << 1)})
-            info["units"] += 1
-        return info
-
-    # ------------------------------------------------------------------ bf16 storage (BASELINE config 5: PHiSeg3D "bf16")
     def _b16_slots(self, o):
-        """(p[] slot, format bit) of the tensor operands of op `o` that may be bf16; () = no bf16-storage form.  A pass-through to
-        _ops.b16_slots, kept because callers outside this module ask the plan."""
-        return _ops.b16_slots(o)
+        return _passes._b16_slots(self, o)
 
     def _b16_ok(self, o):
-        """Can op `o` run through its bf16-storage entry point (whatever the formats of its operands turn out to be)?  Only the base
-        form of a kernel has one (Op.base_form: the format bits themselves are what this pass sets, they do not count)."""
-        c = o["code"]
-        if c in _ops.CONV_KIND:
-            kind, cin, cout, N, H, W, ks = conv_dims(o)
-            base = o.base_form() and (kind != 1 or o.p("fold_arg") is None)
-            if ks == 1:
-                return cout in (1, 2, 3, 4, 6, 8) and cin <= 512 and (H * W) % 4 == 0 and base
-            if ks != 3 or W % 32:
-                return False
-            if kind == 2:
-                # (a weight gradient may leave its slabs to the table launch - slabs_only / nslab - in either storage: uz_conv_bwd_weight_b16 takes slabs_out)
-                if any(o.i("x_packed", "x_seg2_c0", "dy_packed")) or o.p("db") is not None:
-                    return False
-            elif not base:
-                return False
-            if kind != 2 and self.L.uz_conv_split_parts(kind, cin, cout, N, H, W) != 1:
-                return False
-            return self.L.uz_conv_route(kind, cin, cout, N, H, W, 3) == 1
-        if c == "UZ_OP_BN_RELU_FWD":
-            N, H, W = o.i("N", "H", "W")
-            return N * H * W > 32768 and (H * W) % 4 == 0 and o.i("training") == 1 and o.base_form()
-        if c == "UZ_OP_BN_RELU_BWD":
-            N, H, W = o.i("N", "H", "W")
-            return N * H * W > 32768 and (H * W) % 4 == 0 and o.base_form() and o.p("da_partials") is None
-        if c in ("UZ_OP_AVGPOOL3D_FWD", "UZ_OP_AVGPOOL3D_BWD"):
-            return o.i("W") % 4 == 0 and o.i("H") % 2 == 0
-        if c in ("UZ_OP_DEPTH_LERP_FWD", "UZ_OP_DEPTH_LERP_BWD"):
-            return (o.i("H") * o.i("W")) % 4 == 0
-        if c == "UZ_OP_BILINEAR_FWD":                          # the band kernel's shapes
-            return o.i("W") % 4 == 0 and o.i("W") <= 128 and o.i("H") >= 4 and o.base_form() and (o.p("x_amax") is None or True)
-        if c == "UZ_OP_BILINEAR_BWD":
-            return 2 * o.i("W") <= 128 and o.i("H") >= 4 and 256 % o.i("W") == 0 and o.p("a") is None and o.base_form()
-        return False
-
-    def _b16_pass(self):
-        """Which volume tensors are kept in bf16 (UZ_STORE_B16=1 / Plan.store_b16, single-piece bf16 arithmetic only): a buffer whose
-        EVERY reader and writer - in every tape - is an op with a bf16-storage form on a shape that form serves (the 3x3x3
-        convolutions on the matrix pipe with planes wider than 32, the large-plane BatchNorm path, AvgPool3d, the depth stage of the
-        trilinear interpolation).  The decision is per buffer, every op carries one format bit per tensor operand (its b16 slot), so the
-        two formats mix freely: what some other op touches (the 1x1x1 heads' inputs, the in-plane interpolation's operands, the
-        latent and loss tensors, the image) stays fp32.  A unit's dy moves to a bf16 twin of the zero-bordered scratch class when
-        its three backward ops all qualify.  Returns / keeps a summary in self.b16_info."""
-        info = self.b16_info = dict(buffers=0, grads=0, dy=0, bytes_saved=0, ops=0)
-        on = os.environ.get("UZ_STORE_B16", "1" if self.__dict__.get("store_b16") else "0") == "1"
-        if not on or self.L.uz_get_conv_math() != 3 or not self.bn_training or self.extra_ops:
-            return info
-        all_ops = [o for ops in (self.fwd_ops, self.loss_ops, self.bwd_ops) for o in ops]
-        tabbed = {id(q.buf) for t in self.ptr_tables for q in t if isinstance(q, View)}
-        named = {id(v.buf) for v in self.named.values() if isinstance(v, View)}
-        ok_cache = {}
-        bad, seen = set(), set()
-        for o in all_ops:
-            slots = [j for j, _ in self._b16_slots(o)]
-            if id(o) not in ok_cache:
-                ok_cache[id(o)] = bool(slots) and self._b16_ok(o)
-            for j, r in enumerate(o["p"]):
-                b = _buf_of(r)
-                if b is None:
-                    continue
-                seen.add(id(b))
-                if not (ok_cache[id(o)] and j in slots):
-                    bad.add(id(b))
-        for b in self.bufs:
-            if not b.vol or b.alias is not None or id(b) in tabbed or id(b) in named or id(b) in bad or id(b) not in seen:
-                continue
-            if b.W % 32 or (b.N - 2) * b.H * b.W <= 32768:
-                continue
-            b.b16 = True
-            info["grads" if b.name.startswith("grad:") else "buffers"] += 1
-            info["bytes_saved"] += 2 * b.numel
-        # dy of the units: the lane's zero-bordered scratch class (slices, elements per slice) -> its bf16 twin
-        for u in self.__dict__.get("_vol_units", []):
-            B, Wg, Dg, gyv = u["bn_bwd"], u["wgrad"], u["dgrad"], u["gyv"]
-            if Wg is None or gyv.zkey is None or gyv.view is not None:
-                continue
-            if not (self._b16_ok(B) and self._b16_ok(Wg) and (Dg is None or self._b16_ok(Dg))):
-                continue
-            old = gyv.zkey
-            new = (old[0], old[1], 16)
-            self._gyz[new] = max(self._gyz.get(new, 0), (self._gyz[old] + 1) // 2)
-            gyv.zkey = new
-            assert B.p("dy") == ("gyvol", old)
-            B.set(p={"dy": ("gyvol", new)})
-            B["b16_dy"] = Wg["b16_dy"] = True
-            if Dg is not None:
-                assert Dg.p("dy") == ("gywin", old)
-                Dg.set(p={"dy": ("gywin", new)})
-                Dg["b16_dy"] = True
-            info["dy"] += 1
-        used = set()
-        for o in all_ops:
-            for q in o["p"]:
-                if isinstance(q, _ScratchView) and q.zkey is not None:
-                    used.add(q.zkey)
-                elif isinstance(q, tuple) and q and q[0] in ("gyvol", "gywin"):
-                    used.add(q[1])
-        for k in [k for k in self._gyz if k not in used]:
-            del self._gyz[k]                                   # an fp32 class every unit has left
-        # format bits
-        for o in all_ops:
-            slots = self._b16_slots(o)
-            if not slots or not ok_cache.get(id(o)):
-                continue
-            dy_slot = _ops.SCHEMA[o["code"]].px["dy"] if o.get("b16_dy") else None
-            bits = 0
-            for j, k in slots:
-                b = _buf_of(o["p"][j])
-                bits |= int((b is not None and b.b16) or j == dy_slot) << k
-            if bits:
-                o.set(i={"b16": bits})
-                info["ops"] += 1
-        return info
-
-    # ------------------------------------------------------------------ finalisation
-
-    # ------------------------------------------------------------------ deep-level chain (round 6; csrc/chain.hip)
-    def _chain_limit(self):
-        """Largest N*H*W whose ops run inside the persistent chain launch (0: off).  Only with two-piece operands (the chain's
-        convolutions are split-fp16: UZ_CONV_MATH=f32 keeps every convolution on the fp32 matrix pipe, bf16 is the volume path) and
-        training-mode BatchNorm."""
-        px = int(os.environ.get("UZ_CHAIN", str(self.chain_px)))
-        if px <= 0 or not self.bn_training or self.L.uz_get_conv_math() in (0, 3) or self.extra_ops:
-            return 0
-        return px
-
-    def _hazard_deps(self, ops):
-        """Per op of `ops` (program order) the set of earlier ops it must follow (RAW, WAR, WAW over the same resources the lane
-        scheduler uses; bound-slot accumulators commute with each other)."""
-        hist, deps = {}, []
-        for k, o in enumerate(ops):
-            reads, writes, accs = self._access(o)
-            d = set()
-            for space, lo, hi in reads:
-                for e in hist.get(space, ()):
-                    if e[0] < hi and lo < e[1]:
-                        if e[2] is not None:
-                            d.add(e[2])
-                        d.update(e[4])
-            for space, lo, hi in accs:
-                for e in hist.get(space, ()):
-                    if e[0] < hi and lo < e[1]:
-                        if e[2] is not None:
-                            d.add(e[2])
-                        d.update(e[3])
-            for space, lo, hi in writes:
-                for e in hist.get(space, ()):
-                    if e[0] < hi and lo < e[1]:
-                        if e[2] is not None:
-                            d.add(e[2])
-                        d.update(e[3])
-                        d.update(e[4])
-            d.discard(k)
-            deps.append(d)
-            for space, lo, hi in reads:
-                for e in hist.setdefault(space, []):
-                    if e[0] < hi and lo < e[1]:
-                        e[3].add(k)
-                hist[space].append([lo, hi, None, {k}, set()])
-            for space, lo, hi in accs:
-                for e in hist.setdefault(space, []):
-                    if e[0] < hi and lo < e[1]:
-                        e[4].add(k)
-                hist[space].append([lo, hi, None, set(), {k}])
-            for space, lo, hi in writes:
-                lst = hist.setdefault(space, [])
-                keep = [e for e in lst if not (lo <= e[0] and e[1] <= hi)]
-                keep.append([lo, hi, k, set(), set()])
-                hist[space] = keep
-        return deps
-
-    @staticmethod
-    def _chain_net(o):
-        """The sub-network an op belongs to (first component of the name of the tensor / parameter it is about): backward chains are
-        built per sub-network, so that the prior's deep levels - which only wait for the KL gradients - run beside the likelihood's
-        device-filling kernels instead of behind them."""
-        c = o["code"]
-        if c in ("UZ_OP_CONV_BWD_DATA", "UZ_OP_CONV_FWD"):
-            w = o.p("w")
-            return w[1].split(".")[0] if isinstance(w, tuple) else None          # w = ("param", key, offset)
-        slot = {"UZ_OP_BN_RELU_BWD": "y", "UZ_OP_BN_RELU_FWD": "y", "UZ_OP_AVGPOOL_BWD": "dy", "UZ_OP_BILINEAR_BWD": "dy",
-                "UZ_OP_LATENT_BWD": "dmu", "UZ_OP_LATENT_HEADS_BWD_DATA": "dy_a"}.get(c)
-        if slot is None or not isinstance(o.p(slot), View):
-            return None
-        nm = o.p(slot).buf.name
-        return (nm[5:] if nm.startswith("grad:") else nm).split(".")[0]
-
-    def _chain_eligible_fwd(self, o, px):
-        c = o["code"]
-        if c == "UZ_OP_CONV_FWD":
-            _, cin, cout, N, H, W, ks = conv_dims(o)
-            x = o.p("x")
-            if o.i("b16") or ks != 3 or N * H * W > px or o.i("relu") or o.i("x_packed") or o.p("bn_partials") is not None or not isinstance(x, View) or x.nb is not None:
-                return False
-            if cin <= 4:
-                return True
-            return cin % 16 == 0 and cout % 32 == 0 and o.p("x_amax") is not None
-        if c == "UZ_OP_BN_RELU_FWD":
-            N, H, W = o.i("N", "H", "W")
-            y = o.p("y")
-            return not o.i("b16") and o.i("training") == 1 and o.i("npart") == 0 and not o.i("a_packed") and N * H * W <= px and isinstance(y, View) and y.nb is None
-        if c == "UZ_OP_AVGPOOL_FWD":
-            N, H, W = o.i("N", "H", "W")
-            return N * ((H + 1) // 2) * ((W + 1) // 2) <= px and not o.i("y_packed") and o.p("x").nb is None
-        if c == "UZ_OP_BILINEAR_FWD":
-            N, H, W = o.i("N", "H", "W")
-            return not o.i("b16") and N * 4 * H * W <= px and not o.i("y_packed") and o.p("x").nb is None
-        if c == "UZ_OP_LATENT_HEADS_FWD":
-            N, H, W = o.i("N", "H", "W")
-            return o.i("L") == 2 and N * H * W <= px
-        return False
-
-    def _chain_eligible_bwd(self, o, px):
-        c = o["code"]
-        own_dy = lambda r: isinstance(r, _ScratchView) and r.view is not None and r.zkey is None
-        if c == "UZ_OP_BN_RELU_BWD":
-            N, H, W = o.i("N", "H", "W")
-            da, y = o.p("da", "y")
-            return (not o.i("b16") and N * H * W <= px and not any(o.i("npart", "dy_packed", "dbias_rows")) and own_dy(o.p("dy"))
-                    and isinstance(da, View) and da.nb is None and isinstance(y, View) and not y.buf.packed)
-        if c == "UZ_OP_CONV_BWD_DATA":
-            _, cin, cout, N, H, W, ks = conv_dims(o)
-            fold = o.i("fold")
-            if o.i("b16") or ks != 3 or N * H * W > px or not own_dy(o.p("dy")) or fold not in (0, 3) or o.i("dy_packed") or o.p("dx").nb is not None:
-                return False
-            if cin <= 4:
-                return fold == 0
-            return cout % 16 == 0 and cin % 32 == 0 and o.p("dy_amax") is not None
-        if c == "UZ_OP_AVGPOOL_BWD":
-            N, H, W = o.i("N", "H", "W")
-            return N * H * W <= px and o.p("a") is None and o.p("dy").nb is None
-        if c == "UZ_OP_BILINEAR_BWD":
-            N, H, W = o.i("N", "H", "W")
-            return not o.i("b16") and N * 4 * H * W <= px and o.p("a") is None and o.p("dy").nb is None
-        if c == "UZ_OP_LATENT_BWD":
-            dmu = o.p("dmu")
-            return isinstance(dmu, View) and dmu.C == 2 and dmu.N * dmu.H * dmu.W <= px
-        if c == "UZ_OP_LATENT_HEADS_BWD_DATA":
-            N, H, W = o.i("N", "H", "W")
-            return o.i("L") == 2 and N * H * W <= px
-        return False
-
-    def _chain_pass(self):
-        """Collects the small-plane ops of a tape into UZ_OP_CHAIN ops (uz_chain_run): a sub-DAG is levelled into phases of independent
-        sub-ops, every 3 x 3 convolution gets a split-K factor and a slab buffer of its own, its weights a fragment-ordered image packed
-        once per tape (UZ_OP_CHAIN_PACK).  Forward tape: one chain; backward tape: one chain per sub-network (_chain_net).  The tape
-        keeps a valid program order: [every op the chain depends on] [chain] [the rest]; a chain's set must be convex in the dependency
-        DAG (an op outside may not sit between two inside) - offenders and what hangs behind them stay per-op launches."""
-        self.chain_info = {}
-        px = self._chain_limit()
-        if px <= 0:
-            return
-        only = os.environ.get("UZ_CHAIN_NETS")                # diagnostics: "fwd,prior" = the forward chain and the prior's backward chain only
-        only = None if only is None else set(only.split(","))
-        jobs = [("fwd", self.fwd_ops, self._chain_eligible_fwd, None)] if (only is None or "fwd" in only) else []
-        if self.bwd_ops and os.environ.get("UZ_CHAIN_BWD", "1") == "1":
-            nets = []
-            for o in self.bwd_ops:
-                if self._chain_eligible_bwd(o, px):
-                    nt = self._chain_net(o)
-                    if nt not in nets:
-                        nets.append(nt)
-            jobs += [("bwd", self.bwd_ops, self._chain_eligible_bwd, nt) for nt in nets if only is None or nt in only]
-        for which, ops, elig, net in jobs:
-            if ops:
-                self._chain_build(which, ops, elig, net, px)
-        # the chains' weight images: one buffer and one packing launch per tape, a scheduling group of its own behind the parameter bound
-        for which, imgs in self._chain_imgs.items():
-            if not imgs:
-                continue
-            off = blk = 0
-            refs = []
-            for wkey, e in imgs.items():
-                e["off"], e["blk0"] = off, blk
-                refs += [self.P(wkey), ("chainimg", which, wkey), ("raw", e["mc"]), ("raw", e["kc"]), ("raw", e["cin"]), ("raw", e["dgrad"]), ("raw", blk)]
-                off += e["bytes"]
-                blk += e["blocks"]
-            self._chain_imgbuf[which] = self.vec("chain_weights:" + which, off // 4)
-            tape = self.fwd_ops if which == "fwd" else self.bwd_ops
-            pos = next(k for k, o in enumerate(tape) if o["code"] == "UZ_OP_CHAIN")
-            tape.insert(pos, _ops.make("UZ_OP_CHAIN_PACK", p=[self.ptr_table(refs), ("amaxw", 0), self._chain_imgbuf[which]], i=[len(imgs), blk],
-                                       gid=("chainpack", which)))
-
-    def _chain_build(self, which, ops, elig, net, px):
-        fwd = which == "fwd"
-        E = [k for k, o in enumerate(ops) if elig(o, px) and (net is None or self._chain_net(o) == net)]
-        if len(E) < 8:
-            return
-        deps = self._hazard_deps(ops)
-        vkey = lambda v: (id(v.buf), v.c0) if isinstance(v, View) else (id(v.view.buf), v.view.c0)
-        # pairing tables
-        ywriter, bn_of_y, dgrad_of_dx, bn_of_da = {}, {}, {}, {}
-        for k, o in enumerate(ops):
-            c = o["code"]
-            if c == "UZ_OP_CONV_FWD" and isinstance(o.p("y"), View):
-                ywriter[vkey(o.p("y"))] = k
-            elif c == "UZ_OP_BN_RELU_FWD":
-                bn_of_y[vkey(o.p("y"))] = k
-            elif c == "UZ_OP_CONV_BWD_DATA" and isinstance(o.p("dx"), View):
-                dgrad_of_dx.setdefault(vkey(o.p("dx")), []).append(k)
-            elif c == "UZ_OP_BN_RELU_BWD" and isinstance(o.p("da"), View):
-                bn_of_da[vkey(o.p("da"))] = k
-        Es = set(E)
-        changed = True
-        while changed:
-            changed = False
-            for k in sorted(Es):
-                o = ops[k]
-                c = o["code"]
-                if c == "UZ_OP_BN_RELU_FWD" and o.i("nslab") > 0 and ywriter.get(vkey(o.p("y"))) not in Es:
-                    Es.discard(k); changed = True                 # its convolution leaves slabs for it outside the chain
-                elif c == "UZ_OP_CONV_FWD" and o.i("slabs_only") and bn_of_y.get(vkey(o.p("y"))) not in Es:
-                    Es.discard(k); changed = True
-                elif c == "UZ_OP_BN_RELU_BWD" and o.i("nslab") > 0:
-                    dg = dgrad_of_dx.get(vkey(o.p("da")), [])
-                    if len(dg) != 1 or dg[0] not in Es:
-                        Es.discard(k); changed = True             # dA arrives as slabs of a data gradient that is not in the chain
-                elif c == "UZ_OP_CONV_BWD_DATA" and o.i("fold") == 3 and bn_of_da.get(vkey(o.p("dx"))) not in Es:
-                    Es.discard(k); changed = True
-                elif c == "UZ_OP_LATENT_BWD" and not (k + 1 < len(ops) and ops[k + 1]["code"] == "UZ_OP_LATENT_HEADS_BWD_DATA" and (k + 1) in Es):
-                    Es.discard(k); changed = True
-                elif c == "UZ_OP_LATENT_HEADS_BWD_DATA" and not (k >= 1 and ops[k - 1]["code"] == "UZ_OP_LATENT_BWD" and (k - 1) in Es):
-                    Es.discard(k); changed = True
-            # convexity: no op outside may both depend on the set and be depended on by it
-            desc = set()
-            for k in range(len(ops)):
-                if any(d in Es or d in desc for d in deps[k]):
-                    desc.add(k)
-            bad = {k for k in Es if any((d not in Es) and (d in desc) for d in deps[k])}
-            if bad:
-                drop = set(bad)
-                for k in sorted(Es):
-                    if any(d in drop for d in deps[k]):
-                        drop.add(k)
-                Es -= drop
-                changed = True
-        if len(Es) < 8:
-            return
-        anc = set()
-        for k in reversed(range(len(ops))):
-            if k in Es or k in anc:
-                anc.update(d for d in deps[k] if d not in Es)
-        # a scheduling group (one unit's ops, same gid, back to back) shares the lane's scratch - a unit's dy, a convolution's split-K
-        # slabs - which the dependency analysis does not see: a group moves in front of the chain as a whole or not at all
-        runs, a0 = [], 0
-        for k in range(1, len(ops) + 1):
-            if k == len(ops) or ops[k]["gid"] != ops[a0]["gid"]:
-                runs.append((a0, k)); a0 = k
-        grew = True
-        while grew:
-            grew = False
-            for a0, b0 in runs:
-                if any(k in anc for k in range(a0, b0)):
-                    for k in range(a0, b0):
-                        if k not in Es and k not in anc:
-                            anc.add(k); grew = True
-            for k in sorted(anc, reverse=True):
-                for d in deps[k]:
-                    if d not in Es and d not in anc:
-                        anc.add(d); grew = True
-        desc = set()
-        for k in range(len(ops)):
-            if any(d in Es or d in desc for d in deps[k]):
-                desc.add(k)
-        if any(k in desc for k in anc):
-            return                                            # a group straddles the chain: leave this tape / sub-network per-op
-        level = {}
-        for k in sorted(Es):
-            level[k] = 1 + max((level[d] for d in deps[k] if d in Es), default=-1)
-        imgs = self._chain_imgs.setdefault(which, {})
-        G = int(os.environ.get("UZ_CHAIN_WGS" if fwd else "UZ_CHAIN_WGS_BWD", str(self.chain_wgs if fwd else self.chain_wgs_bwd)))
-        sub, flops = [], 0.0
-
-        def emit(k, code, p, i, f=(), lvl=None):
-            sub.append(dict(code=code, p=list(p), i=[int(v) for v in i], f=list(f), level=level[k] if lvl is None else lvl, orig=ops[k], k=k))
-
-        def image(wkey, mc, kc, cin, dgrad):
-            if wkey not in imgs:
-                imgs[wkey] = dict(mc=mc, kc=kc, cin=cin, dgrad=dgrad, bytes=self.L.uz_chain_packed_bytes(kc, mc), blocks=self.L.uz_chain_pack_blocks(kc, mc))
-            return ("chainimg", which, wkey)
-
-        def weight_key(w):
-            kind, wkey, offset = w
-            assert kind == "param" and offset == 0, w
-            return wkey
-
-        extra_levels = {}            # op index -> 1 when a slab-sum phase was put behind it (shifts everything that depends on it)
-        slab_of = {}
-        for k in sorted(Es, key=lambda k: (level[k], k)):
-            o = ops[k]
-            c, I, P = o["code"], o.i, o.p
-            if c == "UZ_OP_CONV_FWD":
-                _, cin, cout, N, H, W, _ = conv_dims(o)
-                x, w, bias, y = P("x", "w", "bias", "y")
-                if cin <= 4:
-                    emit(k, "UZ_CH_CONV3_SMALL", [x, w, bias, y], [cin, I("ctot_x"), cout, I("ctot_y"), N, H, W])
-                    continue
-                bk = bn_of_y.get(vkey(y))
-                S = self.L.uz_chain_conv_ksplit(cin, cout, N, H, W, G) if (bk in Es) else 1
-                wkey = weight_key(w)
-                slab = self.vec(wkey + ":chslab", S * N * cout * H * W) if S > 1 else None
-                if slab is not None:
-                    slab_of[vkey(y)] = (slab, S)
-                emit(k, "UZ_CH_CONV3", [x, image(wkey, cout, cin, cin, 0), bias if S == 1 else None, y if S == 1 else None, slab, P("x_amax"), P("w_amax")],
-                     [cin, I("ctot_x"), cout, I("ctot_y"), N, H, W, S, 0])
-                flops += 2.0 * N * H * W * cin * cout * 9
-                self._packs["fwd"].pop(wkey, None)          # the image replaces the per-tape LDS image of the split kernels
-            elif c == "UZ_OP_BN_RELU_FWD":
-                slab, S = slab_of.get(vkey(P("y")), (None, 1))
-                cbias = ops[ywriter[vkey(P("y"))]].p("bias") if S > 1 else None
-                emit(k, "UZ_CH_BN_FWD", [*P("y", "gamma", "beta", "running_mean", "running_var", "save", "a"), slab, P("a_amax"), cbias],
-                     [*I("C", "ctot_y", "ctot_a", "N"), I("H") * I("W"), I("relu"), S], o.f("eps", "momentum"))
-            elif c == "UZ_OP_AVGPOOL_FWD":
-                emit(k, "UZ_CH_AVGPOOL_FWD", P("x", "y", "x_amax", "y_amax"), I("C", "ctot_x", "ctot_y", "N", "H", "W"))
-            elif c == "UZ_OP_BILINEAR_FWD":
-                emit(k, "UZ_CH_BILINEAR_FWD", P("x", "y", "x_amax", "y_amax"), I("C", "ctot_x", "ctot_y", "N", "H", "W", "align_corners"))
-            elif c == "UZ_OP_LATENT_HEADS_FWD":
-                emit(k, "UZ_CH_HEADS_FWD", o["p"], [*I("cin", "ctot_h", "N"), I("H") * I("W"), I("act")])
-            elif c == "UZ_OP_BN_RELU_BWD":
-                slab, S = slab_of.get(("da",) + vkey(P("da")), (None, 1))
-                emit(k, "UZ_CH_BN_BWD", [*P("da", "y", "gamma", "save"), P("dy").view, *P("dgamma", "dbeta", "dbias", "dy_amax"), slab, P("beta")],
-                     [*I("C", "ctot_da", "ctot_y", "N"), I("H") * I("W"), I("relu"), S])
-            elif c == "UZ_OP_CONV_BWD_DATA":
-                _, cin, cout, N, H, W, _ = conv_dims(o)
-                acc, dy, dx = I("accumulate"), P("dy").view, P("dx")
-                wkey = weight_key(P("w"))
-                if cin <= 4:
-                    emit(k, "UZ_CH_CONV3_SMALL_BWD_DATA", [dy, P("w"), dx], [cin, I("ctot_dx"), cout, I("ctot_dy"), N, H, W, acc])
-                    continue
-                S = self.L.uz_chain_conv_ksplit(cout, cin, N, H, W, G)
-                folded = I("fold") == 3                           # the consumer's BatchNorm backward adds the slabs (the only reader of a dA this op alone writes)
-                slab = self.vec(wkey + ":chdslab", S * N * cin * H * W) if S > 1 else None
-                emit(k, "UZ_CH_CONV3", [dy, image(wkey, cin, cout, cin, 1), None, dx if S == 1 else None, slab, P("dy_amax"), P("w_amax")],
-                     [cout, I("ctot_dy"), cin, I("ctot_dx"), N, H, W, S, acc if S == 1 else 0])
-                flops += 2.0 * N * H * W * cout * cin * 9
-                if S > 1 and folded:
-                    slab_of[("da",) + vkey(dx)] = (slab, S)
-                elif S > 1:
-                    # other writers / readers of dx: a reduction phase of its own right behind the convolution
-                    extra_levels[k] = 1
-                    emit(k, "UZ_CH_SLAB_SUM", [slab, dx], [S, N, cin, I("ctot_dx"), H * W, acc], lvl=level[k] + 0.5)
-                self._packs["bwd"].pop(wkey, None)
-            elif c == "UZ_OP_AVGPOOL_BWD":
-                emit(k, "UZ_CH_AVGPOOL_BWD", P("dy", "dx"), I("C", "ctot_dy", "ctot_dx", "N", "H", "W", "accumulate"))
-            elif c == "UZ_OP_BILINEAR_BWD":
-                emit(k, "UZ_CH_BILINEAR_BWD", P("dy", "dx"), I("C", "ctot_dy", "ctot_dx", "N", "H", "W", "align_corners", "accumulate"))
-            elif c == "UZ_OP_LATENT_BWD":
-                h = ops[k + 1]
-                # (head a = the sigma head: LATENT_HEADS_BWD_DATA p = g_pre, g_mu, w_sigma, w_mu, dh)
-                emit(k, "UZ_CH_LATENT_HEADS_BWD", [*o["p"], *h.p("w_a", "w_b", "dh")],
-                     [*h.i("cin", "ctot_h", "N"), h.i("H") * h.i("W"), I("act"), h.i("accumulate")], lvl=level[k + 1])
-            elif c == "UZ_OP_LATENT_HEADS_BWD_DATA":
-                pass                                              # fused into the sub-op of the LATENT_BWD in front of it
-            else:
-                raise AssertionError(c)
-        # a slab-sum phase sits at level + 0.5: renumber the levels densely, keeping the order
-        if extra_levels:
-            # everything that depends (inside the set) on an op with a slab-sum must come after the half level: recompute levels with that op one deeper
-            lv2 = {}
-            for k in sorted(Es):
-                lv2[k] = max((lv2[d] + 1 + extra_levels.get(d, 0) for d in deps[k] if d in Es), default=0)
-            for e in sub:
-                e["level"] = lv2[e["k"]] + (1 if e["code"] == "UZ_CH_SLAB_SUM" else 0)
-                if e["code"] == "UZ_CH_LATENT_HEADS_BWD":
-                    e["level"] = lv2[e["k"] + 1]
-        sub.sort(key=lambda e: (e["level"], e["k"], e["code"] == "UZ_CH_SLAB_SUM"))
-        dense = {lv: n for n, lv in enumerate(sorted({e["level"] for e in sub}))}
-        for e in sub:
-            e["level"] = dense[e["level"]]
-        idx = len(self._chains)
-        self._chains.append(dict(sub=sub, which=which, n_wgs=G, net=net))
-        # access of the whole launch = the union of what its sub-ops touch (the packed images instead of the split kernels' ones)
-        acc_ops = []
-        for k in sorted(Es):
-            q = ops[k].clone()
-            if q["code"] in ("UZ_OP_CONV_FWD", "UZ_OP_CONV_BWD_DATA"):
-                q.set(p={"w_image": None})
-            acc_ops.append(q)
-        n_ph = 1 + max(e["level"] for e in sub)
-        chain_op = _ops.make("UZ_OP_CHAIN", p=[("chaintab", idx, "ops"), ("chaintab", idx, "phases"), ("chaintab", idx, "state")],
-                             i=[n_ph, G, len(sub)], gid=("chain", idx), _acc_ops=acc_ops, _which=which,
-                             _cost_s=n_ph * 12e-6 + flops / 100e12)   # (flops: the chain's 3 x 3 convolutions; first guess for the lane scheduler, tune_schedule measures it)
-        new_ops = [ops[k] for k in range(len(ops)) if k in anc] + [chain_op] + [ops[k] for k in range(len(ops)) if k not in anc and k not in Es]
-        ops[:] = new_ops
-        self.chain_info.setdefault(which, []).append(dict(net=net, ops=len(sub), phases=n_ph, convs=sum(e["code"] == "UZ_CH_CONV3" for e in sub), workgroups=G))
+        return _passes._b16_ok(self, o)
 
     def _chain_tables(self, idx):
-        """Device tables of chain `idx` (built once, when the arena exists): the sub-ops in phase order with their tile ranges, the
-        phase table, the barrier state."""
-        ch = self._chains[idx]
-        if "dev" in ch:
-            return ch["dev"]
-        codes = _ffi.chain_codes()
-        sub = ch["sub"]
-        arr = (_ffi.uz_chain_op * len(sub))()
-        phases, tile0, cur = [], 0, None
-        for k, e in enumerate(sub):
-            a = arr[k]
-            a.code = codes[e["code"]]
-            assert len(e["i"]) <= 16 and len(e["p"]) <= 12
-            for j, v in enumerate(e["i"]):
-                a.i[j] = int(v)
-            for j, v in enumerate(e["f"]):
-                a.f[j] = float(v)
-            for j, r in enumerate(e["p"]):
-                a.p[j] = self._resolve(r, 0)
-            nt = self.L.uz_chain_op_tiles(C.byref(a))
-            if nt <= 0:
-                raise RuntimeError(f"chain sub-op {e['code']} {e['i']} is not covered by uz_chain_run")
-            if e["level"] != cur:
-                cur, tile0 = e["level"], 0
-                phases.append([k, 0])
-            # the op's tiles are dealt to the workgroups round-robin from workgroup tile0 on: behind a short op the next one starts
-            # on the workgroups the first left idle
-            a.tile0, a.ntiles = tile0 % ch["n_wgs"], nt
-            tile0 += nt
-            phases[-1][1] += 1
-            e["tile0"], e["ntiles"] = a.tile0, nt
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone()
-        dev = dict(ops=raw.to(self.device), phases=torch.tensor(phases, dtype=torch.int32).reshape(-1).to(self.device),
-                   state=torch.zeros(self.L.uz_chain_state_bytes() // 4, dtype=torch.int32, device=self.device), n_phases=len(phases))
-        ch["dev"] = dev
-        return dev
+        return _chain_plan._chain_tables(self, idx)
 
     def chain_status(self, stream_ptr):
-        """0 when every chain launch of the last replay completed, else 1 + the phase whose grid barrier timed out (synchronises)."""
-        worst = 0
-        for idx, ch in enumerate(self._chains):
-            if "dev" in ch:
-                out = C.c_int(0)
-                _ffi.check(self.L.uz_chain_status(C.c_void_p(ch["dev"]["state"].data_ptr()), C.byref(out), C.c_void_p(stream_ptr)), "chain_status")
-                worst = max(worst, out.value)
-        return worst
+        return _chain_plan.chain_status(self, stream_ptr)
 
+    # ------------------------------------------------------------------ finalisation
     def finalize(self, want_backward=True):
         assert not self.finalized
         self.loss_scale = self.vec("loss_scale", 1)
@@ -1847,7 +1144,7 @@ class Plan:
                                p=[self.ptr_table(refs), ("gflat_keys", tuple(j[1] for j in part_jobs))],
                                i=[len(part_jobs), max(j[3] for j in part_jobs)])
                 self._dbias_jobs = []
-            jobs = self.__dict__.get("_wgrad_jobs", [])
+            jobs = self._wgrad_jobs
             if jobs:
                 # One launch for ALL layers.  (UZ_WGRAD_TABLE_CHUNK = n: one launch per n layers in backward order, each a scheduling group
                 # that is ready as soon as ITS layers' slabs are written - measured: 1 789 / 1 790 / 1 793 / 1 791 images/s for one table /
@@ -1879,10 +1176,10 @@ class Plan:
                 self._newgroup()
                 self._emit(self.bwd_ops, "UZ_OP_EVENT_RECORD", p=[("event", b), ("gflat_range", lo, hi)])
         self._bwd = []
-        self._split_storage_passes()
-        self._bn_offchain_pass()
-        self._b16_pass()
-        self._chain_pass()
+        _passes._split_storage_passes(self)
+        _passes._bn_offchain_pass(self)
+        _passes._b16_pass(self)
+        _chain_plan._chain_pass(self)
         # magnitude-bound slots: zero the forward-side slots and measure the parameter bound at the head of the forward tape,
         # zero the backward-side slots at the head of the backward tape (group 0 of each tape: everything else depends on it)
         self.n_amax_fwd = self.n_amax
@@ -1931,7 +1228,7 @@ class Plan:
                                           n=4 * _AMAX_FLOATS * (self.n_amax - self.n_amax_fwd), gid=head)]
         # arena layout
         off = 0
-        for slot in self.__dict__.get("_rev_slots", {}).values():
+        for slot in self._rev_slots.values():
             slot["off"] = off
             off += -(-slot["floats"] // _ALIGN) * _ALIGN
         for b in self.bufs:
@@ -2120,7 +1417,7 @@ class Plan:
         if kind == "ptrtab":
             return [x for q in self.ptr_tables[r[1]] for x in self._resources(q)]
         if kind == "packw":
-            return self._resources(self._packbuf[r[1]]) if r[1] in self._packbuf else [(("packw", r[1]), 0, 1)]      # (before finalize() lays the images out: _chain_pass)
+            return self._resources(self._packbuf[r[1]]) if r[1] in self._packbuf else [(("packw", r[1]), 0, 1)]      # (before finalize() lays the images out: _chain_plan._chain_pass)
         if kind == "chainimg":
             return self._resources(self._chain_imgbuf[r[1]]) if r[1] in self._chain_imgbuf else [(("chainimg", r[1]), 0, 1)]
         if kind == "chaintab":
@@ -2150,293 +1447,18 @@ class Plan:
             return []
         raise ValueError(r)
 
-    @staticmethod
-    def _op_cost(o):
-        """Rough duration (s) of one op on MI355X - only the RELATIVE sizes matter: the list scheduler
-        below uses them to decide which chains can share a lane."""
-        c = o["code"]
-        if "_cost_s" in o:
-            return o["_cost_s"]
-        if c in _ops.CONV_KIND:
-            kind, cin, cout, N, H, W, ks = conv_dims(o)
-            flop = 2.0 * N * H * W * cin * cout * ks * ks
-            # measured fp32-equivalent TFLOP/s per plane size at batch 32 (tools/op_profile.py), forward / data
-            # gradient and weight gradient; small channel counts and 1x1 kernels run far below these
-            px = N * H * W
-            table = ((262144, 180, 150), (65536, 190, 159), (16384, 148, 122), (4096, 97, 85), (1024, 37, 31), (256, 11, 9), (0, 3, 2.2))
-            rate = next((f if kind != 2 else w) for lim, f, w in table if px >= lim) * 1e12
-            if min(cin, cout) < 32 or ks == 1:
-                rate = min(rate, 20e12)
-            return flop / rate + 4e-6
-        if c == "UZ_OP_BN_RELU_FWD" and o.i("phase") == 1:
-            return 6e-6                                              # statistics from the convolution's partials: one small launch
-        if c in ("UZ_OP_BN_RELU_FWD", "UZ_OP_BN_RELU_BWD", "UZ_OP_RELU_BWD"):
-            C_, N, H, W = o.i("C", "N", "H", "W")
-            if c == "UZ_OP_BN_RELU_FWD":
-                return C_ * N * H * W * 12.0 / 4e12 + 10e-6
-            return C_ * N * H * W * 20.0 / 4e12 + 14e-6
-        if c in ("UZ_OP_AVGPOOL_FWD", "UZ_OP_AVGPOOL_BWD", "UZ_OP_BILINEAR_FWD", "UZ_OP_BILINEAR_BWD", "UZ_OP_NEAREST_FWD", "UZ_OP_NEAREST_BWD"):
-            C_, N, H, W = o.i("C", "N", "H", "W")
-            return C_ * N * H * W * 24.0 / 2e12 + 6e-6
-        return 6e-6
+    _op_cost = staticmethod(_sched._op_cost)
+    _op_cost_beside = staticmethod(_sched._op_cost_beside)
 
-    @staticmethod
-    def _op_cost_beside(o):
-        """Duration (s) of one op as the lane replay REALISES it beside the other lanes' kernels (round 5: fitted per op class to the
-        per-op lane traces profiles/r5_lane_trace_{fwd,bwd}.json of the headline configuration, tools/sched_calibrate.py prints the fit).
-        The isolated model above is 2 - 6x short for the small launches (a 7-us convolution takes 33 - 45 us beside a device-filling
-        kernel) and 1.4 - 10x long for the large ones: the list scheduler then queued off-critical weight gradients in front of a
-        critical chain on the same lane and the chain started 2 ms late."""
-        c = o["code"]
-        if "_cost_s" in o:
-            return o["_cost_s"]
-        m = Plan._op_cost(o) * 1e6
-        if c in ("UZ_OP_CONV_FWD", "UZ_OP_CONV_BWD_DATA"):
-            us = 28.0 + 0.62 * m
-        elif c == "UZ_OP_CONV_BWD_WEIGHT":
-            us = 25.0 + 0.70 * m
-        elif c == "UZ_OP_BN_RELU_FWD":
-            us = 20.0 + 0.50 * m
-        elif c in ("UZ_OP_BN_RELU_BWD", "UZ_OP_RELU_BWD"):
-            us = 25.0 + 0.80 * m
-        elif c in ("UZ_OP_AVGPOOL_FWD", "UZ_OP_AVGPOOL_BWD"):
-            us = 12.0 + 0.06 * m
-        elif c in ("UZ_OP_BILINEAR_FWD", "UZ_OP_BILINEAR_BWD", "UZ_OP_NEAREST_FWD", "UZ_OP_NEAREST_BWD"):
-            us = 18.0 + 0.42 * m
-        elif c == "UZ_OP_WGRAD_REDUCE_TABLE":
-            us = 8.0 + 0.0031 * o.i("total_blocks")       # HBM-bound: PHiSeg's 106 layers = 95 301 blocks take 300 us
-        elif c in ("UZ_OP_MEMSET",):
-            us = 8.0
-        elif c in ("UZ_OP_W3D_PERMUTE", "UZ_OP_AVGPOOL3D_FWD", "UZ_OP_AVGPOOL3D_BWD", "UZ_OP_DEPTH_LERP_FWD", "UZ_OP_DEPTH_LERP_BWD",
-                   "UZ_OP_NEAREST3D_FWD", "UZ_OP_NEAREST3D_BWD", "UZ_OP_ADD_VIEWS"):
-            # volume ops stream whole volumes: a flat 25 us was wrong by orders of magnitude (PHiSeg3D's static schedule, ADVICE r5)
-            us = 12.0 + Plan._vol_bytes(o) / 3.0e6                  # ~3 TB/s realised beside the other lanes' kernels
-        else:
-            us = 25.0
-        return us * 1e-6
-
-    @staticmethod
-    def _vol_bytes(o):
-        """Bytes a volume / view op moves (input + output once)."""
-        c = o["code"]
-        if c == "UZ_OP_W3D_PERMUTE":
-            return 8.0 * o.i("cout") * o.i("cin") * 27
-        if c == "UZ_OP_ADD_VIEWS":
-            C_, N, H, W = o.i("C", "N", "H", "W")
-            return 12.0 * C_ * N * H * W
-        C_, D, H, W = o.i("C", "D", "H", "W")
-        n = float(C_) * D * H * W
-        if c in ("UZ_OP_AVGPOOL3D_FWD", "UZ_OP_AVGPOOL3D_BWD"):
-            return 4.0 * n * (1.0 + 0.125)
-        if c in ("UZ_OP_DEPTH_LERP_FWD", "UZ_OP_DEPTH_LERP_BWD"):
-            return 4.0 * n * 3.0
-        return 4.0 * n * (1.0 + float(o.i("factor")) * o.i("factor") * o.i("factor_z"))          # nearest-neighbour 3-D
-
-    @staticmethod
-    def _op_heavy(o):
-        """True for ops that fill the chip on their own (only one of those is simulated in flight at a time)."""
-        c = o["code"]
-        if c in _ops.CONV_KIND:
-            _, cin, cout, N, H, W, _ = conv_dims(o)
-            return N * H * W >= 2048 and cin * cout >= 32 * 32      # measured: 512..8192 pixels all within 1 %
-        if c in ("UZ_OP_BN_RELU_FWD", "UZ_OP_BN_RELU_BWD", "UZ_OP_RELU_BWD"):
-            C_, N, H, W = o.i("C", "N", "H", "W")
-            return C_ * N * H * W >= 4.0e6
-        if c in ("UZ_OP_AVGPOOL_FWD", "UZ_OP_AVGPOOL_BWD", "UZ_OP_BILINEAR_FWD", "UZ_OP_BILINEAR_BWD", "UZ_OP_NEAREST_FWD", "UZ_OP_NEAREST_BWD"):
-            C_, N, H, W = o.i("C", "N", "H", "W")
-            return C_ * N * H * W >= 2.0e6
-        return False
+    def _hazard_deps(self, ops):
+        """Per op of `ops` (program order) the set of earlier ops it must follow."""
+        return _sched.hazard_deps([self._access(o) for o in ops])
 
     def _schedule(self, ops):
-        """Turns the tape into a DAG schedule for uz_graph_create_lanes and REORDERS `ops` in place.
-
-        1. Hazard analysis in program order: a group (one layer's forward, or one layer's backward;
-           its ops stay back to back) depends on every earlier group it has a RAW, WAR or WAW conflict
-           with (buffer channel ranges, gradient ranges, BN running buffers).
-        2. Event-driven list scheduling in simulated time (cost model above) on n_lanes lanes (a lane is a
-           scratch copy, so the groups of a lane stay ordered): among the groups that are ready, the one
-           with the longest remaining critical path starts first; at most ONE device-filling ("heavy")
-           group is in flight at a time, light groups start whenever a lane is free.  This staggers the
-           independent chains (posterior / prior encoders, likelihood branches) so that the latency-bound
-           deep levels of one run beside the device-filling layers of another, instead of both being
-           deep - and the chip idle - at the same time.
-        3. The tape is rewritten in simulated start order (a topological order of the DAG, so the
-           eager runner stays correct) and every group gets: its lane, and the cross-lane groups it
-           must wait for that are not already implied by its lane predecessor.
-        Returns the ctypes uz_sched array (indexed like the reordered ops)."""
-        n, K = len(ops), self.n_lanes
-        sched = (_ffi.uz_sched * max(n, 1))()
-        if n == 0:
-            return sched
-        groups = []                                         # [first, last] op index per group, program order
-        for k, o in enumerate(ops):
-            if groups and ops[groups[-1][1]]["gid"] == o["gid"]:
-                groups[-1][1] = k
-            else:
-                groups.append([k, k])
-        G = len(groups)
-        # ---- 1. hazards
-        hist = {}                                           # space -> list of [lo, hi, last_writer_gi, readers{gi}, accumulators{gi}]
-        deps = []
-        for gi, (a, b) in enumerate(groups):
-            reads, writes, accs = [], [], []
-            for o in ops[a:b + 1]:
-                r_, w_, a_ = self._access(o)
-                reads.extend(r_); writes.extend(w_); accs.extend(a_)
-            d = set()
-            for space, lo, hi in reads:                     # after the last writer and every accumulator since
-                for e in hist.get(space, ()):
-                    if e[0] < hi and lo < e[1]:
-                        if e[2] is not None:
-                            d.add(e[2])
-                        d.update(e[4])
-            for space, lo, hi in accs:                      # after the last writer and every reader since (not after other accumulators)
-                for e in hist.get(space, ()):
-                    if e[0] < hi and lo < e[1]:
-                        if e[2] is not None:
-                            d.add(e[2])
-                        d.update(e[3])
-            for space, lo, hi in writes:
-                for e in hist.get(space, ()):
-                    if e[0] < hi and lo < e[1]:
-                        if e[2] is not None:
-                            d.add(e[2])
-                        d.update(e[3])
-                        d.update(e[4])
-            d.discard(gi)
-            deps.append(d)
-            for space, lo, hi in reads:
-                for e in hist.setdefault(space, []):
-                    if e[0] < hi and lo < e[1]:
-                        e[3].add(gi)
-                hist[space].append([lo, hi, None, {gi}, set()])
-            for space, lo, hi in accs:
-                for e in hist.setdefault(space, []):
-                    if e[0] < hi and lo < e[1]:
-                        e[4].add(gi)
-                hist[space].append([lo, hi, None, set(), {gi}])
-            for space, lo, hi in writes:
-                lst = hist.setdefault(space, [])
-                keep = [e for e in lst if not (lo <= e[0] and e[1] <= hi)]     # fully covered entries are superseded
-                keep.append([lo, hi, gi, set(), set()])
-                hist[space] = keep
-        # ---- 2. list scheduling in simulated time
-        # UZ_SCHED_COST: "alone" = the isolated-launch model, "beside" = the model fitted to the lane replay's realised durations
-        cmodel = os.environ.get("UZ_SCHED_COST", self.__dict__.get("sched_cost", "alone"))
-        assert cmodel in ("alone", "beside"), cmodel
-        op_cost = self._op_cost_beside if cmodel == "beside" else self._op_cost
-        cost = [sum((o["cost_us"] * 1e-6 if "cost_us" in o else op_cost(o)) for o in ops[a:b + 1]) for a, b in groups]    # cost_us: measured (tune_schedule)
-        succ = [[] for _ in range(G)]
-        indeg = [len(d) for d in deps]
-        for gi, d in enumerate(deps):
-            for e in d:
-                succ[e].append(gi)
-        ready_at = [0.0] * G
-        ready = [gi for gi in range(G) if indeg[gi] == 0]
-        free = [0.0] * K
-        tail = [None] * K
-        finish = [0.0] * G
-        order, lane_of = [], [None] * G
-        # one device-filling group at a time (critical path first); light groups start whenever a lane is free
-        # UZ_SCHED_HEAVY: "r4" = the round-4 rule (any op of the group above the size thresholds of _op_heavy), a number = groups whose
-        # modelled duration reaches that many microseconds, "off" = no group is heavy (plain critical-path list scheduling)
-        hmode = os.environ.get("UZ_SCHED_HEAVY", self.__dict__.get("sched_heavy", "r4"))
-        if hmode == "r4":
-            heavy = [any(self._op_heavy(o) for o in ops[a:b + 1]) for a, b in groups]
-        elif hmode == "off":
-            heavy = [False] * G
-        else:
-            heavy = [c >= float(hmode) * 1e-6 for c in cost]
-        # (round 5, measured under the lane replay and removed - commit 0cbd7b7 has the code: device-filling groups on a lane of their own
-        #  -7 %, weight-gradient-only groups on a low-priority lane -11 %, heavy weight gradients deferred behind the data-gradient chain -2 %;
-        #  profiles/NOTES_r5.md section 3)
-        blevel = [0.0] * G
-        for gi in reversed(range(G)):
-            blevel[gi] = cost[gi] + max((blevel[sg] for sg in succ[gi]), default=0.0)
-        for gi, (a, b) in enumerate(groups):
-            if any(o["code"] == "UZ_OP_EVENT_RECORD" for o in ops[a:b + 1]):
-                blevel[gi], cost[gi] = 1e9, 1e-7      # bucket-final markers cost nothing and must fire the moment their bucket is done
-                # ... and so must the bucket's deferred reductions (slab / bias-row tables): they are the last writers of the bucket, they
-                # have no other successor, and left at their own bottom level the list scheduler runs them LAST - all buckets final at 98 %
-                # of the tape, nothing of the exchange overlapped (headline plan under the round-5 cost model; 84 % under the old one)
-                for d in deps[gi]:
-                    if any(o["code"] in ("UZ_OP_WGRAD_REDUCE_TABLE", "UZ_OP_CHAN_SUM_TABLE") for o in ops[groups[d][0]:groups[d][1] + 1]):
-                        blevel[d] = 1e8
-        t, running = 0.0, []
-        while len(order) < G:
-            running = [(f, g) for f, g in running if f > t + 1e-12]
-            busy_lanes = {lane_of[g] for _, g in running}
-            heavy_busy = any(heavy[g] for _, g in running)
-            started = False
-            for gi in sorted((g for g in ready if ready_at[g] <= t + 1e-12), key=lambda g: (-blevel[g], g)):
-                lanes_free = [l for l in range(K) if l not in busy_lanes]
-                if not lanes_free or (heavy[gi] and heavy_busy):
-                    continue
-                pref = [l for l in lanes_free if tail[l] is not None and tail[l] in deps[gi]]
-                lane = pref[0] if pref else min(lanes_free, key=lambda l: (free[l], l))
-                lane_of[gi] = lane
-                finish[gi] = t + cost[gi]
-                free[lane] = finish[gi]
-                tail[lane] = gi
-                order.append(gi)
-                ready.remove(gi)
-                running.append((finish[gi], gi))
-                busy_lanes.add(lane)
-                heavy_busy = heavy_busy or heavy[gi]
-                started = True
-                for sgi in succ[gi]:
-                    indeg[sgi] -= 1
-                    ready_at[sgi] = max(ready_at[sgi], finish[gi])
-                    if indeg[sgi] == 0:
-                        ready.append(sgi)
-            if not started:
-                nxt = [f for f, _ in running] + [ready_at[g] for g in ready if ready_at[g] > t + 1e-12]
-                assert nxt, "dependency cycle in the tape"
-                t = min(nxt)
-        assert len(order) == G, "dependency cycle in the tape"
-        # ---- 3. rewrite the tape in schedule order, compute waits
-        new_ops, first, last = [], [0] * G, [0] * G
-        for gi in order:
-            a, b = groups[gi]
-            first[gi] = len(new_ops)
-            new_ops.extend(ops[a:b + 1])
-            last[gi] = len(new_ops) - 1
-        ops[:] = new_ops
-        sched = (_ffi.uz_sched * max(n, 1))()
-        anc = [0] * G                                       # bitset of transitive predecessors (incl. lane order)
-        ltail = [None] * K
-        for gi in order:
-            lane = lane_of[gi]
-            mask = 0
-            for d in deps[gi]:
-                mask |= anc[d] | (1 << d)
-            implied = 0
-            if ltail[lane] is not None:
-                implied = anc[ltail[lane]] | (1 << ltail[lane])
-                mask |= implied
-            per_lane = {}
-            for d in deps[gi]:
-                if lane_of[d] != lane and not (implied >> d) & 1:
-                    cur = per_lane.get(lane_of[d])
-                    if cur is None or first[d] > first[cur]:
-                        per_lane[lane_of[d]] = d
-            waits = list(per_lane.values())
-            waits = [d for d in waits if not any(d != e and (anc[e] >> d) & 1 for e in waits)]
-            anc[gi] = mask
-            ltail[lane] = gi
-            k0 = first[gi]
-            sched[k0].n_wait = len(waits)
-            for w, d in enumerate(sorted(waits, key=lambda d: first[d])):
-                sched[k0].wait[w] = last[d]
-                sched[last[d]].signal = 1
-            for k in range(first[gi], last[gi] + 1):
-                sched[k].lane = lane
-                ops[k]["lane"] = lane
-        # the scheduled DAG, for diagnostics (tools/critical_path.py): per group in schedule order its op range, lane and predecessors
-        pos = {gi: n_ for n_, gi in enumerate(order)}
-        self.__dict__.setdefault("dag", {})[id(ops)] = [dict(first=first[gi], last=last[gi], lane=lane_of[gi], deps=sorted(pos[d] for d in deps[gi]),
-                                                              sim_start=finish[gi] - cost[gi], sim_cost=cost[gi], blevel=blevel[gi])
-                                                         for gi in order]
+        """Lane schedule of tape `ops` (_sched.schedule: REORDERS `ops` in place); the environment overrides the plan's two settings."""
+        cost_model = os.environ.get("UZ_SCHED_COST", self.sched_cost)
+        heavy_mode = os.environ.get("UZ_SCHED_HEAVY", self.sched_heavy)
+        sched, self.dag[id(ops)] = _sched.schedule(ops, self._access, self.n_lanes, cost_model, heavy_mode)
         return sched
 
     # ------------------------------------------------------------------ execution helpers
@@ -2485,3 +1507,6 @@ class _ScratchView:
         self.nb = None
         self.view = None          # a buffer of its own instead of the lane's scratch (decoupled weight gradients, see _conv_bwd)
         self.zkey = None          # volume units: the zero-bordered scratch class (slices, floats per slice) this dy lives in
+
+
+from . import _chain_plan, _passes      # noqa: E402  (down here: both import View, _ScratchView and _buf_of from this module)
