@@ -47,6 +47,20 @@ def test_plan_builds_schedules_and_rejects_what_the_reference_rejects():
         net.forward(torch.zeros(1, 4, 16, 32, 32), torch.zeros(1, 3, 16, 32, 32))
 
 
+@pytest.mark.parametrize("reversible", [False, True])
+@pytest.mark.parametrize("filters,latent_levels", [([8, 16, 16], 3), ([8, 16, 16], 2), ([8, 16, 16, 16], 2)])   # level difference 0, 1, 2
+def test_every_level_layout_builds_its_train_eval_and_decode_plans(filters, latent_levels, reversible):
+    from unet_zoo_amd.models.phiseg3D import PHISeg3D, phiseg3d_spec
+    cin, K, dhw = 4, 3, (16, 32, 32)
+    net = PHISeg3D(cin, K, filters, latent_levels=latent_levels, reversible=reversible, device="cpu")
+    assert len(phiseg3d_spec(cin, K, filters, latent_levels, reversible)) == len(net.state_dict())
+    for args in ((True, True), (False, False), (False, False, True)):           # train, eval, decode
+        io = net._build(*dhw, *args).io
+        assert [(v.N, v.C, v.H, v.W) for v in io["s"]] == [(dhw[0], K, dhw[1], dhw[2])] * latent_levels
+        if not args[2:]:
+            assert len(io["eps"]) == 2 * latent_levels
+
+
 def test_bf16_storage_pass_marks_buffers_and_operands_consistently(monkeypatch):
     """Plan._b16_pass (BASELINE config 5, bf16 STORAGE): which volume tensors become 2-byte buffers is decided per buffer from its
     readers and writers; every op then carries one format bit per tensor operand (i[13]).  Checked here on the CPU: the bits of every

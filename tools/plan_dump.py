@@ -32,7 +32,8 @@ def golden_meta(root, name):
 
 
 def configurations(root):
-    """[(name, dict(model=..., env=..., mode=..., dp=..., resched=...))]: `model` is (kind, constructor kwargs, _build args)."""
+    """[(name, dict(model=..., env=..., mode=..., dp=..., resched=..., method=...))]: `model` is (kind, constructor kwargs, arguments
+    of the builder `method`: _build, or PHISeg._build_predict)."""
     ps, us, pus, p3s = (golden_meta(root, n) for n in ("phiseg_small", "unet_small", "probunet_small", "phiseg3d_small"))
     models = {
         "unet": ("unet", dict(num_filters=[32, 64, 128, 192]), (32, 128, 128)),
@@ -52,10 +53,21 @@ def configurations(root):
     dp_small = ("phiseg", dict(num_filters=[4, 8, 8, 8, 8, 8, 8], image_size=(1, 64, 64)), (2, 64, 64, True, True))
     out = []
 
-    def add(name, model, env=None, mode=None, dp=None, resched=False):
-        out.append((name, dict(model=models[model] if isinstance(model, str) else model, env=env or {}, mode=mode, dp=dp, resched=resched)))
+    def add(name, model, env=None, mode=None, dp=None, resched=False, method="_build"):
+        out.append((name, dict(model=models[model] if isinstance(model, str) else model, env=env or {}, mode=mode, dp=dp, resched=resched, method=method)))
     for m in models:
         add(m, m)
+    # the hierarchical builder shared by PHISeg and PHISeg3D: 2-D reversible, the two predict() plans, and the 3-D level layouts
+    # with as many latent as resolution levels (l3) and with a level difference of two (d2); train / eval / decode / reversible each
+    add("phiseg_small_rev", (dp_small[0], dict(dp_small[1], reversible=True), dp_small[2]))
+    add("phiseg_small@trunk", ("phiseg", models["phiseg_small"][1], (2, 64, 64, "trunk")), method="_build_predict")
+    add("phiseg_small@draw", ("phiseg", models["phiseg_small"][1], (6, 64, 64, "draw")), method="_build_predict")
+    for tag, nf, lat in (("l3", [8, 16, 16], 3), ("d2", [8, 16, 16, 16], 2)):
+        kw = dict(ch=(4, 3), num_filters=nf, latent_levels=lat)
+        add(f"phiseg3d_{tag}", ("phiseg3d", kw, (16, 32, 32, True, True)))
+        add(f"phiseg3d_{tag}@eval", ("phiseg3d", kw, (16, 32, 32, False, False)))
+        add(f"phiseg3d_{tag}@decode", ("phiseg3d", kw, (16, 32, 32, False, False, True)))
+        add(f"phiseg3d_{tag}_rev", ("phiseg3d", dict(kw, reversible=True), (16, 32, 32, True, True)))
     for mode in (0, 1, 2, 3):
         for m in ("unet", "phiseg7", "probunet7", "phiseg_small", "phiseg3d_mid", "phiseg3d_tiny_rev"):
             add(f"{m}@math{mode}", m, mode=mode)
@@ -110,7 +122,7 @@ def build_plan(cfg, device):
         if cfg["dp"] is not None:
             buckets = dp.param_buckets(net._ptab) if cfg["dp"] == "default" else dp.param_buckets(net._ptab, target_floats=cfg["dp"])
             net._dp = type("S", (), dict(overlap=True, buckets=buckets))()
-        plan = net._build(*args)
+        plan = getattr(net, cfg["method"])(*args)
         if cfg["resched"]:
             # deterministic "measured" durations, then one reschedule() per tape (Engine.tune_schedule does this with real ones)
             for which in ("fwd", "bwd"):

@@ -52,6 +52,7 @@ class NativeModel(nn.Module):
         self._plans = {}
         self._cur = None
         self._dp_group = None
+        self._dp = None                     # dp.GradSync of set_data_parallel()
         self._use_graphs = False
         self._graphs = {}
         self._plans_mode = None             # convolution math mode the cached plans were built under (_plan)
@@ -104,7 +105,7 @@ class NativeModel(nn.Module):
         a caller that gets non-zero repeats the step it just ran from the state snapshot_step() saved (train_model.py does).
         Costs one stream synchronisation: meant for loops that synchronise per step anyway (the reference's scheduler does)."""
         flags = self.check_bounds()
-        if getattr(self, "_dp", None) is not None:
+        if self._dp is not None:
             from . import dp
             flags = dp.or_flags(flags, self._dp.group)          # ONE collective for the three bits (ADVICE round 4)
         if flags:
@@ -195,7 +196,7 @@ class NativeModel(nn.Module):
         plan.decouple_wgrad_px = self.decouple_wgrad_px
         plan.chain_px = self.chain_px
         plan.decouple_wgrad_prefixes = tuple(self.decouple_wgrad_prefixes)
-        dp = getattr(self, "_dp", None)
+        dp = self._dp
         if dp is not None and dp.overlap:
             plan.grad_buckets = list(dp.buckets)
         # Stream budget (measured, DESIGN.md section 2: five or more concurrently active hardware queues collapse a PHiSeg step from 16 to
@@ -323,7 +324,7 @@ class NativeModel(nn.Module):
         from ._plan import Plan
         from . import dp as _dp_mod
         grp = getattr(self, "_dp_group", None)
-        if getattr(self, "_dp", None) is None:
+        if self._dp is None:
             def allmax(v):
                 return [float(x) for x in v]
         else:                                             # data parallel: one schedule for all ranks (the bucket exchange order follows it)
@@ -407,7 +408,7 @@ class NativeModel(nn.Module):
         process group runs on nccl, torch.distributed collectives otherwise (gloo test double)."""
         from . import dp
         self._dp_group = group
-        if getattr(self, "_dp", None) is not None:
+        if self._dp is not None:
             self._dp.close()                   # communicator and communication stream of an earlier call (streams are a scarce resource: dp.GradSync.close)
         self._dp = dp.GradSync(self, None if group is True else group, backend=backend, overlap=overlap)
         self._plans.clear()                # plans built before this call carry no bucket events
@@ -436,7 +437,7 @@ class NativeModel(nn.Module):
         if prev is not None:
             gflat.add_(prev)
         self._post_backward(plan)
-        if getattr(self, "_dp", None) is not None:
+        if self._dp is not None:
             self._dp.sync(plan, serial=prev is not None)
         for key in plan.param_grads:
             p = self._pmap[key]
@@ -458,6 +459,13 @@ class NativeModel(nn.Module):
     def _loss_tensor(self, plan):
         return _TapeLoss.apply(self._anchor, self, plan)
 
+    def _loss_value(self, plan):
+        """The loss of the last forward pass: bound to the backward tape where autograd is on and the plan has one, else a plain value."""
+        if torch.is_grad_enabled() and plan.tapes["bwd"][1]:
+            return self._loss_tensor(plan)
+        plan.run("loss", self._stream())
+        return plan.tensor(plan.total).reshape(()).clone()
+
     def _bump_nbt(self, plan, which="bn_prefixes_nbt"):
         """num_batches_tracked += 1 for every BatchNorm the pass ran (uz_step_counters: one tiny launch of our own, no ATen
         index_add_ in the step)."""
@@ -475,7 +483,7 @@ class NativeModel(nn.Module):
         mixed into the Philox key: ranks that share a torch seed still draw different noise for their different shards."""
         st = self._rng_state_t
         if st is None:
-            rank = int(os.environ.get("RANK", "0")) if getattr(self, "_dp", None) is not None or int(os.environ.get("WORLD_SIZE", "1")) > 1 else 0
+            rank = int(os.environ.get("RANK", "0")) if self._dp is not None or int(os.environ.get("WORLD_SIZE", "1")) > 1 else 0
             seed = (torch.initial_seed() ^ (rank << 32) ^ (rank * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF
             st = torch.tensor([seed, 0], dtype=torch.int64, device=self.device)
             object.__setattr__(self, "_rng_state_t", st)

@@ -227,6 +227,7 @@ class Plan:
         self.bn_prefixes_nbt, self.bn_prefixes_nbt_loss, self.bn_prefixes_nbt_bwd, self.bn_prefixes_nbt_extra = [], [], [], []
         self._nbt_idx = {}                   # which of those lists -> its counters' indices on the device (NativeModel._bump_nbt)
         self._warm = set()                   # tapes that had their eager warm-up run before graph capture (NativeModel._run)
+        self.host = {}                       # what a model keeps with this plan between calls (device pointer tables, the noise span, predict() outputs)
         # filled by finalize(): the loss-scale cell, the bound-slot numbering, the arena and its layout, the pointer tables, the tapes
         self.loss_scale = self.loss_scale_t = None
         self._amax_remap = {}

@@ -224,13 +224,13 @@ class ProbabilisticUnet(NativeModel):
     def _fcomb_sample(self, plan, S):
         """The one uz_fcomb_sample_fwd launch of predict(): features, mu and sigma of the eval plan `plan` (forward has run) and the
         noise in the plan's predict buffers for S samples -> z and logits in those buffers."""
-        io, bufs = plan.io, plan._predict_bufs[S]
+        io, bufs = plan.io, plan.host["predict_bufs"][S]
         feat, mu, sigma = io["fcat"].slice(0, self.num_filters[0]), io["p_mu"], io["p"].sigma
         if any(v.buf.b16 or v.buf.packed for v in (feat, mu, sigma)):
             raise _ffi.UzError("predict(): the Fcomb input, mu or sigma is not kept as fp32 in this arithmetic mode")
-        tab = plan.__dict__.get("_fcomb_tab")
+        tab = plan.host.get("fcomb_tab")
         if tab is None:                                # the parameters never move: built once per plan
-            tab = plan._fcomb_tab = torch.tensor([plan._resolve(r) for r in self._fcomb_param_refs()], dtype=torch.int64, device=self.device)
+            tab = plan.host["fcomb_tab"] = torch.tensor([plan._resolve(r) for r in self._fcomb_param_refs()], dtype=torch.int64, device=self.device)
         _ffi.check(_ffi.lib().uz_fcomb_sample_fwd(plan._resolve(feat), feat.C, feat.Ctot, plan._resolve(mu), plan._resolve(sigma),
                                                   bufs["eps"].data_ptr(), tab.data_ptr(), self.no_convs_fcomb - 1, BN_EPS, self.latent_dim,
                                                   self.num_classes, feat.N, S, feat.H, feat.W, bufs["z"].data_ptr(), bufs["logits"].data_ptr(),
@@ -256,10 +256,10 @@ class ProbabilisticUnet(NativeModel):
         plan, dev = self._cur, self.device
         B, _, H, W = patch.shape
         L, K = self.latent_dim, self.num_classes
-        bufs = plan.__dict__.setdefault("_predict_bufs", {}).get(S)
+        bufs = plan.host.setdefault("predict_bufs", {}).get(S)
         if bufs is None:
             logits = torch.empty(S * B, K, H, W, device=dev)
-            bufs = plan._predict_bufs[S] = dict(eps=torch.empty(S * B, L, device=dev), z=torch.empty(S * B, L, device=dev), logits=logits,
+            bufs = plan.host["predict_bufs"][S] = dict(eps=torch.empty(S * B, L, device=dev), z=torch.empty(S * B, L, device=dev), logits=logits,
                                                 s_tab=torch.tensor([logits.data_ptr()], dtype=torch.int64, device=dev))
         if eps is None:
             self._fill_normal(bufs["eps"])
@@ -306,11 +306,7 @@ class ProbabilisticUnet(NativeModel):
             self._fill_normal(T(plan.io["eps"]))
         else:
             T(plan.io["eps"]).copy_(eps.reshape(N, self.latent_dim, 1, 1))
-        if torch.is_grad_enabled() and plan.tapes["bwd"][1]:
-            total = self._loss_tensor(plan)
-        else:
-            plan.run("loss", self._stream())
-            total = T(plan.total).reshape(()).clone()
+        total = self._loss_value(plan)
         if self.training:
             self._bump_nbt(plan, "bn_prefixes_nbt_loss")
         terms = T(plan.io["terms"]).reshape(-1).clone()

@@ -151,7 +151,7 @@ class Unet(NativeModel):
             raise RuntimeError("call forward() before loss()")
         N, _, H, W = plan.tensor(plan.io["mask"]).shape
         plan.tensor(plan.io["mask"]).copy_(mask.reshape(N, 1, H, W))
-        if torch.is_grad_enabled():
+        if torch.is_grad_enabled():         # not NativeModel._loss_value: the loss stays bound to the tape even where that is empty (reversible, eval)
             return self._loss_tensor(plan)
         plan.run("loss", self._stream())
         return plan.tensor(plan.total).reshape(()).clone()
