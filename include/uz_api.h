@@ -416,6 +416,24 @@ int uz_batch_repeat_fwd(const float* x, int C, int CtotX, float* y, int CtotY,
  * as np.argmax does.  1 <= K <= 8.  soft (S*B,K,H,W), labels (S*B,H,W), mean_label (B,H,W) and entropy (B,H,W) are nullable.   */
 int uz_sample_stats(const float* const* s_ptrs, int L, int K, int B, int S, int H, int W,
                     float* soft, uint8_t* labels, float* mean_soft, uint8_t* mean_label, float* entropy, void* stream);
+/* The same statistics for S samples of ONE volume that arrive one after another (PHISeg3D.predict; csrc/predict.hip), read from the
+ * L level logits at their own resolution - the nearest resize to the full volume is never materialised.
+ * uz_vol_sample_accum, one sample:
+ *   s_ptrs, ctot, f, fz   HOST arrays of L entries: level l is a volume [D / fz[l]][ctot[l]][H / f[l]][W / f[l]] (Plan.vol layout; the
+ *                         pointer addresses real slice 0, classes are its channels 0 .. K-1, ctot[l] >= K); voxel (od, oy, ox) reads
+ *                         (od / fz, oy / f, ox / f), the index of uz_nearest3d_fwd.  The inputs are not written.
+ *   labels  (D, H, W) uint8, soft (K, D, H, W) fp32 or null: this sample's argmax (first maximum) and softmax, dense
+ *   acc     (K, D, H, W) fp64: the running sum of the samples' probabilities, ASSIGNED when first != 0, added to otherwise
+ * The logits are summed in fp32 in the level order of uz_sample_stats, everything behind the sum is fp64.
+ * uz_vol_sample_finish: p = acc / S -> mean_soft (K, D, H, W) fp32, mean_label (D, H, W) uint8 = first maximum of the unrounded p,
+ * entropy (D, H, W) fp32 = -sum_k p_k ln p_k (a term with p_k = 0 is 0); mean_label and entropy are nullable.
+ * Fed S samples in the order s = 0 .. S-1, the pair gives bit for bit what uz_sample_stats gives on the resized levels with B = 1 and
+ * H W := D H W.  1 <= K <= 8, 1 <= L <= 8, D H W < 2^31; a null pointer, a factor below 1, a size that is not level size x factor and
+ * ctot < K are errors.  One voxel per thread, any shape and alignment.                                                           */
+int uz_vol_sample_accum(const float* const* s_ptrs, const int* ctot, const int* f, const int* fz, int L, int K, int D, int H, int W,
+                        uint8_t* labels, float* soft, double* acc, int first, void* stream);
+int uz_vol_sample_finish(const double* acc, int K, int S, int D, int H, int W,
+                         float* mean_soft, uint8_t* mean_label, float* entropy, void* stream);
 /* Fcomb (probabilistic_unet.py:185-199) in eval mode for S latent draws per image, features read once (ProbabilisticUnet.predict;
  * csrc/fcomb.hip).
  *   feat      (B, C of CtotF, H, W), C == 32

@@ -11,10 +11,15 @@
             (the harness loop gives S identical maps for this model, so it is no way to distinct samples)
   and `fcomb_ms`: uz_fcomb_sample_fwd alone on predict's buffers, the kernel's own share of predict
 
-Both draw their noise on the device.  Per S the two are warmed up, then timed alternately `--repeats` times, each call between two
+--model phiseg3d (PHISeg3D at the volume setting of bench.py: filters 32/64/128/192/192, 4 channels, 3 classes, one 128 x 128 x 64 volume):
+  predict : net.predict(patch, n_samples=S)                       - trunk plan once, S x (noise, draw plan, uz_vol_sample_accum), uz_vol_sample_finish
+  parent  : S x (net.forward(patch, zeros, training=False) + accumulate_output(use_softmax=True) + argmax), then the mean in torch
+  and `accum_ms` / `finish_ms`: the two kernels alone on predict's buffers, with the bytes they move and the GB/s that makes
+
+All draw their noise on the device.  Per S the two are warmed up, then timed alternately `--repeats` times, each call between two
 torch.cuda.Event records on the current stream; the figures are the medians, with the fastest and slowest call beside them.
 Before timing, the two paths run once on the SAME noise and the largest difference of their level logits is printed.
-Prints one JSON line per S.  usage: python tools/bench_predict.py [--model phiseg|probunet] [--samples 16 100] [--repeats 30] [--warmup 5] [--graphs 1]"""
+Prints one JSON line per S.  usage: python tools/bench_predict.py [--model phiseg|probunet|phiseg3d] [--samples 16 100] [--repeats 30] [--warmup 5] [--graphs 1]"""
 import argparse
 import ctypes as C
 import json
@@ -32,6 +37,7 @@ from unet_zoo_amd.models.probabilistic_unet import ProbabilisticUnet  # noqa: E4
 from unet_zoo_amd.synthetic import synthetic_batch  # noqa: E402
 
 FILTERS = [32, 64, 128, 192, 192, 192, 192]
+FILTERS3D, DHW3D = [32, 64, 128, 192, 192], (128, 128, 64)        # bench.py --model phiseg3d
 
 
 def timed(fn):
@@ -102,9 +108,82 @@ def probunet(args, dev):
                               max_logit_diff_same_noise=diff, bound_flags=flags, device=torch.cuda.get_device_name(0))), flush=True)
 
 
+def phiseg3d(args, dev):
+    import torch.nn.functional as F
+    from unet_zoo_amd.models.phiseg3D import PHISeg3D
+    (D, H, W), Cin, K, nl = DHW3D, 4, 3, 5
+    n = D * H * W
+    torch.manual_seed(1)
+    net = PHISeg3D(Cin, K, FILTERS3D, latent_levels=nl, image_size=(Cin, D, H, W))
+    with torch.no_grad():                          # running statistics away from (0, 1): BatchNorm is then no identity to either route
+        net._ptab.bflat.uniform_(0.5, 1.5)
+    net.eval()
+    net.enable_graphs(bool(args.graphs))
+    g = torch.Generator(device=dev).manual_seed(5)
+    patch = (torch.randn(1, Cin, D, H, W, generator=g, device=dev) * 0.25).clamp_(-0.5, 0.5)
+    zeros = torch.zeros(1, K, D, H, W, device=dev)
+    lib, st = _ffi.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    with torch.no_grad():
+        eps = [torch.randn(1, 2, D >> (4 - k), H >> (4 - k), W >> (4 - k), generator=g, device=dev) for k in range(nl)]
+        lv = net.predict(patch, n_samples=1, eps=eps, return_levels=True).levels
+        ref = net.forward(patch, zeros, training=False, eps=eps + eps)
+        diff = max(float((F.interpolate(a[0], size=[D, H, W], mode="nearest") - b).abs().max()) for a, b in zip(lv, ref))
+        del lv, ref
+    for S in args.samples:
+        sink = {}
+
+        def predict():
+            sink["p"] = net.predict(patch, n_samples=S)
+
+        def parent():
+            labels, acc = [], None
+            for _ in range(S):
+                soft = net.accumulate_output(net.forward(patch, zeros, training=False), use_softmax=True)
+                labels.append(torch.argmax(soft, dim=1))
+                acc = soft if acc is None else acc + soft
+            sink["q"] = (labels, acc / S)
+
+        with torch.no_grad():
+            for _ in range(args.warmup):
+                predict(), parent()
+            torch.cuda.synchronize()
+            tp, tq, ta, tf = [], [], [], []
+            for _ in range(args.repeats):
+                tp.append(timed(predict))
+                tq.append(timed(parent))
+            # the two kernels alone: the launches predict() makes, on the buffers its last call left (first = 0: the sum is read and written)
+            draw = net._plans[("draw", D, H, W)]
+            host = net._predict_state(draw, D, H, W)
+            labels = torch.empty(n, dtype=torch.uint8, device=dev)
+            mean_soft, mean_label, entropy = torch.empty(K * n, device=dev), torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, device=dev)
+
+            def accum():
+                _ffi.check(lib.uz_vol_sample_accum(host["ptrs"], host["ctot"], host["f"], host["fz"], nl, K, D, H, W, labels.data_ptr(), None,
+                                                   host["acc"].data_ptr(), 0, st), "vol_sample_accum")
+
+            def finish():
+                _ffi.check(lib.uz_vol_sample_finish(host["acc"].data_ptr(), K, S, D, H, W, mean_soft.data_ptr(), mean_label.data_ptr(),
+                                                    entropy.data_ptr(), st), "vol_sample_finish")
+            for _ in range(args.warmup):
+                accum(), finish()
+            for _ in range(args.repeats):
+                ta.append(timed(accum))
+                tf.append(timed(finish))
+        flags = net.check_bounds()
+        accum_bytes = sum(4 * K * (n >> (3 * l)) for l in range(nl)) + 2 * 8 * K * n + n          # levels read, sum read + written, labels
+        finish_bytes = 8 * K * n + 4 * K * n + n + 4 * n                                         # sum read; mean_soft, mean_label, entropy written
+        print(json.dumps(dict(bench="predict", model="phiseg3d", filters=FILTERS3D, dhw=[D, H, W], samples=S, graphs=args.graphs, repeats=args.repeats,
+                              conv_math=lib.uz_get_conv_math(), predict_ms=stats(tp), parent_ms=stats(tq),
+                              speedup=round(statistics.median(tq) / statistics.median(tp), 3), accum_ms=stats(ta), finish_ms=stats(tf),
+                              accum_bytes=accum_bytes, finish_bytes=finish_bytes,
+                              accum_gbs=round(accum_bytes / statistics.median(ta) / 1e6, 1), finish_gbs=round(finish_bytes / statistics.median(tf) / 1e6, 1),
+                              draw_ops=len(draw.fwd_ops), max_logit_diff_same_noise=diff, bound_flags=flags,
+                              device=torch.cuda.get_device_name(0))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=["phiseg", "probunet"], default="phiseg")
+    ap.add_argument("--model", choices=["phiseg", "probunet", "phiseg3d"], default="phiseg")
     ap.add_argument("--samples", type=int, nargs="+", default=[16, 100])
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--size", type=int, default=128)
@@ -117,6 +196,8 @@ def main():
     dev = torch.device("cuda", 0)
     if args.model == "probunet":
         return probunet(args, dev)
+    if args.model == "phiseg3d":
+        return phiseg3d(args, dev)
     B, hw = args.batch, args.size
     torch.manual_seed(1)
     net = PHISeg(1, 2, FILTERS, latent_levels=5, image_size=(1, hw, hw))

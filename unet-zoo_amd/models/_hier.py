@@ -141,9 +141,9 @@ class HierarchicalModel(NativeModel):
             zs.append(z_override[k] if z_override is not None else lat.z)
         return lats, zs
 
-    def _likelihood(self, plan, zs, full):
+    def _likelihood(self, plan, zs, full, resize=True):
         """zs in draw order (k = 0 deepest), full: the size of the image / volume.  Returns the level logits resized to `full` and
-        as the s_layers give them, both by level (index 0 finest)."""
+        as the s_layers give them, both by level (index 0 finest).  resize=False emits no resize op and returns None for the first."""
         nf, L, root = self.num_filters, self._L, "likelihood"
         diff, depth = self._R - L, self.rev_depths[1]
         cats, post_c = {}, [None] * L
@@ -173,8 +173,38 @@ class HierarchicalModel(NativeModel):
         for k in range(L):
             lvl = L - 1 - k
             s_in[lvl] = plan.conv_bare(post_c[lvl], f"{root}.s_layer.{k}.convolution.0.convolution.0")
-            s[lvl] = self._nearest_full(plan, s_in[lvl], full, f"{root}.s{lvl}")
-        return s, s_in
+            if resize:
+                s[lvl] = self._nearest_full(plan, s_in[lvl], full, f"{root}.s{lvl}")
+        return (s if resize else None), s_in
+
+    def _build_predict_plan(self, N, full, part, resize=True):
+        """The two plans of predict() at plan batch N for an image / volume of size `full`, both with eval-mode BatchNorm, fp32 storage
+        and no loss or backward tape (_passes._b16_pass leaves a plan that is not bn_training alone, so neither is ever in bf16
+        storage).  part = "trunk": patch -> the prior's contracting path (nothing in it depends on the noise).  part = "draw": the
+        prior's latent path and the likelihood; the skip slices of its concat buffers and the deepest feature map are plan inputs that
+        predict() fills from the trunk plan (no producer of this plan keeps a magnitude bound for them, so Plan.amax_in answers None
+        for the mixed buffers and the split convolutions measure those tensors themselves).  io["feats"] lists the hand-over views,
+        levels R-L .. R-2 and the deepest, in the same order in both plans.  resize=False: the draw plan ends at the un-resized level
+        logits io["s_in"] and holds no resize op (io["s"] is None)."""
+        nf, R, L, root = self.num_filters, self._R, self._L, "prior"
+        plan = self._new_plan(N, False)
+        plan.bn_prefixes_nbt = []
+        io = {}
+        if part == "trunk":
+            io["patch"] = self._new_buf(plan, "patch", self.input_channels, full, requires_grad=False)
+            skips, pre = self._contracting(plan, root, io["patch"])
+        else:
+            io["eps"] = self._latent_bufs(plan, "eps", L, full)
+            skips = {i: self._new_buf(plan, f"{root}.cat{i}", 2 * nf[0] + nf[i], tuple(s >> i for s in full), requires_grad=False)
+                     for i in range(R - L, R - 1)}
+            pre = self._new_buf(plan, f"{root}.deepest", nf[R - 1], tuple(s >> (R - 1) for s in full), requires_grad=False)
+            io["prior"], io["prior_z"] = self._latent_path(plan, root, skips, pre, io["eps"], None, True)
+            io["s"], io["s_in"] = self._likelihood(plan, io["prior_z"], full, resize)
+        io["feats"] = [skips[i].slice(2 * nf[0], nf[i]) for i in range(R - L, R - 1)] + [pre]
+        plan.total = plan.vec("total", 1)
+        plan.finalize(want_backward=False)
+        plan.io = io
+        return plan
 
     def _build_plan(self, N, full, training, bn_training, decode_only):
         """The plan of forward() + loss() at plan batch N for an image / volume of size `full`; decode_only: the likelihood alone on

@@ -34,7 +34,8 @@ class Prediction:
     """What PHISeg.predict returns for S samples of B images: labels (S, B, H, W) uint8, mean_soft (B, K, H, W) - the mean class
     probabilities over the samples -, mean_label (B, H, W) uint8 = argmax of mean_soft, entropy (B, H, W) of mean_soft (natural log),
     levels - the five level logits (S * B, K, H, W) as views of the plan's buffers, valid until the next predict() of that shape -
-    and soft (S, B, K, H, W), the per-sample probabilities, or None unless asked for."""
+    and soft (S, B, K, H, W), the per-sample probabilities, or None unless asked for.  PHISeg3D.predict returns the same object for one
+    volume, with (D, H, W) in the place of (H, W) and other `levels` (see there)."""
     __slots__ = ("labels", "mean_soft", "mean_label", "entropy", "levels", "soft")
 
     def __init__(self, labels, mean_soft, mean_label, entropy, levels, soft=None):
@@ -95,32 +96,12 @@ class PHISeg(HierarchicalModel):
         return self._build_plan(N, (H, W), training, bn_training, decode_only)
 
     def _build_predict(self, N, H, W, part):
-        """The two plans of predict(), both with eval-mode BatchNorm and no loss or backward tape.  part = "trunk": patch -> the
-        prior's contracting path at the batch of the images (nothing in it depends on the noise).  part = "draw": the prior's latent
-        path and the likelihood at the batch of images x samples; the skip slices of its concat buffers and the deepest feature map
-        are plan inputs that predict() fills from the trunk plan (no producer of this plan keeps a magnitude bound for them, so
-        Plan.amax_in answers None for the mixed buffers and the split convolutions measure those tensors themselves).
-        io["feats"] lists the five hand-over views, levels 2 .. 5 and the deepest, in the same order in both plans."""
+        """The two plans of predict() (HierarchicalModel._build_predict_plan): part = "trunk" at the batch of the images, part = "draw"
+        at the batch of images x samples, ending at the five level logits resized to the image.  io["feats"] lists the five hand-over
+        views, levels 2 .. 5 and the deepest, in the same order in both plans."""
         if H % 64 or W % 64:
             raise ValueError("PHISeg needs H and W divisible by 64 (7 resolution levels)")
-        nf, root = self.num_filters, "prior"
-        plan = self._new_plan(N, False)
-        plan.bn_prefixes_nbt = []
-        io = {}
-        if part == "trunk":
-            io["patch"] = plan.buf("patch", self.input_channels, H, W, requires_grad=False)
-            skips, pre = self._contracting(plan, root, io["patch"])
-        else:
-            io["eps"] = self._latent_bufs(plan, "eps", LAT_LEVELS, (H, W))
-            skips = {i: plan.buf(f"{root}.cat{i}", 2 * nf[0] + nf[i], H >> i, W >> i, requires_grad=False) for i in range(2, 6)}
-            pre = plan.buf(f"{root}.deepest", nf[RES_LEVELS - 1], H >> (RES_LEVELS - 1), W >> (RES_LEVELS - 1), requires_grad=False)
-            io["prior"], io["prior_z"] = self._latent_path(plan, root, skips, pre, io["eps"], None, True)
-            io["s"], _ = self._likelihood(plan, io["prior_z"], (H, W))
-        io["feats"] = [skips[i].slice(2 * nf[0], nf[i]) for i in range(2, 6)] + [pre]
-        plan.total = plan.vec("total", 1)
-        plan.finalize(want_backward=False)
-        plan.io = io
-        return plan
+        return self._build_predict_plan(N, (H, W), part)
 
     # ------------------------------------------------------------------ reference API
     def forward(self, patch, mask, training=True, eps=None):

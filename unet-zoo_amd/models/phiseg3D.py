@@ -13,10 +13,15 @@ First slice, with these limits stated up front:
   * the reference's own forward raises at its last line (:398 hands a 2-element `size` to a 5-D `interpolate`); the evident
     intent - nearest resize of every level to the full volume - is what runs here, and parity is pinned on everything up to
     the un-resized level logits `s_in` (Posterior, prior, Likelihood), which the reference does execute.
+Beyond the reference: predict(patch, n_samples) - samples, mean probabilities and an uncertainty map of a volume without a label mask.
 """
+import ctypes as C
+
 import torch
 
+from .. import _ffi
 from ._hier import HierarchicalModel, hier_spec, lift3
+from .phiseg import Prediction
 
 
 def phiseg3d_spec(input_channels, num_classes, num_filters, latent_levels, reversible=False):
@@ -81,11 +86,22 @@ class PHISeg3D(HierarchicalModel):
         io["patch"] = xin.slice(0, self.input_channels)
         return xin
 
-    def _build(self, D, H, W, training, bn_training, decode_only=False):
+    def _check_size(self, D, H, W):
         R = len(self.num_filters)
         if D % (1 << (R - 1)) or H % (1 << (R - 1)) or W % (1 << (R - 1)):
             raise ValueError("PHISeg3D needs every spatial size divisible by 2^(levels-1)")
+
+    def _build(self, D, H, W, training, bn_training, decode_only=False):
+        self._check_size(D, H, W)
         return self._build_plan(D, (D, H, W), training, bn_training, decode_only)
+
+    def _build_predict(self, D, H, W, part):
+        """The two plans of predict() for one volume (HierarchicalModel._build_predict_plan): eval-mode BatchNorm, no loss or backward
+        tape, fp32 storage (_passes._b16_pass skips plans that are not bn_training).  part = "trunk": patch -> the prior's contracting
+        path; part = "draw": the prior's latent path and the likelihood up to the un-resized level logits io["s_in"] - no
+        UZ_OP_NEAREST3D_FWD: uz_vol_sample_accum reads the levels at their own resolution."""
+        self._check_size(D, H, W)
+        return self._build_predict_plan(D, (D, H, W), part, resize=False)
 
     # ------------------------------------------------------------------ reference API (volumes are NCDHW at the boundary)
     @staticmethod
@@ -128,6 +144,81 @@ class PHISeg3D(HierarchicalModel):
         V = self._boundary(plan)
         self.s_in_list = [V(v) for v in io["s_in"]]
         return self._publish(plan)
+
+    def _predict_state(self, draw, D, H, W):
+        """What predict() keeps with its draw plan between calls (plan.host): the fp64 running sum and the host tables of
+        uz_vol_sample_accum - level pointers, channel counts and the two resize factors, finest level first."""
+        st = draw.host.get("vol_stats")
+        if st is None:
+            lv = draw.io["s_in"]
+            n = len(lv)
+            st = draw.host["vol_stats"] = dict(
+                acc=torch.empty(self.num_classes, D, H, W, dtype=torch.float64, device=self.device),
+                ptrs=(C.c_void_p * n)(*[draw._resolve(v) for v in lv]), ctot=(C.c_int * n)(*[v.Ctot for v in lv]),
+                f=(C.c_int * n)(*[H // v.H for v in lv]), fz=(C.c_int * n)(*[D // v.N for v in lv]))
+        return st
+
+    def predict(self, patch, n_samples=1, eps=None, return_soft=False, return_levels=False):
+        """Segment the volume `patch` (1, C, D, H, W) without a label mask: n_samples draws from the prior, from ONE pass of its
+        contracting path (in eval mode it does not depend on the noise).  The trunk plan runs once and hands its feature maps to the
+        draw plan (uz_batch_repeat_fwd with S = 1: a strided slice copy; nothing in the draw plan writes them, so they survive all its
+        runs); then per sample: noise, the draw plan, uz_vol_sample_accum - which reads the level logits at their own resolution,
+        writes the sample's labels and adds its probabilities to an fp64 running sum kept with the plan -, and at the end
+        uz_vol_sample_finish.  `eps` (optional, L tensors, deepest level first, each (n_samples, 2, d_k, h_k, w_k)) injects the noise;
+        default draws it on the device.  Returns a Prediction with one more spatial axis: labels (S, 1, D, H, W) uint8, mean_soft
+        (1, K, D, H, W), mean_label and entropy (1, D, H, W), soft (S, 1, K, D, H, W) or None, and levels - with return_levels=True
+        (meant for small volumes and tests) L tensors (S, 1, K, d_l, h_l, w_l) of every sample's UN-RESIZED level logits, finest
+        first, copied per sample; else None.  prior_mu / prior_sigma / prior_latent_space are set as forward() sets them, for the
+        LAST sample drawn (views of the plan's buffers)."""
+        self._require_gpu()
+        if self.training:
+            raise RuntimeError("predict() needs eval mode: with batch statistics the contracting path of a volume is not shared by its samples")
+        if self.reversible:
+            raise NotImplementedError("predict() is not built for the reversible variant")
+        if patch.shape[0] != 1:
+            raise NotImplementedError("native PHISeg3D runs one volume per call (the reference's BraTS config uses batch_size 1)")
+        S, nl, K, dev = int(n_samples), self.latent_levels, self.num_classes, self.device
+        if S < 1:
+            raise ValueError("predict() needs n_samples >= 1")
+        D, H, W = self._dims(patch)
+        self._check_size(D, H, W)
+        if eps is not None and len(eps) != nl:
+            raise ValueError(f"predict() takes {nl} eps tensors (deepest level first), got {len(eps)}")
+        trunk = self._plan(("trunk", D, H, W), lambda: self._build_predict(D, H, W, "trunk"))
+        draw = self._plan(("draw", D, H, W), lambda: self._build_predict(D, H, W, "draw"))
+        L, st = _ffi.lib(), C.c_void_p(self._stream())
+        T, io = draw.tensor, draw.io
+        trunk.tensor(trunk.io["patch"]).copy_(self._to_slices(patch))
+        self._run(trunk, "fwd")
+        for src, dst in zip(trunk.io["feats"], io["feats"]):
+            _ffi.check(L.uz_batch_repeat_fwd(trunk._resolve(src), src.C, src.Ctot, draw._resolve(dst), dst.Ctot, src.N, 1, src.H, src.W, st),
+                       "batch_repeat_fwd")
+        host = self._predict_state(draw, D, H, W)
+        out = Prediction(labels=torch.empty(S, 1, D, H, W, dtype=torch.uint8, device=dev), mean_soft=torch.empty(1, K, D, H, W, device=dev),
+                         mean_label=torch.empty(1, D, H, W, dtype=torch.uint8, device=dev), entropy=torch.empty(1, D, H, W, device=dev),
+                         levels=[torch.empty(S, 1, v.C, v.N, v.H, v.W, device=dev) for v in io["s_in"]] if return_levels else None,
+                         soft=torch.empty(S, 1, K, D, H, W, device=dev) if return_soft else None)
+        for s in range(S):
+            for k, e in enumerate(io["eps"]):
+                if eps is None:
+                    self._fill_normal(T(e))
+                else:
+                    T(e).copy_(self._to_slices(eps[k][s:s + 1]))
+            self._run(draw, "fwd")
+            _ffi.check(L.uz_vol_sample_accum(host["ptrs"], host["ctot"], host["f"], host["fz"], nl, K, D, H, W, out.labels[s].data_ptr(),
+                                             out.soft[s].data_ptr() if return_soft else None, host["acc"].data_ptr(), int(s == 0), st),
+                       "vol_sample_accum")
+            if return_levels:
+                for l, v in enumerate(io["s_in"]):
+                    out.levels[l][s].copy_(self._to_volume(T(v)))
+        _ffi.check(L.uz_vol_sample_finish(host["acc"].data_ptr(), K, S, D, H, W, out.mean_soft.data_ptr(), out.mean_label.data_ptr(),
+                                          out.entropy.data_ptr(), st), "vol_sample_finish")
+        order = [nl - 1 - lvl for lvl in range(nl)]        # level -> draw index
+        V = self._boundary(draw)
+        self.prior_mu = [V(io["prior"][k].mu) for k in order]
+        self.prior_sigma = [V(io["prior"][k].sigma) for k in order]
+        self.prior_latent_space = [V(io["prior_z"][k]) for k in order]
+        return out
 
     def _publish_loss(self, total, terms):
         # the reference accumulates both parts into loss_tot and returns the running total from each helper (:547-555,:582-583,

@@ -306,8 +306,9 @@ class UNetModel:
 
     @torch.no_grad()
     def predict(self, images, n_samples=1):
-        """Segment unlabelled images: a numpy or torch batch (B, H, W) or (B, C, H, W) -> the net's Prediction (models/phiseg.py) of
-        `n_samples` prior samples per image.  No mask, no loss: validate() and test() keep the reference's loop."""
+        """Segment unlabelled images: a numpy or torch batch (B, H, W) or (B, C, H, W) - or, for PHISeg3D, one volume (1, C, D, H, W),
+        handed through as it is - -> the net's Prediction (models/phiseg.py) of `n_samples` prior samples per image.  No mask, no
+        loss: validate() and test() keep the reference's loop."""
         if not hasattr(self.net, "predict"):
             raise NotImplementedError(f"{type(self.net).__name__} has no mask-free predict()")
         self.net.eval()
