@@ -40,6 +40,11 @@ def draw_augmentation(n_images, shape, options):
         raise AssertionError("When doing augmentations with rotations, scaling, or elastic transformations "
                              "the parameter 'nlabels' must be provided.")
     n_x, n_y = shape
+    if do_scale and n_x != n_y:
+        # :214-217 draw ONE side r_y from n_y, the crop's column from n_x - r_y and its row from n_y - r_y, and use them on the other
+        # axis each: on a wide image the draw itself fails (n_x < r_y), on a tall one the crop leaves the image's columns
+        raise ValueError(f"do_scaleaug crops a square whose side and position are drawn for a square image (the reference's "
+                         f"_augmentation_function): got {n_x} x {n_y}; switch it off for non-square images")
     out = np.zeros((n_images, 8), np.float32)
     out[:, 1] = 1.0
     for ii in range(n_images):

@@ -62,7 +62,7 @@ class SyntheticData:
             lab = np.stack([np.roll(m[:n_train, 0], shift=(a, -a), axis=(1, 2)) for a in range(n_ann_t)], axis=-1).astype(np.uint8)
             self.train = BatchProvider(x[:n_train, 0], lab, np.arange(n_train), add_dummy_dimension=True, do_augmentations=True,
                                        augmentation_options=getattr(exp_config, "augmentation_options", None) or
-                                       dict(do_rotations=True, do_scaleaug=True, nlabels=getattr(exp_config, "n_classes", 2)),
+                                       dict(do_rotations=True, do_scaleaug=h == w, nlabels=getattr(exp_config, "n_classes", 2)),      # (the scale augmentation is defined for square images only)
                                        num_labels_per_subject=n_ann_t, annotator_range=range(n_ann_t))
         # validation labels carry several annotators per image, (n, H, W, A), like the LIDC HDF5 (lidc_data_loader.py:92-110)
         n_ann = getattr(exp_config, "num_labels_per_subject", 4)
