@@ -464,6 +464,30 @@ int uz_label_pair_counts(const uint8_t* a, int Na, const uint8_t* b, int Nb, int
  * (N,K,HW) against M one-hot ground truths (M,K,HW); then ncc(E_ss, E_sy[j]) for every j (utils.py:130-145).              */
 int uz_ncc_maps(const float* soft, const float* gt_onehot, int N, int M, int K, int HW, float* E_ss, float* E_sy, void* stream);
 int uz_ncc(const float* a, const float* v, int M, int HW, float* out, void* stream);
+/* GED, NCC and per-label Dice of S samples of B images against A annotators each, in five launches on `stream` with no host round
+ * trip (csrc/score.hip).  P = pixels of a map (H W, or D H W of a volume with B = 1).
+ *   labels (S, B, P) uint8: sample s of image b is row s*B + b (Prediction.labels); ann (B, A, P) uint8; mean_label (B, P) uint8;
+ *   soft (S, B, K, P) fp32 (Prediction.soft) or null: no NCC, `ncc` and `ncc_pairs` are then not written.
+ * Bit planes: for every map and every label k in 0 .. K-1 a plane of ceil(P / 64) 64-bit words in the workspace, bit q % 64 of word
+ * q / 64 set when pixel q equals k (bits from P on are 0; a pixel value >= K sets no bit).  Pair counts: popcount(x & y) over the
+ * planes.  counts (nullable) int32: for b = 0 .. B-1, within b for k = 0 .. K-1, three matrices [S][A][3] (samples x annotators),
+ * [S][S][3] (samples x samples), [A][A][3] (annotators x annotators), each in the layout of uz_label_pair_counts: intersection,
+ * |first|, |second|.  Integer, no atomics.
+ *   ged (B) fp64: per pair and label l in 1 .. K-1, IoU = 1 if both maps are empty of l, 0 if exactly one is, else inter / union;
+ *       d = 1 - (sum_l IoU_l) / (K - 1);  GED_b = 2/(S A) sum d_sy - 1/S^2 sum d_ss - 1/A^2 sum d_yy.  One 256-thread workgroup per
+ *       image: thread t adds the pairs t, t + 256, ... of a matrix in row-major pair order, the 256 partial sums are then added by
+ *       the xor-butterfly within each wave (offsets 32 .. 1) and the four waves in the order 0 .. 3.
+ *   dice (B, A, K) fp64: mean_label[b] against EVERY annotator j, label k: 1 if both are empty of k, 0 if exactly one is, else
+ *       2 inter / (|a| + |b|) (train_model.py:212-224).
+ *   ncc_pairs (B, A) fp32: for image b what uz_ncc_maps + uz_ncc give on soft[:, b] and the one-hot of ann[b], bit for bit (the same
+ *       device functions; the one-hot value is read from the uint8 label).  ncc (B) fp64 = (sum_j ncc_pairs[b][j], j = 0 .. A-1) / A.
+ * Every output is written once by its owner, nothing is accumulated across launches: a repeated call is bit-equal.
+ * 2 <= K <= 8; B, S, A, P >= 1; the element counts of every operand, of `counts` and of the planes must fit int32.  A refused call
+ * writes nothing.  workspace: uz_score_workspace bytes (0 for sizes uz_score_samples refuses), 256-byte aligned.                    */
+size_t uz_score_workspace(int B, int S, int A, int K, int P);
+int uz_score_samples(const uint8_t* labels, const uint8_t* ann, const uint8_t* mean_label, const float* soft,
+                     int B, int S, int A, int K, int P, void* workspace,
+                     int32_t* counts, double* ged, float* ncc_pairs, double* ncc, double* dice, void* stream);
 
 /* ---------------------------------------------------------------- optimiser / vector ops
  * torch.optim.Adam(lr, betas, eps, weight_decay as L2 added to the gradient): train_model.py:49,122.

@@ -16,10 +16,19 @@
   parent  : S x (net.forward(patch, zeros, training=False) + accumulate_output(use_softmax=True) + argmax), then the mean in torch
   and `accum_ms` / `finish_ms`: the two kernels alone on predict's buffers, with the bytes they move and the GB/s that makes
 
+--score (with --model phiseg | probunet): a pass over a 32-image test split, the way UNetModel.test walks it
+  parent  : the loop over UNetModel._evaluate_image (forward on the repeated patch and mask, loss, argmax, then GED / NCC / Dice one
+            label and one pair set at a time, each behind a .cpu())
+  score   : UNetModel.score at --images-per-call 1 2 4 8 (predict + metrics.score_prediction, one host copy per call)
+  Host clock around a pass that ends in a device synchronise (the parent's cost includes its syncs); both warmed, then --passes
+  rounds of [parent, score at every images-per-call]; median, fastest, slowest.  Also per setting: uz_score_samples alone against
+  the per-image sequence of the existing metric launches on the SAME Prediction (device events), and the arena of the plan that
+  draws.  One JSON line per S.
+
 All draw their noise on the device.  Per S the two are warmed up, then timed alternately `--repeats` times, each call between two
 torch.cuda.Event records on the current stream; the figures are the medians, with the fastest and slowest call beside them.
 Before timing, the two paths run once on the SAME noise and the largest difference of their level logits is printed.
-Prints one JSON line per S.  usage: python tools/bench_predict.py [--model phiseg|probunet|phiseg3d] [--samples 16 100] [--repeats 30] [--warmup 5] [--graphs 1]"""
+Prints one JSON line per S.  usage: python tools/bench_predict.py [--model phiseg|probunet|phiseg3d] [--score [--samples 10 16 100] [--passes 10]] [--samples 16 100] [--repeats 30] [--warmup 5] [--graphs 1]"""
 import argparse
 import ctypes as C
 import json
@@ -181,8 +190,94 @@ def phiseg3d(args, dev):
                               device=torch.cuda.get_device_name(0))), flush=True)
 
 
+def score(args, dev):
+    """--score: see the module docstring."""
+    import tempfile
+    import time
+    import types
+
+    import numpy as np
+
+    from unet_zoo_amd import metrics as DM
+    from unet_zoo_amd import train_model as TM
+    hw, K, A, n_img = args.size, 2, 4, args.images
+    model = PHISeg if args.model == "phiseg" else ProbabilisticUnet
+    cfg = types.SimpleNamespace(experiment_name="bench", log_dir_name="bench", filter_channels=FILTERS, latent_levels=5, n_classes=K,
+                                no_convs_fcomb=3, beta=10.0, use_reversible=False, input_channels=1, image_size=(1, hw, hw), batch_size=12,
+                                num_labels_per_subject=A, model=model)
+    torch.manual_seed(1)
+    h = TM.UNetModel(cfg, log_root=tempfile.mkdtemp())            # enables lane replay, as the harness runs the nets
+    with torch.no_grad():                                          # running statistics away from (0, 1)
+        h.net._ptab.bflat.uniform_(0.5, 1.5)
+    h.net.eval()
+    data = TM.SyntheticData(None, cfg, n_train=4, n_val=n_img)
+    images, labels = data.test.images, data.test.labels
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3
+
+    for S in args.samples:
+        def parent():
+            rng = np.random.default_rng(0)
+            return [h._evaluate_image(images[i], labels[i], S, rng) for i in range(n_img)]
+
+        def new(ipc):
+            return h.score(images, labels, n_samples=S, images_per_call=ipc, rng=np.random.default_rng(0))
+
+        for _ in range(args.warmup):
+            parent()
+            for ipc in args.images_per_call:
+                new(ipc)
+        tq, tn = [], {ipc: [] for ipc in args.images_per_call}
+        for _ in range(args.passes):
+            tq.append(wall(parent))
+            for ipc in args.images_per_call:
+                tn[ipc].append(wall(lambda: new(ipc)))
+        rows = {}
+        for ipc in args.images_per_call:
+            # the scoring call alone against the per-image launches it replaces, on one Prediction of this shape
+            patch = torch.as_tensor(images[:ipc], dtype=torch.float32).to(dev).unsqueeze(1).contiguous()
+            ann = torch.from_numpy(np.ascontiguousarray(np.moveaxis(labels[:ipc], -1, 1)).astype(np.uint8)).to(dev)
+            with torch.no_grad():
+                pred = h.net.predict(patch, n_samples=S, return_soft=True)
+
+                def one_call():
+                    DM.score_prediction(pred, ann)
+
+                def per_image():
+                    for b in range(ipc):
+                        yb = ann[b].long()
+                        DM.generalised_energy_distance(pred.labels[:, b], yb, nlabels=K - 1, label_range=range(1, K))
+                        DM.variance_ncc_dist(pred.soft[:, b], torch.stack([(yb == k) for k in range(K)], dim=1).long())
+                        DM.per_label_dice(pred.mean_label[b], yb[0], K)
+                for _ in range(args.warmup):
+                    one_call(), per_image()
+                tk, tp = [], []
+                for _ in range(args.repeats):
+                    tk.append(timed(one_call))
+                    tp.append(timed(per_image))
+            if args.model == "phiseg":
+                arena = h.net._plans[("draw", ipc * S, hw, hw)].arena_floats * 4 / 2 ** 20
+            else:                                                  # the eval plan at batch ipc + the logits of all samples behind it
+                arena = h.net._cur.arena_floats * 4 / 2 ** 20 + ipc * S * K * hw * hw * 4 / 2 ** 20
+            rows[str(ipc)] = dict(pass_ms=stats(tn[ipc]), speedup=round(statistics.median(tq) / statistics.median(tn[ipc]), 3),
+                                  score_call_ms=stats(tk), per_image_metrics_ms=stats(tp), draw_arena_MB=round(arena, 1),
+                                  score_workspace_MB=round(_ffi.lib().uz_score_workspace(ipc, S, A, K, hw * hw) / 2 ** 20, 2))
+        print(json.dumps(dict(bench="score", model=args.model, filters=FILTERS, size=hw, classes=K, annotators=A, images=n_img, samples=S,
+                              passes=args.passes, parent_pass_ms=stats(tq), score=rows, bound_flags=h.net.check_bounds(),
+                              conv_math=_ffi.lib().uz_get_conv_math(), device=torch.cuda.get_device_name(0))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--score", action="store_true", help="time UNetModel.score against the per-image evaluation loop (phiseg | probunet)")
+    ap.add_argument("--images", type=int, default=32, help="--score: images of the synthetic test split")
+    ap.add_argument("--images-per-call", type=int, nargs="+", default=[1, 2, 4, 8])
+    ap.add_argument("--passes", type=int, default=10, help="--score: alternating timed passes over the split")
     ap.add_argument("--model", choices=["phiseg", "probunet", "phiseg3d"], default="phiseg")
     ap.add_argument("--samples", type=int, nargs="+", default=[16, 100])
     ap.add_argument("--batch", type=int, default=1)
@@ -194,6 +289,10 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_predict needs a GPU: a time taken anywhere else says nothing")
     dev = torch.device("cuda", 0)
+    if args.score:
+        if args.model == "phiseg3d":
+            sys.exit("--score times the 2-D models")
+        return score(args, dev)
     if args.model == "probunet":
         return probunet(args, dev)
     if args.model == "phiseg3d":

@@ -26,47 +26,20 @@ __global__ __launch_bounds__(256) void pair_counts_k(const uint8_t* __restrict__
     if (threadIdx.x < 3) out[((size_t)i * nb + j) * 3 + threadIdx.x] = sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
 }
 
-// E_ss[p] = mean_i( -sum_k mean_seg[k,p] * log(s_i[k,p] + eps) ),  E_sy[j,p] = mean_i( -sum_k gt_j[k,p] * log(s_i[k,p] + eps) )
+// E_ss[p] = mean_i( -sum_k mean_seg[k,p] * log(s_i[k,p] + eps) ),  E_sy[j,p] = mean_i( -sum_k gt_j[k,p] * log(s_i[k,p] + eps) ): uz::ncc_maps_px
 __global__ __launch_bounds__(256) void ncc_maps_k(const float* __restrict__ soft, const float* __restrict__ gt, int N, int M, int K, int HW,
                                                    float* __restrict__ Ess, float* __restrict__ Esy) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= HW) return;
-    double ess = 0.0;
-    for (int k = 0; k < K; ++k) {
-        float ms = 0.f;
-        for (int i = 0; i < N; ++i) ms += soft[((size_t)i * K + k) * HW + q];
-        ms /= (float)N;
-        double acc = 0.0;
-        for (int i = 0; i < N; ++i) acc += (double)(ms * logf(soft[((size_t)i * K + k) * HW + q] + 1e-8f));
-        ess -= acc;
-    }
-    Ess[q] = (float)(ess / N);
-    for (int j = 0; j < M; ++j) {
-        double acc = 0.0;
-        for (int k = 0; k < K; ++k) {
-            const float g = gt[((size_t)j * K + k) * HW + q];
-            if (g != 0.f)
-                for (int i = 0; i < N; ++i) acc -= (double)(g * logf(soft[((size_t)i * K + k) * HW + q] + 1e-8f));
-        }
-        Esy[(size_t)j * HW + q] = (float)(acc / N);
-    }
+    uz::ncc_maps_px(soft, K, N, M, K, HW, q, gt, Ess, Esy);
 }
 
-// ncc(a, v) with zero_norm=True (utils.py:130-145) = Pearson correlation of the two maps
+// ncc(a, v) with zero_norm=True (utils.py:130-145) = Pearson correlation of the two maps: uz::ncc_sums, uz::ncc_of_sums
 __global__ __launch_bounds__(256) void ncc_k(const float* __restrict__ a, const float* __restrict__ v, int HW, float* __restrict__ out) {
     __shared__ double sm[4 * 5];
-    const float* vj = v + (size_t)blockIdx.x * HW;
-    double s[5] = {0, 0, 0, 0, 0};
-    for (int q = threadIdx.x; q < HW; q += 256) {
-        const double x = a[q], y = vj[q];
-        s[0] += x; s[1] += x * x; s[2] += y; s[3] += y * y; s[4] += x * y;
-    }
-    uz::block_sum_d<5>(s, sm);
-    if (threadIdx.x == 0) {
-        const double n = HW, ma = s[0] / n, mv = s[2] / n;
-        const double sa = sqrt(fmax(s[1] / n - ma * ma, 0.0)), sv = sqrt(fmax(s[3] / n - mv * mv, 0.0));
-        out[blockIdx.x] = (float)((s[4] / n - ma * mv) / (sa * sv));
-    }
+    double s[5];
+    uz::ncc_sums(a, v + (size_t)blockIdx.x * HW, HW, s, sm);
+    if (threadIdx.x == 0) out[blockIdx.x] = uz::ncc_of_sums(s, HW);
 }
 
 }  // namespace

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "uz_api.h"
 
 namespace uz {
@@ -56,6 +57,51 @@ __device__ __forceinline__ void block_sum_d(double (&v)[NV], double* smem /* >= 
 #pragma unroll
         for (int i = 0; i < NV; ++i) v[i] = smem[i] + smem[NV + i] + smem[2 * NV + i] + smem[3 * NV + i];
     }
+}
+
+// The arithmetic of variance_ncc_dist (utils.py:130-145,202-247), shared by metrics.hip (one image, materialised one-hot ground truths)
+// and score.hip (B images, the one-hot read from uint8 labels): ONE statement of it, so the two agree bit for bit.
+// ncc_maps_px, pixel q of one image: sample i, class k is soft[(i * R + k) * HW + q] (R maps of HW pixels per sample); gt holds the M ground truths, as one-hot
+// floats (M, K, HW) or as uint8 label maps (M, HW) whose one-hot value is 1 where the label equals k (a product with 1.0f is exact).  E_ss[q] = mean_i( -sum_k mean_seg[k] * log(s_i[k] + eps) ), E_sy[j][q] = mean_i( -sum_k gt_j[k] * log(s_i[k] + eps) ):
+// fp32 mean over the samples in the order i = 0 .. N-1, fp64 accumulation of fp32 products.
+template <class GT>
+__device__ __forceinline__ void ncc_maps_px(const float* soft, int R, int N, int M, int K, int HW, int q, const GT* gt, float* Ess, float* Esy) {
+    double ess = 0.0;
+    for (int k = 0; k < K; ++k) {
+        float ms = 0.f;
+        for (int i = 0; i < N; ++i) ms += soft[((size_t)i * R + k) * HW + q];
+        ms /= (float)N;
+        double acc = 0.0;
+        for (int i = 0; i < N; ++i) acc += (double)(ms * logf(soft[((size_t)i * R + k) * HW + q] + 1e-8f));
+        ess -= acc;
+    }
+    Ess[q] = (float)(ess / N);
+    for (int j = 0; j < M; ++j) {
+        double acc = 0.0;
+        for (int k = 0; k < K; ++k) {
+            float g;
+            if constexpr (std::is_same<GT, float>::value) g = gt[((size_t)j * K + k) * HW + q];        // float: materialised one-hot (M, K, HW)
+            else g = gt[(size_t)j * HW + q] == k ? 1.f : 0.f;                           // uint8_t: label maps (M, HW)
+            if (g != 0.f)
+                for (int i = 0; i < N; ++i) acc -= (double)(g * logf(soft[((size_t)i * R + k) * HW + q] + 1e-8f));
+        }
+        Esy[(size_t)j * HW + q] = (float)(acc / N);
+    }
+}
+// ncc(a, v) with zero_norm=True (utils.py:130-145) = Pearson correlation of two maps of HW pixels, by one 256-thread workgroup:
+// ncc_sums leaves the five fp64 sums in thread 0 (sm: >= 20 doubles of LDS), ncc_of_sums is what thread 0 makes of them.
+__device__ __forceinline__ void ncc_sums(const float* __restrict__ a, const float* __restrict__ v, int HW, double (&s)[5], double* sm) {
+    for (int i = 0; i < 5; ++i) s[i] = 0.0;
+    for (int q = threadIdx.x; q < HW; q += 256) {
+        const double x = a[q], y = v[q];
+        s[0] += x; s[1] += x * x; s[2] += y; s[3] += y * y; s[4] += x * y;
+    }
+    block_sum_d<5>(s, sm);
+}
+__device__ __forceinline__ float ncc_of_sums(const double (&s)[5], int HW) {
+    const double n = HW, ma = s[0] / n, mv = s[2] / n;
+    const double sa = sqrt(fmax(s[1] / n - ma * ma, 0.0)), sv = sqrt(fmax(s[3] / n - mv * mv, 0.0));
+    return (float)((s[4] / n - ma * mv) / (sa * sv));
 }
 
 // conv_split.hip: 3x3 forward / data gradient on the fp16 matrix pipe with two-piece split operands (fp32-accurate)

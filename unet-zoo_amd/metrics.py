@@ -5,6 +5,7 @@ Same call signatures as the reference helpers (``utils.generalised_energy_distan
 train_model.py:212-224); the pixel loops run in libuz_hip.so (integer pair counts, cross-entropy maps,
 correlations), only the O(N*M) scalar bookkeeping stays on the host.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -75,3 +76,54 @@ def per_label_dice(pred, gt, n_classes):
         else:
             out.append(2.0 * inter / float(ca + cb))
     return out
+
+
+# --------------------------------------------------------------------------- S samples of B images against A annotators, one call
+Scores = collections.namedtuple("Scores", "ged dice ncc ncc_pairs counts packed")
+Scores.__doc__ = """What score_prediction returns, all on the device: ged (B) fp64, dice (B, A, K) fp64 - the mean label of image b against
+EVERY annotator, the caller picks its own -, ncc (B) fp64 and ncc_pairs (B, A) fp32 (both None when the Prediction carries no `soft`),
+counts (B, K, S*A + S*S + A*A, 3) int32 or None: per image and label the pair-count matrices samples x annotators, samples x samples,
+annotators x annotators, flattened one behind the other, each in pair_counts' layout.  ged, ncc and dice are views of `packed`, one
+fp64 buffer [ged (B) | ncc (B) | dice (B*A*K)], so that a caller copies them to the host in one transfer."""
+
+
+def score_prediction(pred, annotations, return_counts=False):
+    """GED, NCC and per-label Dice of a Prediction (models/phiseg.py: S samples of B images, or PHISeg3D's S samples of one volume)
+    against `annotations` (B, A, ...), an integer tensor of annotator label maps on the device - for all B images in ONE
+    uz_score_samples call (csrc/score.hip): one workspace allocation, no host synchronisation, no ATen arithmetic on the maps
+    (annotations that are not uint8 already are converted once).  Per image the values are those of generalised_energy_distance
+    (labels 1 .. K-1), variance_ncc_dist and per_label_dice above on pred.labels[:, b], pred.soft[:, b] and pred.mean_label[b];
+    K is the class dimension of pred.mean_soft.  Returns a Scores of device tensors."""
+    labels, mean_label, soft = pred.labels, pred.mean_label, pred.soft
+    S, B = int(labels.shape[0]), int(labels.shape[1])
+    K = int(pred.mean_soft.shape[1])
+    P = 1
+    for d in labels.shape[2:]:
+        P *= int(d)
+    if annotations.dim() < 3 or int(annotations.shape[0]) != B or tuple(annotations.shape[2:]) != tuple(labels.shape[2:]):
+        raise ValueError(f"annotations {tuple(annotations.shape)} do not match (B, A) + {tuple(labels.shape[2:])} with B = {B}")
+    if annotations.device != labels.device:
+        raise ValueError("annotations must be on the device of the Prediction")
+    A = int(annotations.shape[1])
+    ann = annotations if annotations.dtype == torch.uint8 else annotations.to(torch.uint8)
+    ann, labels, mean_label = ann.contiguous(), labels.contiguous(), mean_label.contiguous()
+    if labels.dtype != torch.uint8 or mean_label.dtype != torch.uint8:
+        raise TypeError("Prediction.labels and Prediction.mean_label must be uint8")
+    if soft is not None:
+        if soft.dtype != torch.float32 or tuple(soft.shape) != (S, B, K) + tuple(labels.shape[2:]):
+            raise ValueError(f"Prediction.soft {tuple(soft.shape)} {soft.dtype} is not fp32 (S, B, K, ...)")
+        soft = soft.contiguous()
+    L, dev = _ffi.lib(), labels.device
+    nbytes = L.uz_score_workspace(B, S, A, K, P)
+    if nbytes == 0:
+        raise _ffi.UzError(f"score_prediction: sizes refused (B {B} S {S} A {A} K {K} P {P}; 2 <= K <= 8, every element count within int32)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)                # (the caching allocator hands out 512-byte aligned blocks)
+    packed = torch.empty(2 * B + B * A * K, dtype=torch.float64, device=dev)
+    ged, ncc, dice = packed[:B], packed[B:2 * B], packed[2 * B:].view(B, A, K)
+    ncc_pairs = torch.empty(B, A, dtype=torch.float32, device=dev) if soft is not None else None
+    counts = torch.empty(B, K, S * A + S * S + A * A, 3, dtype=torch.int32, device=dev) if return_counts else None
+    _ffi.check(L.uz_score_samples(labels.data_ptr(), ann.data_ptr(), mean_label.data_ptr(), soft.data_ptr() if soft is not None else None,
+                                  B, S, A, K, P, ws.data_ptr(), counts.data_ptr() if return_counts else None, ged.data_ptr(),
+                                  ncc_pairs.data_ptr() if soft is not None else None, ncc.data_ptr() if soft is not None else None,
+                                  dice.data_ptr(), _stream(labels)), "score_samples")
+    return Scores(ged=ged, dice=dice, ncc=ncc if soft is not None else None, ncc_pairs=ncc_pairs, counts=counts, packed=packed)

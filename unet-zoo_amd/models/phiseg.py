@@ -47,6 +47,7 @@ class PHISeg(HierarchicalModel):
     default_lanes_by_mode = {"lanes": 3}     # host-issued lane replay: 2 lanes 17.7 ms, 3: 16.3, 4: 16.2 (one box, round 5)
     decouple_wgrad_px = 8192       # see NativeModel.decouple_wgrad_px: the 16 x 16 ... 2 x 2 levels at batch 32
     decouple_wgrad_prefixes = ("likelihood",)      # its backward is a single chain (posterior / prior pair up): A/B 1 726 -> 1 744 images/s
+    predict_rows_budget = 128  # UNetModel.score: predict()'s draw plan runs at batch images x samples, 87 MB of arena per row at the headline filters (profiles/NOTES_predict.md)
     rev_depths = (3, 2)        # reversible_depth of the contracting / sample_z stacks and of the up / likelihood stacks (phiseg.py:25-26,53-54,87-88)
 
     def __init__(self, input_channels, num_classes, num_filters, latent_levels=5, latent_dim=2, initializers=None,

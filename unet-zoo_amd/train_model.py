@@ -122,6 +122,38 @@ def load_experiment(path):
 
 
 # --------------------------------------------------------------------------- harness
+# UNetModel.score: images per predict() + score_prediction() call when the caller names none.  Measured on one MI355X (headline filters,
+# 128 x 128, 32 images, lane replay; profiles/NOTES_predict.md, "Scoring a split"): more images per call is faster at every setting up
+# to the largest one timed, 8 - PHISeg 2.87 x the per-image loop at 10 samples (1.37 x at one image per call), ProbabilisticUnet
+# 9.8 x - but PHISeg's draw plan runs at batch images x samples and holds 87 MB of arena per row: 8 images x 100 samples are 69 GB for
+# 1.64 x against 1.43 x at one image.  So: 8 images, fewer where a model declares a row budget (PHISeg.predict_rows_budget = 128 rows,
+# 11 GB: 8 images up to 16 samples, one image at 100).
+SCORE_IMAGES_PER_CALL = 8
+
+
+def default_images_per_call(n_samples, rows_budget=None):
+    """SCORE_IMAGES_PER_CALL, or as many images as keep images x n_samples inside `rows_budget` rows (at least one)."""
+    if rows_budget is None:
+        return SCORE_IMAGES_PER_CALL
+    return max(1, min(SCORE_IMAGES_PER_CALL, int(rows_budget) // max(1, int(n_samples))))
+
+
+def score_chunks(n, per_call):
+    """The calls UNetModel.score makes over a split of n images: a list of (indices, keep).  Every call has the same number of
+    images, min(per_call, n) - one trunk / draw plan pair per call shape -; `indices` are the split's images of the call, the last
+    call padded by repeating its last image, and `keep` says how many leading results of the call are real.  Every image appears
+    exactly once among the kept results, in order."""
+    n, per_call = int(n), int(per_call)
+    if n < 1 or per_call < 1:
+        raise ValueError(f"score_chunks: n = {n}, per_call = {per_call}")
+    per = min(per_call, n)
+    out = []
+    for start in range(0, n, per):
+        stop = min(start + per, n)
+        out.append((list(range(start, stop)) + [stop - 1] * (per - (stop - start)), stop - start))
+    return out
+
+
 class UNetModel:
     """Wrapper that trains a native model exactly as the reference harness does (train_model.py:27-136)."""
 
@@ -318,11 +350,48 @@ class UNetModel:
         return self.net.predict(patch.contiguous(), n_samples=n_samples)
 
     @torch.no_grad()
-    def test(self, data, sys_config=None, rounds=10, n_samples=10):
+    def score(self, images, labels, n_samples=10, images_per_call=None, rng=None):
+        """GED, NCC and per-label Dice of a data split without a label mask going through the net: images (n, H, W), labels
+        (n, H, W, A) annotator label maps (the arrays of a split).  The split is walked in calls of `images_per_call` images
+        (score_chunks; default: default_images_per_call - 8, or what the net's predict_rows_budget allows):
+        net.predict(chunk, n_samples, return_soft=True) - one pass of the trunk for the chunk, n_samples prior draws per
+        image - then metrics.score_prediction, and ONE copy to the host per call.  The Dice
+        annotator of each image is rng.choice(annotator_range), drawn in image order exactly as _evaluate_image draws it (rng
+        defaults to default_rng(0), test()'s).  A ragged last call is padded with its last image and the padding's results are
+        dropped.  Returns dict(ged (n,), ncc (n,), dice (n, K)) of numpy arrays.  The values per image are those of
+        _evaluate_image's metrics on predict()'s samples; the samples themselves come from another noise sequence than
+        forward()'s (see test())."""
+        from . import metrics
+        if not hasattr(self.net, "predict"):
+            raise NotImplementedError(f"{type(self.net).__name__} has no mask-free predict()")
+        self.net.eval()
+        images, labels = np.asarray(images), np.asarray(labels)
+        n, A, K = images.shape[0], labels.shape[-1], self.exp_config.n_classes
+        ann_range = list(getattr(self.exp_config, "annotator_range", range(A)))
+        rng = np.random.default_rng(0) if rng is None else rng
+        pick = np.asarray([rng.choice(ann_range) for _ in range(n)], dtype=np.int64)
+        ged, ncc, dice = np.empty(n), np.empty(n), np.empty((n, K))
+        for idx, keep in score_chunks(n, images_per_call or default_images_per_call(n_samples, getattr(self.net, "predict_rows_budget", None))):
+            B = len(idx)
+            patch = torch.as_tensor(images[idx], dtype=torch.float32).to(self.device).unsqueeze(1).contiguous()
+            ann = torch.from_numpy(np.ascontiguousarray(np.moveaxis(labels[idx], -1, 1)).astype(np.uint8)).to(self.device)      # (B, A, H, W)
+            sc = metrics.score_prediction(self.net.predict(patch, n_samples=n_samples, return_soft=True), ann)
+            host = sc.packed.cpu().numpy()                                      # [ged (B) | ncc (B) | dice (B, A, K)]: the call's one copy
+            real = idx[:keep]
+            ged[real], ncc[real] = host[:keep], host[B:B + keep]
+            dice[real] = host[2 * B:].reshape(B, A, K)[np.arange(keep), pick[real]]
+        return dict(ged=ged, ncc=ncc, dice=dice)
+
+    @torch.no_grad()
+    def test(self, data, sys_config=None, rounds=10, n_samples=10, mask_free=False, images_per_call=None):
         """UNetModel.test (train_model.py:333-475): load `<experiment>_best_loss.pth`, then `rounds` passes over the
         test split with `n_samples` prior samples per image; GED / NCC arrays are dumped as
         `ged<n>_<model>_2.npz` / `ncc<n>_<model>_2.npz` next to the checkpoint (:446-447); returns the mean
-        Dice / GED / NCC over the rounds (:473-475 logs them)."""
+        Dice / GED / NCC over the rounds (:473-475 logs them).
+        mask_free=True: every round is one score() over the split (`images_per_call` images per call) instead of the reference's
+        loop over _evaluate_image; files, lists and log lines are the same.  The default stays the reference's loop.  The two
+        routes draw from different noise sequences - forward() draws 2 L noise tensors per call (posterior and prior), predict()
+        draws L - so they agree in distribution, not sample for sample."""
         cfg = self.exp_config
         self.net.eval()
         model_selection = cfg.experiment_name + "_best_loss.pth"
@@ -339,9 +408,13 @@ class UNetModel:
         end = dict(dice=0.0, ged=0.0, ncc=0.0)
         for rnd in range(rounds):
             self.logger.info("Doing iteration {}".format(rnd))
-            for ii in range(data.test.images.shape[0]):
-                r = self._evaluate_image(data.test.images[ii], data.test.labels[ii], n_samples, rng)
-                ged_l.append(r["ged"]); ncc_l.append(r["ncc"]); dice_l.append(r["dice"])
+            if mask_free:
+                r = self.score(data.test.images, data.test.labels, n_samples=n_samples, images_per_call=images_per_call, rng=rng)
+                ged_l.extend(r["ged"].tolist()); ncc_l.extend(r["ncc"].tolist()); dice_l.extend(r["dice"].tolist())
+            else:
+                for ii in range(data.test.images.shape[0]):
+                    r = self._evaluate_image(data.test.images[ii], data.test.labels[ii], n_samples, rng)
+                    ged_l.append(r["ged"]); ncc_l.append(r["ncc"]); dice_l.append(r["dice"])
             dice = torch.tensor(dice_l)
             self.avg_dice = float(dice.mean())
             self.foreground_dice = float(dice.mean(dim=0)[1]) if cfg.n_classes > 1 else float("nan")
@@ -412,6 +485,9 @@ def main(argv=None):
     ap.add_argument("--preproc-folder", default=None, help="sys_config.preproc_folder: where the prepared splits are cached")
     ap.add_argument("--log-root", default=None, help="sys_config.log_root: checkpoints land in <log_root>/<log_dir_name>/<experiment_name>")
     ap.add_argument("--test", action="store_true", help="run UNetModel.test on the best-loss checkpoint after training (train_model.py:333-475)")
+    ap.add_argument("--mask-free", action="store_true", help="with --test: score the test split through predict() + score_prediction "
+                                                             "(UNetModel.score), several images per call, instead of the reference's per-image loop")
+    ap.add_argument("--images-per-call", type=int, default=None, help="with --mask-free: images per predict() call (default: 8, fewer where the model's draw plan would outgrow its row budget)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     sys_config = resolve_sys_config(args.LOCAL, args.data_root, args.preproc_folder, args.log_root)
@@ -421,7 +497,7 @@ def main(argv=None):
     model.train(data, iterations=args.iterations)
     print(model.save_model("last"))
     if args.test:
-        model.test(data, sys_config=sys_config)
+        model.test(data, sys_config=sys_config, mask_free=args.mask_free, images_per_call=args.images_per_call)
 
 
 if __name__ == "__main__":
