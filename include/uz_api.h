@@ -693,6 +693,41 @@ int  uz_event_elapsed_ms(void* start, void* stop, float* ms_out);
 int uz_augment_batch(const float* X, const uint8_t* Y, int H, int W, int A, const int* idx, const int* ann,
                      const float* params, int B, int nlabels, float* x_out, float* s_out, void* stream);
 
+/* ---------------------------------------------------------------- volume input pipeline (data/bratsDataset.py:34-96,
+ * data/BratsProcessing/augmentation.py:12-104)
+ * One BraTS volume, resident in HBM as the HDF5 file stores it, through augment3DImage + random crop + _toEvaluationOneHot + the
+ * NCXYZ transpose.  img [X][Y][Z][C] f32 channels last; lbl [X][Y][Z] u8 with the raw values 0, 1, 2, 4, or NULL (hasMasks=False:
+ * y_eval and y_raw must be NULL too).  Outputs: x_out (C, Xc, Yc, Zc) f32 planar - PHISeg3D's patch[0] with D = X, H = Y, W = Z;
+ * y_eval (3, Xc, Yc, Zc) f32, nullable: l != 0, l != 0 && l != 2, l == 4; y_raw (Xc, Yc, Zc) u8, nullable: the augmented raw label.
+ * prm is a HOST table of UZ_AUG3_NPRM doubles drawn by data/brats_dataset.py:draw_augmentation3d in the reference's order:
+ *   [0] do_rot [1] cos [2] sin   [3] do_scale [4] sX [5] sY (the integer scaled size round(X scale), round(Y scale))
+ *   [6] do_elastic [7..15] dx[9] [16..24] dy[9] (the 3 x 3 displacement matrices, row major)
+ *   [25] do_shift [26..29] shift[4]   [30] flips (bit 0, 1, 2 = axis X, Y, Z)   [31] ox [32] oy [33] oz (crop origin)
+ * Stages run in the reference's order, each on the result of the one before (two channels-last images in `workspace`, 16-byte
+ * aligned, uz_augment_volume_workspace bytes); all in-plane geometry acts on the plane [X][Y] of one z, rows = X, columns = Y:
+ *   rotate   source = rot_coords of csrc/augment.hip about (Y/2, X/2) in fp32, BORDER_REPLICATE; image bilinear with clamped taps,
+ *            label the voxel at floor(s + 0.5) per axis, clamped;
+ *   scale    resize to (sX, sY): image INTER_LINEAR ((o + 0.5) src/dst - 0.5, clamped taps), label INTER_NEAREST min(floor(o src/dst),
+ *            src - 1) in fp64; a smaller plane is centred at (X - sX)/2 and the rest filled with voxel [0,0,0,:] of the volume AS IT
+ *            ENTERS the stage (labels 0), a larger one centre-cropped at (sX - X)/2;
+ *   elastic  dx, dy resized to X x Y with INTER_CUBIC (A = -0.75, taps clamped) in fp64 on the device, map = (float)(index + d);
+ *            image: q = rint(32 map) half to even, taps q >> 5 and + 1 with weights (q & 31)/32, BORDER_REFLECT of any distance;
+ *            label: the voxel at rint(map), BORDER_REFLECT;
+ *   last     shift[c] added to channels 0..3, flips, out[x][y][z] = flipped[x + ox][y + oy][z + oz] - in the last stage's store.
+ * 1 <= C <= 8, every element count within int32, shift only with C >= 4 (the reference hard-codes four channels and raises below).
+ * A NULL where none is allowed, a crop that leaves the volume or a parameter that is not finite is refused before any launch (-1,
+ * uz_last_error names the reason) and nothing is written.  No atomics: every output element is written once, a repeated call is
+ * bit-equal.  One thread per voxel, z fastest; with C == 4 and a 16-byte aligned img a tap is one float4, else a scalar path.
+ * uz_augment_volume_route (host only, like uz_vol_route; align_img = 16, 8 or 4) answers from the predicate the launch uses:
+ * out2[0] = 0 scalar path, 1 float4 path; out2[1] = workgroups of the widest launch a call on this volume can make (a stage over
+ * the whole volume, 256 voxels per workgroup).                                                                               */
+#define UZ_AUG3_NPRM 34
+size_t uz_augment_volume_workspace(int C, int X, int Y, int Z);
+int    uz_augment_volume(const float* img, const uint8_t* lbl, int C, int X, int Y, int Z,
+                         const double* prm, int Xc, int Yc, int Zc, void* workspace,
+                         float* x_out, float* y_eval, uint8_t* y_raw, void* stream);
+int    uz_augment_volume_route(int C, int X, int Y, int Z, int align_img, int* out2);
+
 /* ---------------------------------------------------------------- volumes (models/phiseg3D.py), one sample
  * A volume is stored [D + 2][C][H][W] (zero slice before and after the D real ones) = a batch of D 2-D images.  Conv3d(3x3x3,
  * pad 1) (phiseg3D.py:24) then is uz_conv_fwd / uz_conv_bwd_* with the depth window as 3 C input channels (pointer = slice d-1,
