@@ -532,32 +532,14 @@ int uz_l2_norms_bwd(const float* flat, const int64_t* offs_counts, int n_tensors
 /* ---------------------------------------------------------------- op tape
  * A forward or backward pass is a static list of the calls above ("tape"), built once by
  * the host for a (model, N, H, W) and replayed with ONE FFI call per pass - or captured
- * into a hipGraph.  uz_op mirrors the argument lists above positionally: p[] pointers,
- * i[] ints, f[] floats, in declaration order of the corresponding function.               */
+ * into a hipGraph.  What each op's i[] / p[] / f[] slots mean - the tape encoding - is defined in
+ * ONE place, the table uz_ops.def next to this header: csrc/tape.hip dispatches by its names,
+ * the Python face builds its plans by them, and the op codes below are its entries in order.  */
 enum {
-  UZ_OP_CONV_FWD = 1, UZ_OP_CONV_BWD_DATA, UZ_OP_CONV_BWD_WEIGHT,
-  UZ_OP_BN_RELU_FWD, UZ_OP_BN_RELU_BWD, UZ_OP_RELU_BWD,
-  UZ_OP_AVGPOOL_FWD, UZ_OP_AVGPOOL_BWD, UZ_OP_BILINEAR_FWD, UZ_OP_BILINEAR_BWD,
-  UZ_OP_NEAREST_FWD, UZ_OP_NEAREST_BWD, UZ_OP_SPATIAL_MEAN_FWD, UZ_OP_SPATIAL_MEAN_BWD,
-  UZ_OP_POSTERIOR_INPUT, UZ_OP_LATENT_FWD, UZ_OP_LATENT_BWD, UZ_OP_KL_FWD, UZ_OP_KL_BWD,
-  UZ_OP_CE_FWD, UZ_OP_CE_BWD, UZ_OP_SUM_TERMS, UZ_OP_ACC_SOFTMAX_ARGMAX,
-  UZ_OP_ADAM, UZ_OP_AXPY, UZ_OP_SCALE, UZ_OP_L2_NORMS, UZ_OP_L2_NORMS_BWD,
-  UZ_OP_MEMSET, UZ_OP_COPY, UZ_OP_BCAST_CHANNELS, UZ_OP_BCAST_CHANNELS_BWD,
-  UZ_OP_ABSMAX,          /* p[0] = src, p[1] = slot, n = count */
-  UZ_OP_ABSMAX_COPY,     /* p[0] = src slot, p[1] = dst slot */
-  UZ_OP_W3D_PERMUTE,     /* p = src, dst; i = Cout, Cin, mode */
-  UZ_OP_AVGPOOL3D_FWD, UZ_OP_AVGPOOL3D_BWD, UZ_OP_DEPTH_LERP_FWD, UZ_OP_DEPTH_LERP_BWD, UZ_OP_NEAREST3D_FWD, UZ_OP_NEAREST3D_BWD,
-  UZ_OP_ADD_VIEWS,       /* p = a, b, y, a_amax, b_amax, y_amax; i = CtotA, CtotB, CtotY, C, N, H, W, accumulate; f[0] = alpha */
-  UZ_OP_EVENT_RECORD,    /* p[0] = event (uz_event_create): marks "every earlier op this one depends on is done" */
-  UZ_OP_PACK_WEIGHTS,    /* p[0] = table, p[1] = w_amax; i = n_layers, total_rows (uz_conv_pack_weights); CONV_FWD p[8] / CONV_BWD_DATA p[6] = image */
-  UZ_OP_CHAN_SUM_TABLE,    /* p[0] = table (uz_chan_sum_table), p[1] = the gradient regions it writes; i = n_entries, max_channels */
-  UZ_OP_WGRAD_REDUCE_TABLE, /* p[0] = table (uz_wgrad_reduce_table), p[1] = the gradient regions it writes; i = n_layers, total_blocks */
-  UZ_OP_CHAN_SUM_PARTIALS, /* p = partials, out; i = n_rows, C (uz_chan_sum_partials); CONV_BWD_DATA p[7] = a (folded ReLU backward), p[8] = partials, p[9] = dx bound; i[9] = CtotA */
-  UZ_OP_LATENT_HEADS_FWD,        /* p = h, w_mu, b_mu, w_sigma, b_sigma, eps, mu, pre, sigma, z; i = Cin, CinTot, L, N, H, W, act (uz_latent_heads_fwd) */
-  UZ_OP_LATENT_HEADS_BWD_DATA,   /* p = dy_a, dy_b, w_a, w_b, dh; i = L, Cin, CinTot, N, H, W, accumulate */
-  UZ_OP_LATENT_HEADS_BWD_WEIGHT, /* p = h, dy_a, dy_b, dw_a, db_a, dw_b, db_b, workspace; i = Cin, CinTot, L, N, H, W; n = workspace bytes */
-  UZ_OP_CHAIN,           /* p = sub-op table, phase table, state; i = n_phases, n_workgroups, n_sub_ops (uz_chain_run); p[3..] = the buffers it touches (scheduling only) */
-  UZ_OP_CHAIN_PACK,      /* p = table, w_amax, images; i = n_layers, total_blocks (uz_chain_pack_weights) */
+  UZ_OP__NONE = 0,       /* no op: a zeroed uz_op is refused */
+#define UZ_OP(name, lists) UZ_OP_##name,
+#include "uz_ops.def"
+#undef UZ_OP
   UZ_OP__COUNT
 };
 typedef struct uz_op {

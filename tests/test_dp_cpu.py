@@ -143,7 +143,7 @@ def test_byte_weighted_buckets_on_the_headline_schedule():
     dag = plan.dag[id(ops)]
     end = max(g["sim_start"] + g["sim_cost"] for g in dag)
     tot = sum(hi - lo for lo, hi in b)
-    final = sorted((g["sim_start"] / end, (b[ops[g["first"]]["p"][0][1]][1] - b[ops[g["first"]]["p"][0][1]][0]) / tot)
+    final = sorted((g["sim_start"] / end, (b[ops[g["first"]].p("event")[1]][1] - b[ops[g["first"]].p("event")[1]][0]) / tot)
                    for g in dag if ops[g["first"]]["code"] == "UZ_OP_EVENT_RECORD")
     assert len(final) == len(b) == 7
     assert final[-1][1] <= 0.15                                   # the exchange that trails the tape is one slice
@@ -166,7 +166,7 @@ def test_bucket_events_are_scheduled_behind_every_writer_of_their_bucket():
     assert len(marks) == len(plan.grad_buckets) >= 3
     _check_lane_schedule(plan, "bwd", ops)
     for k in marks:
-        b = ops[k]["p"][0][1]
+        b = ops[k].p("event")[1]
         lo, hi = plan.grad_buckets[b]
         writers = [j for j, o in enumerate(ops) for idx in plan._WRITES[o["code"]] if idx < len(o["p"])
                    for (space, a, c) in plan._resources(o["p"][idx]) if space == ("gflat",) and a < hi and lo < c]
@@ -179,7 +179,7 @@ def test_bucket_events_are_scheduled_behind_every_writer_of_their_bucket():
         assert len(tabs) <= len(plan.grad_buckets)
         owners = []
         for o in tabs:
-            offs = {plan.ptab.poff[k] for k in o["p"][1][1]}
+            offs = {plan.ptab.poff[k] for k in o.p("grads")[1]}
             own = {b for b, (lo, hi) in enumerate(plan.grad_buckets) if any(lo <= x < hi for x in offs)}
             assert len(own) == 1, (code, own)
             owners.append(own.pop())

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import unet_zoo_amd  # noqa: F401
-from unet_zoo_amd import _ffi
+from unet_zoo_amd import _ffi, _ops
 from tests import _golden as G
 
 
@@ -316,7 +316,7 @@ def test_unet_plan_folds_the_relu_backward_into_the_last_writer_of_dA(monkeypatc
     count = lambda plan, code: sum(o["code"] == code for o in plan.bwd_ops)
     net = Unet(1, 2, [32, 64, 128, 192], device="cpu")
     plan = net._build(32, 128, 128)
-    n_units = sum(o["code"] == "UZ_OP_CONV_FWD" and o["i"][8] == 1 for o in plan.fwd_ops)          # convolutions with the fused forward ReLU
+    n_units = sum(o["code"] == "UZ_OP_CONV_FWD" and o.i("relu") == 1 for o in plan.fwd_ops)          # convolutions with the fused forward ReLU
     assert n_units == 21
     assert count(plan, "UZ_OP_RELU_BWD") == 1 and count(plan, "UZ_OP_CHAN_SUM_TABLE") == 1 and count(plan, "UZ_OP_CHAN_SUM_PARTIALS") == 0
     # (the folded forms carry the unit's activation and the bias-gradient partials: CONV_BWD_DATA p[7] / p[8], pooling and interpolation p[2] / p[3])
@@ -359,39 +359,40 @@ def test_phiseg_plan_round4_passes(monkeypatch):
             for j, r in enumerate(o["p"]):
                 if not (isinstance(r, View) and r.buf is b):
                     continue
-                c, i = o["code"], o["i"]
+                c, px = o["code"], _ops.SCHEMA[o["code"]].px
                 if c == "UZ_OP_BN_RELU_FWD":
-                    assert j == 6 and i[10] == 1 and o["p"][8] is not None
-                    assert i[8] > 0 or 4096 < i[3] * i[4] * i[5] <= L.uz_bn_fwd_fused_limit(i[4], i[5])      # statistics from the convolution's partials, or the one-launch mid path
-                    slots.add(o["p"][8][:2])       # (producers tag the ref "acc": compare slot numbers)
+                    assert j == px["a"] and o.i("a_packed") == 1 and o.p("a_amax") is not None
+                    N, H, W = o.i("N", "H", "W")
+                    assert o.i("npart") > 0 or 4096 < N * H * W <= L.uz_bn_fwd_fused_limit(H, W)      # statistics from the convolution's partials, or the one-launch mid path
+                    slots.add(o.p("a_amax")[:2])       # (producers tag the ref "acc": compare slot numbers)
                 elif c in ("UZ_OP_BILINEAR_FWD", "UZ_OP_AVGPOOL_FWD"):
-                    assert j == 1 and i[7 if c == "UZ_OP_BILINEAR_FWD" else 6] == 1 and o["p"][2] is not None
-                    slots.add(o["p"][3][:2])
+                    assert j == px["y"] and o.i("y_packed") == 1 and o.p("x_amax") is not None
+                    slots.add(o.p("y_amax")[:2])
                 elif c == "UZ_OP_CONV_FWD":
-                    assert j == 0 and i[10] == 1 and L.uz_conv_route(0, i[0], i[2], i[4], i[5], i[6], 3) == 1
-                    assert i[11] % 16 == 0 and (i[11] == 0) == (o["p"][10] is None)
-                    assert o["p"][5] in slots and (o["p"][10] is None or o["p"][10] in slots)
+                    assert j == px["x"] and o.i("x_packed") == 1 and L.uz_conv_route(0, *o.i("cin", "cout", "N", "H", "W"), 3) == 1
+                    assert o.i("x_seg2_c0") % 16 == 0 and (o.i("x_seg2_c0") == 0) == (o.p("x_amax2") is None)
+                    assert o.p("x_amax") in slots and (o.p("x_amax2") is None or o.p("x_amax2") in slots)
                 elif c == "UZ_OP_CONV_BWD_WEIGHT":
-                    assert j == 0 and i[8] == 1 and L.uz_conv_route(2, i[0], i[2], i[4], i[5], i[6], 3) == 1
+                    assert j == px["x"] and o.i("x_packed") == 1 and L.uz_conv_route(2, *o.i("cin", "cout", "N", "H", "W"), 3) == 1
                 else:
                     raise AssertionError(f"{c} touches the packed buffer {b.name}")
     # the heaviest layer (3 x 3, 224 -> 128 @ 128 x 128) reads its concat input as two segments: 32 channels from the BatchNorm apply, 192 from the interpolation
-    big = [o for o in plan.fwd_ops if o["code"] == "UZ_OP_CONV_FWD" and o["i"][:3] == [224, 224, 128]]
-    assert len(big) == 1 and big[0]["i"][10:12] == [1, 32]
+    big = [o for o in plan.fwd_ops if o["code"] == "UZ_OP_CONV_FWD" and o.i("cin", "ctot_x", "cout") == [224, 224, 128]]
+    assert len(big) == 1 and big[0].i("x_packed", "x_seg2_c0") == [1, 32]
     # dy: packed where the backward is the three-launch large-plane path, fp32 where it is one launch with the channel's batch on chip
     for o in plan.bwd_ops:
         if o["code"] == "UZ_OP_BN_RELU_BWD":
-            i = o["i"]
-            npx, fused = i[4] * i[5] * i[6], L.uz_bn_bwd_fused_limit(i[5], i[6])
-            assert not (i[9] and npx <= fused)                        # dy is packed only on the three-launch path (bound known before the apply pass)
-            assert (i[10] == 1) == (npx > fused)                      # conv-bias partial rows only on the three-launch path
-    n3 = sum(o["code"] == "UZ_OP_BN_RELU_BWD" and o["i"][10] == 1 for o in plan.bwd_ops)
+            N, H, W = o.i("N", "H", "W")
+            npx, fused = N * H * W, L.uz_bn_bwd_fused_limit(H, W)
+            assert not (o.i("dy_packed") and npx <= fused)            # dy is packed only on the three-launch path (bound known before the apply pass)
+            assert (o.i("dbias_rows") == 1) == (npx > fused)          # conv-bias partial rows only on the three-launch path
+    n3 = sum(o["code"] == "UZ_OP_BN_RELU_BWD" and o.i("dbias_rows") == 1 for o in plan.bwd_ops)
     assert 10 <= info["dy_packed"] <= n3
     assert sum(o["code"] == "UZ_OP_CHAN_SUM_TABLE" for o in plan.bwd_ops) == (1 if n3 else 0)
     # weight-gradient slab reductions: one table-driven launch for all 3 x 3 layers, none inside the layers' own ops
     tab = [o for o in plan.bwd_ops if o["code"] == "UZ_OP_WGRAD_REDUCE_TABLE"]
-    wg = [o for o in plan.bwd_ops if o["code"] == "UZ_OP_CONV_BWD_WEIGHT" and o["i"][7] == 3]
-    assert len(tab) == 1 and tab[0]["i"][0] == len(wg) == 106 and all(o["i"][11] == 1 and o["p"][8] is not None for o in wg)
+    wg = [o for o in plan.bwd_ops if o["code"] == "UZ_OP_CONV_BWD_WEIGHT" and o.i("ks") == 3]
+    assert len(tab) == 1 and tab[0].i("n_layers") == len(wg) == 106 and all(o.i("slabs_only") == 1 and o.p("slabs") is not None for o in wg)
     monkeypatch.setenv("UZ_LANES", "2")
     plan2 = PHISeg(1, 2, [32, 64, 128, 192, 192, 192, 192], device="cpu")
     plan2.train()
@@ -399,13 +400,14 @@ def test_phiseg_plan_round4_passes(monkeypatch):
     _check_lane_schedule(plan2, "bwd", plan2.bwd_ops)
     _check_lane_schedule(plan2, "fwd", plan2.fwd_ops)
     # small planes: the split-K data gradients whose only reader is a unit's BatchNorm backward leave slabs for it (no reduce launch)
-    dg = [o for o in plan.bwd_ops if o["code"] == "UZ_OP_CONV_BWD_DATA" and len(o["i"]) > 10 and o["i"][10] == 3]
+    dg = [o for o in plan.bwd_ops if o["code"] == "UZ_OP_CONV_BWD_DATA" and o.i("fold") == 3]
     assert len(dg) == info["dgrad_folded"] >= 20
     for o in dg:
-        i = o["i"]
-        assert i[4] * i[5] * i[6] <= 4096 and L.uz_conv_bwd_splitk_parts(i[2], i[0], i[4], i[5], i[6], i[7]) > 1
-        users = [b for b in plan.bwd_ops if b["code"] == "UZ_OP_BN_RELU_BWD" and len(b["p"]) > 11 and b["p"][11] is o["p"][7]]
-        assert len(users) == 1 and users[0]["i"][11] == L.uz_conv_bwd_splitk_parts(i[2], i[0], i[4], i[5], i[6], i[7])
+        N, H, W = o.i("N", "H", "W")
+        parts = L.uz_conv_bwd_splitk_parts(*o.i("cin", "cout", "N", "H", "W", "ks"))
+        assert N * H * W <= 4096 and parts > 1
+        users = [b for b in plan.bwd_ops if b["code"] == "UZ_OP_BN_RELU_BWD" and b.p("da_partials") is o.p("fold_arg")]
+        assert len(users) == 1 and users[0].i("nslab") == parts
         assert plan.bwd_ops.index(users[0]) > plan.bwd_ops.index(o)
     for k in ("UZ_PACK_ACT", "UZ_PACK_DY", "UZ_DBIAS_TABLE", "UZ_WGRAD_TABLE", "UZ_BN_FOLD_DGRAD"):
         monkeypatch.setenv(k, "0")
@@ -551,7 +553,7 @@ def test_chain_pass_builds_convex_levelled_chains_at_the_headline_size(monkeypat
     assert len(info["fwd"]) == 1 and info["fwd"][0]["ops"] > 140 and [c["net"] for c in info["bwd"]] == ["likelihood", "prior", "posterior"]
     assert sum(o["code"] == "UZ_OP_CHAIN" for o in plan.fwd_ops) == 1 and sum(o["code"] == "UZ_OP_CHAIN" for o in plan.bwd_ops) == 3
     assert sum(o["code"] == "UZ_OP_CHAIN_PACK" for o in plan.fwd_ops) == 1 and sum(o["code"] == "UZ_OP_CHAIN_PACK" for o in plan.bwd_ops) == 1
-    small = lambda o: o["code"] in ("UZ_OP_CONV_FWD", "UZ_OP_CONV_BWD_DATA") and o["i"][7] == 3 and o["i"][4] * o["i"][5] * o["i"][6] <= 8192
+    small = lambda o: o["code"] in ("UZ_OP_CONV_FWD", "UZ_OP_CONV_BWD_DATA") and o.i("ks") == 3 and o.i("N") * o.i("H") * o.i("W") <= 8192
     assert not any(small(o) for o in plan.fwd_ops + plan.bwd_ops)            # every small 3 x 3 forward / data gradient went into a chain
     for ch in plan._chains:
         sub = ch["sub"]
@@ -575,7 +577,7 @@ def test_chain_pass_builds_convex_levelled_chains_at_the_headline_size(monkeypat
         assert pairs > 100
         # (c) a unit whose dy lives in the lane scratch keeps BatchNorm backward, weight gradient and data gradient back to back
         for k, o in enumerate(ops):
-            if o["code"] == "UZ_OP_BN_RELU_BWD" and type(o["p"][5]).__name__ == "_ScratchView" and o["p"][5].view is None:
+            if o["code"] == "UZ_OP_BN_RELU_BWD" and type(o.p("dy")).__name__ == "_ScratchView" and o.p("dy").view is None:
                 mates = [q for q in ops if q.get("gid") == o["gid"]]
                 pos = [ops.index(q) for q in mates]
                 assert pos == list(range(pos[0], pos[0] + len(pos))) and len({q["lane"] for q in mates}) == 1, (which, k)

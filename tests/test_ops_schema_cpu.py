@@ -1,4 +1,4 @@
-"""The operand schema of the tape ops (unet-zoo_amd/_ops.py) against the header, the wire struct, the plans and - for the two parts the
+"""The operand schema of the tape ops (include/uz_ops.def as unet-zoo_amd/_ops.py reads it) against the header, the wire struct, the plans and - for the two parts the
 lane scheduler and the bf16-storage pass depend on - literal copies of the tables the plan builder carried before the schema."""
 import pytest
 

@@ -10,7 +10,13 @@ import torch.nn.functional as F
 import oracle
 from oracle import refgraph3d as R3
 import unet_zoo_amd  # noqa: F401
+from unet_zoo_amd import _ops
 from tests import _golden as G
+
+
+def _b16_word(o):
+    """The storage-format bits of op `o`; 0 for an op that has no bf16-storage form."""
+    return o.i("b16") if _ops.SCHEMA[o["code"]].b16 else 0
 
 
 # ----------------------------------------------------------------------------- host side (CPU tier)
@@ -83,7 +89,7 @@ def test_bf16_storage_pass_marks_buffers_and_operands_consistently(monkeypatch):
             L.uz_set_conv_math(-1)
     off = build("0", 3)
     on = build("1", 3)
-    assert off.b16_info["buffers"] == 0 and not any(b.b16 for b in off.bufs) and not any(len(o["i"]) > 13 and o["i"][13] for o in off.fwd_ops + off.bwd_ops)
+    assert off.b16_info["buffers"] == 0 and not any(b.b16 for b in off.bufs) and not any(_b16_word(o) for o in off.fwd_ops + off.bwd_ops)
     assert build("1", 1).b16_info["buffers"] == 0                   # the fp32-accurate split mode never stores bf16
     info = on.b16_info
     assert info["buffers"] >= 10 and info["grads"] >= 5 and info["dy"] >= 5 and info["ops"] >= 40, info
@@ -104,7 +110,7 @@ def test_bf16_storage_pass_marks_buffers_and_operands_consistently(monkeypatch):
     for ops in (on.fwd_ops, on.loss_ops, on.bwd_ops):
         for o in ops:
             slots = dict(on._b16_slots(o))
-            bits = o["i"][13] if len(o["i"]) > 13 else 0
+            bits = _b16_word(o)
             for j, r in enumerate(o["p"]):
                 f = fmt(r)
                 if f is None:
@@ -121,12 +127,12 @@ def test_bf16_storage_pass_marks_buffers_and_operands_consistently(monkeypatch):
     # bench.py prices every operand at its storage width (the HBM fractions of the bf16 line would otherwise be 2x too high)
     import bench
     for o in on.fwd_ops + on.bwd_ops:
-        bits = o["i"][13] if len(o["i"]) > 13 else 0
+        bits = _b16_word(o)
         if o["code"] == "UZ_OP_BN_RELU_BWD" and bits == 7:
-            i = o["i"]
-            assert bench.op_bytes(o) == i[1] * i[4] * i[5] * i[6] * (2 * (2 + 2) + 2) == bench.op_bytes(dict(o, i=i[:13])) / 2
-        if o["code"] == "UZ_OP_CONV_FWD" and bits == 3 and o["i"][7] == 3:
-            assert bench.conv_bytes(o) < 0.55 * bench.conv_bytes(dict(o, i=o["i"][:13])) + 4.0 * o["i"][0] * o["i"][2] * 9
+            C, N, H, W = o.i("C", "N", "H", "W")
+            assert bench.op_bytes(o) == C * N * H * W * (2 * (2 + 2) + 2) == bench.op_bytes(dict(o, i=o["i"][:_ops.B16_SLOT])) / 2
+        if o["code"] == "UZ_OP_CONV_FWD" and bits == 3 and o.i("ks") == 3:
+            assert bench.conv_bytes(o) < 0.55 * bench.conv_bytes(dict(o, i=o["i"][:_ops.B16_SLOT])) + 4.0 * o.i("cin") * o.i("cout") * 9
     # byte-typed pointers: consecutive bf16 buffers are packed at 2 bytes per element
     b = next(b for b in on.bufs if b.b16)
     assert b.words == (b.numel + 1) // 2 and on.tensor(View(b)).dtype == torch.bfloat16 and on.tensor(View(b)).shape == (b.N, b.C, b.H, b.W)
@@ -586,8 +592,8 @@ def test_baseline_config5_full_volume_in_bf16_mode():
             s = net.forward(xd, od, training=True, eps=epsd)
             res[mode] = (float(net.loss(ld)), [t.clone() for t in s])
             if mode == 3:
-                n_bf16 = sum(1 for o in net._cur.fwd_ops if o["code"] == "UZ_OP_CONV_FWD" and o["i"][7] == 3 and
-                             L.uz_conv_route(0, o["i"][0], o["i"][2], o["i"][4], o["i"][5], o["i"][6], 3) == 1)
+                n_bf16 = sum(1 for o in net._cur.fwd_ops if o["code"] == "UZ_OP_CONV_FWD" and o.i("ks") == 3 and
+                             L.uz_conv_route(0, *o.i("cin", "cout", "N", "H", "W"), 3) == 1)
                 assert n_bf16 >= 20                                   # the volume's 3 x 3 x 3 convolutions really run on the one-piece kernels
                 net.enable_graphs(True)
                 opt = FusedAdam(net, lr=1e-3, weight_decay=1e-5)
@@ -776,8 +782,8 @@ def test_bf16_mode_against_the_reference_modules_run_in_bf16(storage, monkeypatc
         L.uz_set_conv_math(3)
         net, s, loss = _run_native(meta, inputs)
         assert (net._cur.b16_info["buffers"] >= 10) == (storage == "bf16"), net._cur.b16_info
-        n_bf16 = sum(1 for o in net._cur.fwd_ops if o["code"] == "UZ_OP_CONV_FWD" and o["i"][7] == 3 and
-                     L.uz_conv_route(0, o["i"][0], o["i"][2], o["i"][4], o["i"][5], o["i"][6], 3) == 1)
+        n_bf16 = sum(1 for o in net._cur.fwd_ops if o["code"] == "UZ_OP_CONV_FWD" and o.i("ks") == 3 and
+                     L.uz_conv_route(0, *o.i("cin", "cout", "N", "H", "W"), 3) == 1)
         assert n_bf16 >= 10, n_bf16                                   # the mode is really exercised
     finally:
         L.uz_set_conv_math(-1)

@@ -590,7 +590,7 @@ def test_a_tape_replayed_under_another_weight_gradient_grid_refuses_to_run():
     loss.backward()
     torch.cuda.synchronize()
     plan, L = net._cur, _ffi.lib()
-    sized = [o["i"][12] for o in plan.bwd_ops if o["code"] == "UZ_OP_CONV_BWD_WEIGHT" and o["i"][11]]
+    sized = [o.i("nslab") for o in plan.bwd_ops if o["code"] == "UZ_OP_CONV_BWD_WEIGHT" and o.i("slabs_only")]
     assert len(sized) > 50 and all(n > 0 for n in sized)
     before = L.uz_get_wgrad_target()
     try:

@@ -31,7 +31,7 @@ for _ in range(reps):
     L.uz_run_tape(one, 1, st)
 e1.record(); torch.cuda.synchronize()
 print("chain launch alone: %.1f us" % (e0.elapsed_time(e1) * 1e3 / reps), plan.chain_info, "status", plan.chain_status(net._stream()))
-idx = ops[k]["p"][0][1]
+idx = ops[k].p("ops")[1]
 ch = plan._chains[idx]
 stt = ch["dev"]["state"].cpu()
 stamps = stt[32:].view(torch.int64)

@@ -8,6 +8,7 @@ usage: critical_path.py gpurun_out/r4_op_times.json [batch=32]"""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import unet_zoo_amd  # noqa: F401
+from unet_zoo_amd import _ops
 from unet_zoo_amd.models.phiseg import PHISeg
 
 times = json.load(open(sys.argv[1]))
@@ -50,7 +51,7 @@ for tape, ops in (("fwd", plan.fwd_ops), ("bwd", plan.bwd_ops)):
         for j in range(dag[k]["first"], dag[k]["last"] + 1):
             o = ops[j]
             c = o["code"].replace("UZ_OP_", "")
-            H = o["i"][5] if c.startswith("CONV") or c == "BN_RELU_BWD" else (o["i"][4] if len(o["i"]) > 4 else 0)
+            H = o.i("H") if "H" in _ops.SCHEMA[o["code"]].ix else 0
             key = (c, H)
             fam[key] = fam.get(key, 0.0) + ms[j]
     out[tape] = dict(ops=len(ops), groups=G, sum_ms=round(sum(ms), 3), critical_path_ms=round(fin[end], 3), schedule_makespan_ms=round(max(fin2), 3),

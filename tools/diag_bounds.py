@@ -5,7 +5,7 @@ import os, sys, math, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
-from unet_zoo_amd import _ffi
+from unet_zoo_amd import _ffi, _ops
 from unet_zoo_amd.synthetic import synthetic_batch
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 net = bench.build("phiseg"); net.train()
@@ -25,9 +25,10 @@ for k in range(n):
     if o["code"] != "UZ_OP_BN_RELU_BWD":
         continue
     torch.cuda.synchronize()
-    cout, N, H, W = o["i"][1], o["i"][4], o["i"][5], o["i"][6]
-    dy_off = (arr[k].p[5] - base) // 4
-    sl_off = (arr[k].p[10] - base) // 4
+    cout, N, H, W = o.i("C", "N", "H", "W")
+    px = _ops.SCHEMA[o["code"]].px
+    dy_off = (arr[k].p[px["dy"]] - base) // 4
+    sl_off = (arr[k].p[px["dy_amax"]] - base) // 4
     dy = plan.arena[dy_off:dy_off + N * cout * H * W]
     slot = plan.arena[sl_off:sl_off + 256]
     true, bound = float(dy.abs().max()), float(slot.max())

@@ -1,5 +1,8 @@
 """ctypes binding of libuz_hip.so (C ABI declared in include/uz_api.h).
 
+The header is the single source of the binding (``prototypes()``), and the table it includes, include/uz_ops.def, the single
+source of the tape encoding: ``op_table()`` reads it, ``op_codes()`` numbers its entries, ``_ops.py`` builds the schema from it.
+
 The library is loaded lazily; ``lib()`` raises a clear error when it has not been built
 (``python -c 'import __graft_entry__ as g; g.build()'`` or ``make -C unet-zoo_amd/csrc``).
 There is deliberately no fallback implementation.
@@ -12,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # UZ_LIB: an experiment build of the same library (csrc/Makefile VARIANT=...); never a different implementation
 LIB_PATH = os.environ.get("UZ_LIB") or os.path.join(_HERE, "libuz_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "uz_api.h")
+TABLE_PATH = os.path.join(os.path.dirname(_HERE), "include", "uz_ops.def")      # the tape encoding (included by the header)
 
 _lib = None
 
@@ -63,23 +67,24 @@ def header_symbols():
     return sorted(set(re.findall(r"\b(uz_[a-z0-9_]+)\s*\(", text)))
 
 
-def op_codes():
-    """Parse the UZ_OP_* enum from the header (single source of truth for the tape encoding)."""
-    with open(HEADER_PATH) as f:
+def op_table():
+    """include/uz_ops.def, the single source of the tape encoding, as text: (i[] slot of the bf16-storage word, [(op name, {list: [names]})])
+    in code order - the list keys are I, P, F, WRITES, OPTS, B16 and an absent list is empty."""
+    with open(TABLE_PATH) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    body = re.search(r"enum\s*\{(.*?)\};", text, flags=re.S).group(1)
-    codes, nxt = {}, 0
-    for tok in body.split(","):
-        tok = tok.strip()
-        if not tok:
-            continue
-        if "=" in tok:
-            name, val = [t.strip() for t in tok.split("=")]
-            nxt = int(val)
-        else:
-            name = tok
-        codes[name] = nxt
-        nxt += 1
+    b16_slot = int(re.search(r"#define\s+UZ_B16_SLOT\s+(\d+)", text).group(1))
+    ops = []
+    for entry in text.split("UZ_OP(")[1:]:
+        name = entry.split(",", 1)[0].strip()
+        lists = {k: v.replace(",", " ").split() for k, v in re.findall(r"UZ_(I|P|F|WRITES|OPTS|B16)\(([^)]*)\)", entry)}
+        ops.append(("UZ_OP_" + name, {k: lists.get(k, []) for k in ("I", "P", "F", "WRITES", "OPTS", "B16")}))
+    return b16_slot, ops
+
+
+def op_codes():
+    """The UZ_OP_* enum: the header makes it from the table's entries in order, the first one code 1."""
+    codes = {name: k + 1 for k, (name, _) in enumerate(op_table()[1])}
+    codes["UZ_OP__COUNT"] = len(codes) + 1
     return codes
 
 

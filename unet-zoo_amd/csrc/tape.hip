@@ -93,6 +93,33 @@ extern "C" int uz_build_info(char* out, int cap) {
     return experiment;
 }
 
+// The tape encoding (include/uz_ops.def) as slot numbers: slot::<OP>::I / P / F hold the op's i[] / p[] / f[] slots by name, and for the
+// ops with a bf16-storage form slot::<OP>::B16 the bits of the storage word, which is I::b16.  Every `case` below opens its op's
+// namespace and takes its operands through I() / P() / F() / B16(): a name that is not a slot of THAT op and THAT list does not compile.
+namespace slot {
+#define UZ_OP(name, lists) namespace name { lists }
+#define UZ_I(...) namespace I { enum { __VA_ARGS__ }; }
+#define UZ_P(...) namespace P { enum { __VA_ARGS__ }; }
+#define UZ_F(...) namespace F { enum { __VA_ARGS__ }; }
+#define UZ_B16(...) namespace I { enum { b16 = UZ_B16_SLOT }; } namespace B16 { enum { __VA_ARGS__ }; }
+#define UZ_WRITES(...)
+#define UZ_OPTS(...)
+#include "uz_ops.def"
+#undef UZ_OP
+#undef UZ_I
+#undef UZ_P
+#undef UZ_F
+#undef UZ_B16
+#undef UZ_WRITES
+#undef UZ_OPTS
+}  // namespace slot
+#define I(nm) o.i[I::nm]
+#define F(nm) o.f[F::nm]
+#define P(nm) o.p[P::nm]
+#define FP(nm) static_cast<float*>(P(nm))
+#define CFP(nm) static_cast<const float*>(P(nm))
+#define B16(nm) ((I(b16) >> B16::nm) & 1)
+
 #ifdef UZ_DIAG
 // Diagnostics only, compiled in by `make VARIANT=diag XFLAGS=-DUZ_DIAG` (tools/what_if.sh), never in the product library:
 // UZ_DIAG_SKIP="conv:8,bn:8,resample:4,convmin:64" drops every convolution / BatchNorm / resampling
@@ -124,12 +151,15 @@ static bool diag_skip(const uz_op& o) {
     }
     auto hit = [&](int h, int lim) { return only ? (h == only && lim >= only) : h <= lim; };
     switch (o.code) {
-        case UZ_OP_CONV_FWD: return hit(o.i[5], conv) || hit(o.i[5], fwd) || o.i[5] >= convmin;
-        case UZ_OP_CONV_BWD_DATA: return hit(o.i[5], conv) || hit(o.i[5], dgrad) || o.i[5] >= convmin;
-        case UZ_OP_CONV_BWD_WEIGHT: return hit(o.i[5], conv) || hit(o.i[5], wgrad) || o.i[5] >= convmin;
-        case UZ_OP_BN_RELU_FWD: return hit(o.i[4], bn) || hit(o.i[4], bnf);
-        case UZ_OP_BN_RELU_BWD: return hit(o.i[5], bn) || hit(o.i[5], bnb);
-        case UZ_OP_AVGPOOL_FWD: case UZ_OP_AVGPOOL_BWD: case UZ_OP_BILINEAR_FWD: case UZ_OP_BILINEAR_BWD: return hit(o.i[4], rs);
+        case UZ_OP_CONV_FWD: { using namespace slot::CONV_FWD; return hit(I(H), conv) || hit(I(H), fwd) || I(H) >= convmin; }
+        case UZ_OP_CONV_BWD_DATA: { using namespace slot::CONV_BWD_DATA; return hit(I(H), conv) || hit(I(H), dgrad) || I(H) >= convmin; }
+        case UZ_OP_CONV_BWD_WEIGHT: { using namespace slot::CONV_BWD_WEIGHT; return hit(I(H), conv) || hit(I(H), wgrad) || I(H) >= convmin; }
+        case UZ_OP_BN_RELU_FWD: { using namespace slot::BN_RELU_FWD; return hit(I(H), bn) || hit(I(H), bnf); }
+        case UZ_OP_BN_RELU_BWD: { using namespace slot::BN_RELU_BWD; return hit(I(H), bn) || hit(I(H), bnb); }
+        case UZ_OP_AVGPOOL_FWD: { using namespace slot::AVGPOOL_FWD; return hit(I(H), rs); }
+        case UZ_OP_AVGPOOL_BWD: { using namespace slot::AVGPOOL_BWD; return hit(I(H), rs); }
+        case UZ_OP_BILINEAR_FWD: { using namespace slot::BILINEAR_FWD; return hit(I(H), rs); }
+        case UZ_OP_BILINEAR_BWD: { using namespace slot::BILINEAR_BWD; return hit(I(H), rs); }
         default: return false;
     }
 }
@@ -139,166 +169,218 @@ static int run_one(const uz_op& o, void* st) {
 #ifdef UZ_DIAG
     if (diag_skip(o)) return 0;
 #endif
-    const int32_t* i = o.i;
-    const float* f = o.f;
-    void* const* p = o.p;
-#define FP(k) static_cast<float*>(p[k])
-#define CFP(k) static_cast<const float*>(p[k])
+    const size_t n = (size_t)o.n;
     switch (o.code) {
-        case UZ_OP_CONV_FWD:
-            // i[13]: bf16 STORAGE bits (Plan._b16_pass) - bit 0 = x, bit 1 = y hold 2-byte bf16 elements
-            if (i[13] && i[7] == 1) return uz_conv1x1_fwd_b16(p[0], i[0], i[1], CFP(1), CFP(2), FP(3), i[2], i[3], i[4], i[5], i[6], i[13] & 1, st);      // a 1x1 head: only x may be bf16
-            if (i[13]) return uz_conv_fwd_b16(p[0], i[0], i[1], CFP(1), CFP(2), p[3], i[2], i[3], i[4], i[5], i[6], i[7], p[4], (size_t)o.n, p[8], FP(9), i[13] & 1, (i[13] >> 1) & 1, st);
-            if (i[9]) return uz_conv_fwd_slabs(CFP(0), i[0], i[1], CFP(1), i[2], i[4], i[5], i[6], i[7], p[4], (size_t)o.n, st);      // the unit's BatchNorm adds the slabs
-            // i[12] = 1 | relu << 1: x is the producing unit's PRE-normalisation output, p[11] its statistics table - the staging applies BatchNorm + ReLU
-            if (i[12]) return uz_conv_fwd_bn_ex(CFP(0), i[0], i[1], CFP(11), (i[12] >> 1) & 1, CFP(1), CFP(2), FP(3), i[2], i[3], i[4], i[5], i[6], i[7], CFP(5), CFP(6), FP(7), p[4], (size_t)o.n, p[8], FP(9), st);
-            // i[10] = input in split storage, p[10] / i[11] = bound and first channel of its second scale segment
-            return uz_conv_fwd_ex(CFP(0), i[0], i[1], CFP(1), CFP(2), FP(3), i[2], i[3], i[4], i[5], i[6], i[7], i[8], CFP(5), CFP(6), FP(7), p[4], (size_t)o.n, p[8], FP(9),
-                                  i[10], CFP(10), i[11], st);
-        case UZ_OP_CONV_BWD_DATA:
-            // i[10]: fold of the unit that produced the output's forward twin - 1 ReLU mask (p[7] = its activation), 2 BatchNorm-backward
-            // reduction (p[7] = its pre-normalisation output, p[10] = its statistics table, i[12] = its relu flag); i[11] = dy in split storage
-            if (i[13] && i[7] == 1) return uz_conv1x1_bwd_data_b16(CFP(0), i[0], i[1], CFP(1), p[2], i[2], i[3], i[4], i[5], i[6], i[8], (i[13] >> 1) & 1, st);
-            if (i[13]) return uz_conv_bwd_data_b16(p[0], i[0], i[1], CFP(1), p[2], i[2], i[3], i[4], i[5], i[6], i[7], i[8], p[3], (size_t)o.n, p[6], i[13] & 1, (i[13] >> 1) & 1, st);      // bit 0 = dy, bit 1 = dx in bf16 storage
-            if (i[10] == 3) return uz_conv_bwd_data_slabs(CFP(0), i[0], i[1], CFP(1), i[2], i[4], i[5], i[6], i[7], FP(7), st);      // slabs only: the consumer's BatchNorm backward adds them
-            if (i[10] == 1) return uz_conv_bwd_data_relu(CFP(0), i[0], i[1], CFP(1), FP(2), i[2], i[3], i[4], i[5], i[6], i[7], i[8], CFP(4), CFP(5), p[3], (size_t)o.n, p[6], CFP(7), i[9], FP(8), FP(9), st);
-            return uz_conv_bwd_data_ex(CFP(0), i[0], i[1], CFP(1), FP(2), i[2], i[3], i[4], i[5], i[6], i[7], i[8], CFP(4), CFP(5), p[3], (size_t)o.n, p[6], i[11],
-                                       i[10] == 2 ? CFP(7) : nullptr, i[9], CFP(10), i[12], FP(8), st);
-        case UZ_OP_CONV_BWD_WEIGHT:
-            // i[8] = x in split storage, p[7] / i[9] = second scale segment of x, i[10] = dy in split storage
-            // i[11]: slabs only, into p[8] (added by UZ_OP_WGRAD_REDUCE_TABLE at the end of the tape); i[12]: the slab count p[8] and the
+        case UZ_OP_CONV_FWD: { using namespace slot::CONV_FWD;
+            // b16: bf16 STORAGE bits (Plan._b16_pass) - the operand holds 2-byte bf16 elements
+            if (I(b16) && I(ks) == 1) return uz_conv1x1_fwd_b16(P(x), I(cin), I(ctot_x), CFP(w), CFP(bias), FP(y), I(cout), I(ctot_y), I(N), I(H), I(W), B16(x), st);      // a 1x1 head: only x may be bf16
+            if (I(b16)) return uz_conv_fwd_b16(P(x), I(cin), I(ctot_x), CFP(w), CFP(bias), P(y), I(cout), I(ctot_y), I(N), I(H), I(W), I(ks), P(workspace), n, P(w_image), FP(bn_partials), B16(x), B16(y), st);
+            if (I(slabs_only)) return uz_conv_fwd_slabs(CFP(x), I(cin), I(ctot_x), CFP(w), I(cout), I(N), I(H), I(W), I(ks), P(workspace), n, st);      // the unit's BatchNorm adds the slabs
+            // bn_in = 1 | relu << 1: x is the producing unit's PRE-normalisation output, bn_stats its statistics table - the staging applies BatchNorm + ReLU
+            if (I(bn_in)) return uz_conv_fwd_bn_ex(CFP(x), I(cin), I(ctot_x), CFP(bn_stats), (I(bn_in) >> 1) & 1, CFP(w), CFP(bias), FP(y), I(cout), I(ctot_y), I(N), I(H), I(W), I(ks), CFP(x_amax), CFP(w_amax), FP(y_amax), P(workspace), n, P(w_image), FP(bn_partials), st);
+            // x_packed = input in split storage, x_amax2 / x_seg2_c0 = bound and first channel of its second scale segment
+            return uz_conv_fwd_ex(CFP(x), I(cin), I(ctot_x), CFP(w), CFP(bias), FP(y), I(cout), I(ctot_y), I(N), I(H), I(W), I(ks), I(relu), CFP(x_amax), CFP(w_amax), FP(y_amax), P(workspace), n, P(w_image), FP(bn_partials),
+                                  I(x_packed), CFP(x_amax2), I(x_seg2_c0), st);
+        }
+        case UZ_OP_CONV_BWD_DATA: { using namespace slot::CONV_BWD_DATA;
+            // fold: of the unit that produced the output's forward twin - 1 ReLU mask (fold_arg = its activation), 2 BatchNorm-backward
+            // reduction (fold_arg = its pre-normalisation output, bn_stats = its statistics table, fold_relu = its relu flag); dy_packed = dy in split storage
+            if (I(b16) && I(ks) == 1) return uz_conv1x1_bwd_data_b16(CFP(dy), I(cout), I(ctot_dy), CFP(w), P(dx), I(cin), I(ctot_dx), I(N), I(H), I(W), I(accumulate), B16(dx), st);
+            if (I(b16)) return uz_conv_bwd_data_b16(P(dy), I(cout), I(ctot_dy), CFP(w), P(dx), I(cin), I(ctot_dx), I(N), I(H), I(W), I(ks), I(accumulate), P(workspace), n, P(w_image), B16(dy), B16(dx), st);
+            if (I(fold) == 3) return uz_conv_bwd_data_slabs(CFP(dy), I(cout), I(ctot_dy), CFP(w), I(cin), I(N), I(H), I(W), I(ks), FP(fold_arg), st);      // slabs only: the consumer's BatchNorm backward adds them
+            if (I(fold) == 1) return uz_conv_bwd_data_relu(CFP(dy), I(cout), I(ctot_dy), CFP(w), FP(dx), I(cin), I(ctot_dx), I(N), I(H), I(W), I(ks), I(accumulate), CFP(dy_amax), CFP(w_amax), P(workspace), n, P(w_image), CFP(fold_arg), I(ctot_fold), FP(partials), FP(dx_amax), st);
+            return uz_conv_bwd_data_ex(CFP(dy), I(cout), I(ctot_dy), CFP(w), FP(dx), I(cin), I(ctot_dx), I(N), I(H), I(W), I(ks), I(accumulate), CFP(dy_amax), CFP(w_amax), P(workspace), n, P(w_image), I(dy_packed),
+                                       I(fold) == 2 ? CFP(fold_arg) : nullptr, I(ctot_fold), CFP(bn_stats), I(fold_relu), FP(partials), st);
+        }
+        case UZ_OP_CONV_BWD_WEIGHT: { using namespace slot::CONV_BWD_WEIGHT;
+            // x_packed = x in split storage, x_amax2 / x_seg2_c0 = second scale segment of x, dy_packed = dy in split storage
+            // slabs_only: slabs only, into `slabs` (added by UZ_OP_WGRAD_REDUCE_TABLE at the end of the tape); nslab: the slab count `slabs` and the
             // table row were SIZED for when the plan was built.  uz_set_wgrad_target is process state: a caller that replays this tape
             // under another target would write more slabs than were allocated and reduce the wrong number - refuse instead
-            if (i[11] && i[12] > 0 && uz_conv_bwd_weight_slabs(i[0], i[2], i[4], i[5], i[6], i[7]) != i[12])
+            if (I(slabs_only) && I(nslab) > 0 && uz_conv_bwd_weight_slabs(I(cin), I(cout), I(N), I(H), I(W), I(ks)) != I(nslab))
                 return uz::fail("conv_bwd_weight: the plan sized %d slabs for this layer, the library would now write %d (uz_set_wgrad_target / "
                                 "uz_set_conv_math changed between plan build and replay: rebuild the plan or restore the setting)",
-                                i[12], uz_conv_bwd_weight_slabs(i[0], i[2], i[4], i[5], i[6], i[7]));
-            if (i[13] && i[7] == 1) return uz_conv1x1_bwd_weight_b16(p[0], i[0], i[1], CFP(1), i[2], i[3], FP(2), FP(3), i[4], i[5], i[6], p[4], (size_t)o.n, i[13] & 1, st);
-            if (i[13]) return uz_conv_bwd_weight_b16(p[0], i[0], i[1], p[1], i[2], i[3], FP(2), i[4], i[5], i[6], i[7], p[4], (size_t)o.n, i[13] & 1, (i[13] >> 1) & 1, i[11] ? FP(8) : nullptr, st);      // bit 0 = x, bit 1 = dy in bf16 storage
-            return uz_conv_bwd_weight_ex(CFP(0), i[0], i[1], CFP(1), i[2], i[3], FP(2), FP(3), i[4], i[5], i[6], i[7], CFP(5), CFP(6), p[4], (size_t)o.n,
-                                         i[8], CFP(7), i[9], i[10], i[11] ? FP(8) : nullptr, st);
-        case UZ_OP_BN_RELU_FWD:
-            if (i[13]) return uz_bn_relu_fwd_b16(p[0], i[0], i[1], CFP(1), CFP(2), FP(3), FP(4), FP(5), p[6], i[2], i[3], i[4], i[5], f[0], f[1], i[6], i[7], p[7], CFP(9), i[8], i[13] & 1, (i[13] >> 1) & 1, st);      // bit 0 = y, bit 1 = a in bf16 storage
-            if (i[9] > 1) return uz_bn_relu_fwd_slabs(CFP(10), i[9], CFP(11), FP(0), i[0], i[1], CFP(1), CFP(2), FP(3), FP(4), FP(5), FP(6), i[2], i[3], i[4], i[5], f[0], f[1], i[6], i[7], FP(8), st);
-            // i[11] = phase (Plan._bn_offchain_pass): 1 statistics only, 2 apply only
-            if (i[11]) return uz_bn_relu_fwd_phase(CFP(0), i[0], i[1], CFP(1), CFP(2), FP(3), FP(4), FP(5), FP(6), i[2], i[3], i[4], i[5], f[0], f[1], i[7], FP(8), CFP(9), i[8], i[10], i[11], st);
-            // (save holds 4 C floats in plans; i[10] = write the activation as split storage)
-            return uz_bn_relu_fwd_ex(CFP(0), i[0], i[1], CFP(1), CFP(2), FP(3), FP(4), FP(5), FP(6), i[2], i[3], i[4], i[5], f[0], f[1], i[6], i[7], FP(8), p[7], CFP(9), i[8], i[10], st);
-        case UZ_OP_BN_RELU_BWD:
-            // p[11] / i[8] = reduction partials left by the data gradient that wrote dA last, i[9] = write dy as split storage
-            // i[10]: p[8] holds the rows for the conv-bias gradient's partial sums instead of the gradient itself (added by UZ_OP_CHAN_SUM_TABLE)
-            // i[11] > 0: p[11] holds that many split-K slabs of dA left by the data gradient (small planes) instead of reduction partials
-            if (i[13]) return uz_bn_relu_bwd_b16(p[0], i[0], p[1], i[1], i[2], CFP(2), CFP(3), CFP(4), p[5], i[3], FP(6), FP(7), FP(8), i[4], i[5], i[6], i[7], p[9], i[13] & 1, (i[13] >> 1) & 1, (i[13] >> 2) & 1, st);      // bits: dA, y, dy
-            return uz_bn_relu_bwd_ex(CFP(0), i[0], CFP(1), i[1], i[2], CFP(2), CFP(3), CFP(4), FP(5), i[3], FP(6), FP(7), i[10] ? nullptr : FP(8), i[4], i[5], i[6], i[7], FP(10), p[9],
-                                     i[11] ? nullptr : CFP(11), i[8], i[9], i[10] ? static_cast<double*>(p[8]) : nullptr, i[11] ? CFP(11) : nullptr, i[11], st);
-        case UZ_OP_RELU_BWD:
-            return uz_relu_bwd(CFP(0), i[0], CFP(1), i[1], i[2], FP(2), i[3], FP(3), i[4], i[5], i[6], FP(5), p[4], st);
-        case UZ_OP_AVGPOOL_FWD:
-            return uz_avgpool2_fwd_ex(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], CFP(2), FP(3), i[6], st);
-        case UZ_OP_AVGPOOL_BWD:
-            if (p[2]) return uz_avgpool2_bwd_relu(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], CFP(2), i[7], static_cast<double*>(p[3]), FP(4), st);
-            return uz_avgpool2_bwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], st);
-        case UZ_OP_BILINEAR_FWD:
-            if (i[13]) return uz_bilinear2x_fwd_b16(CFP(0), i[0], i[1], p[1], i[2], i[3], i[4], i[5], i[6], (i[13] >> 1) & 1, st);      // bf16 storage of the high-resolution output
-            return uz_bilinear2x_fwd_ex(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], CFP(2), FP(3), i[7], st);
-        case UZ_OP_BILINEAR_BWD:
-            if (i[13]) return uz_bilinear2x_bwd_b16(p[0], i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], i[7], i[13] & 1, st);      // bf16 storage of the incoming (high-resolution) gradient
-            if (p[2]) return uz_bilinear2x_bwd_relu(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], i[7], CFP(2), i[8], static_cast<double*>(p[3]), FP(4), st);
-            return uz_bilinear2x_bwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], i[7], st);
-        case UZ_OP_NEAREST_FWD:
-            return uz_nearest_fwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], st);
-        case UZ_OP_NEAREST_BWD:
-            return uz_nearest_bwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], i[7], st);
-        case UZ_OP_SPATIAL_MEAN_FWD:
-            return uz_spatial_mean_fwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], st);
-        case UZ_OP_SPATIAL_MEAN_BWD:
-            return uz_spatial_mean_bwd(CFP(0), i[0], FP(1), i[1], i[2], i[3], i[4], i[5], st);
-        case UZ_OP_POSTERIOR_INPUT:
-            return uz_posterior_input(CFP(0), i[0], CFP(1), i[1], FP(2), i[2], i[3], i[4], st);
-        case UZ_OP_LATENT_FWD:
-            return uz_latent_sample_fwd(CFP(0), CFP(1), CFP(2), FP(3), FP(4), (size_t)o.n, i[0], st);
-        case UZ_OP_LATENT_BWD:
-            return uz_latent_sample_bwd(CFP(0), CFP(1), CFP(2), CFP(3), CFP(4), FP(5), FP(6), (size_t)o.n, i[0], st);
-        case UZ_OP_KL_FWD:
-            return uz_kl_fwd_ws(CFP(0), CFP(1), CFP(2), CFP(3), i[0], i[1], f[0], FP(4), p[5], st);
-        case UZ_OP_KL_BWD:
-            return uz_kl_bwd(CFP(0), CFP(1), CFP(2), CFP(3), i[0], i[1], f[0], CFP(4), FP(5), FP(6), FP(7), FP(8), st);
-        case UZ_OP_CE_FWD:
-            return uz_residual_ce_fwd(static_cast<const float* const*>(p[0]), i[0], i[1], CFP(1), i[2], i[3], i[4], FP(2), p[3], st);
-        case UZ_OP_CE_BWD:
-            return uz_residual_ce_bwd(static_cast<const float* const*>(p[0]), static_cast<float* const*>(p[1]), i[0], i[1], CFP(2), i[2], i[3], i[4], CFP(3), st);
-        case UZ_OP_SUM_TERMS:
-            return uz_sum_terms(CFP(0), i[0], FP(1), st);
-        case UZ_OP_ACC_SOFTMAX_ARGMAX:
-            return uz_accumulate_softmax_argmax(static_cast<const float* const*>(p[0]), i[0], i[1], i[2], i[3], i[4], FP(1), FP(2), static_cast<uint8_t*>(p[3]), st);
-        case UZ_OP_ADAM:
-            return uz_adam_step(FP(0), CFP(1), FP(2), FP(3), (size_t)o.n, (int64_t)i[0], f[0], f[1], f[2], f[3], *reinterpret_cast<const float*>(&i[1]), 1.0f, st);
-        case UZ_OP_AXPY:
-            return uz_axpy(FP(0), CFP(1), f[0], (size_t)o.n, st);
-        case UZ_OP_SCALE:
-            return uz_scale(FP(0), f[0], (size_t)o.n, st);
-        case UZ_OP_L2_NORMS:
-            return uz_l2_norms(CFP(0), static_cast<const int64_t*>(p[1]), i[0], FP(2), st);
-        case UZ_OP_L2_NORMS_BWD:
-            return uz_l2_norms_bwd(CFP(0), static_cast<const int64_t*>(p[1]), i[0], CFP(2), CFP(3), FP(4), st);
-        case UZ_OP_CHAN_SUM_TABLE:
-            return uz_chan_sum_table(static_cast<const int64_t*>(p[0]), i[0], i[1], st);
-        case UZ_OP_WGRAD_REDUCE_TABLE:
-            return uz_wgrad_reduce_table(static_cast<const int64_t*>(p[0]), i[0], i[1], st);
-        case UZ_OP_CHAN_SUM_PARTIALS:
-            return i[2] ? uz_chan_sum_partials_d(static_cast<const double*>(p[0]), i[0], i[1], FP(1), st) : uz_chan_sum_partials(CFP(0), i[0], i[1], FP(1), st);
-        case UZ_OP_PACK_WEIGHTS:
-            return uz_conv_pack_weights(static_cast<const int64_t*>(p[0]), i[0], i[1], CFP(1), st);
-        case UZ_OP_MEMSET:
-            return uz_zero_f32(FP(0), (size_t)o.n / 4, st);               /* n = bytes, always whole floats */
-        case UZ_OP_COPY:
-            return uz_copy_f32(FP(0), CFP(1), (size_t)o.n / 4, st);
-        case UZ_OP_BCAST_CHANNELS:
-            return uz_bcast_channels_fwd(CFP(0), i[0], FP(1), i[1], i[2], i[3], i[4], st);
-        case UZ_OP_BCAST_CHANNELS_BWD:
-            return uz_bcast_channels_bwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], st);
-        case UZ_OP_ABSMAX_COPY:
-            return uz_absmax_copy(CFP(0), FP(1), st);
-        case UZ_OP_W3D_PERMUTE:
-            return uz_w3d_permute(CFP(0), FP(1), i[0], i[1], i[2], st);
-        case UZ_OP_AVGPOOL3D_FWD:
-            if (i[13]) return uz_avgpool3d_fwd_b16(p[0], i[0], i[1], p[1], i[2], i[3], i[4], i[5], i[13] & 1, (i[13] >> 1) & 1, st);
-            return uz_avgpool3d_fwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], st);
-        case UZ_OP_AVGPOOL3D_BWD:
-            if (i[13]) return uz_avgpool3d_bwd_b16(p[0], i[0], i[1], p[1], i[2], i[3], i[4], i[5], i[6], i[13] & 1, (i[13] >> 1) & 1, st);
-            return uz_avgpool3d_bwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], st);
-        case UZ_OP_DEPTH_LERP_FWD:
-            if (i[13]) return uz_depth_lerp2x_fwd_b16(p[0], i[0], i[1], p[1], i[2], i[3], i[4], i[5], i[13] & 1, (i[13] >> 1) & 1, st);
-            return uz_depth_lerp2x_fwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], st);
-        case UZ_OP_DEPTH_LERP_BWD:
-            if (i[13]) return uz_depth_lerp2x_bwd_b16(p[0], i[0], i[1], p[1], i[2], i[3], i[4], i[5], i[6], i[13] & 1, (i[13] >> 1) & 1, st);
-            return uz_depth_lerp2x_bwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], st);
-        case UZ_OP_NEAREST3D_FWD:
-            return uz_nearest3d_fwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], i[7], st);
-        case UZ_OP_NEAREST3D_BWD:
-            return uz_nearest3d_bwd(CFP(0), i[0], i[1], FP(1), i[2], i[3], i[4], i[5], i[6], i[7], i[8], st);
-        case UZ_OP_ADD_VIEWS:
-            return uz_add_views(CFP(0), i[0], CFP(1), i[1], FP(2), i[2], i[3], i[4], i[5], i[6], f[0], i[7], CFP(3), CFP(4), FP(5), st);
-        case UZ_OP_ABSMAX:
-            return uz_absmax(CFP(0), (size_t)o.n, FP(1), st);
-        case UZ_OP_EVENT_RECORD:
-            return uz_event_record(p[0], st);
-        case UZ_OP_LATENT_HEADS_FWD:
-            return uz_latent_heads_fwd(CFP(0), i[0], i[1], CFP(1), CFP(2), CFP(3), CFP(4), CFP(5), FP(6), FP(7), FP(8), FP(9), i[2], i[3], i[4], i[5], i[6], st);
-        case UZ_OP_LATENT_HEADS_BWD_DATA:
-            return uz_latent_heads_bwd_data(CFP(0), CFP(1), i[0], CFP(2), CFP(3), FP(4), i[1], i[2], i[3], i[4], i[5], i[6], st);
-        case UZ_OP_LATENT_HEADS_BWD_WEIGHT:
-            return uz_latent_heads_bwd_weight(CFP(0), i[0], i[1], CFP(1), CFP(2), i[2], FP(3), FP(4), FP(5), FP(6), i[3], i[4], i[5], p[7], (size_t)o.n, st);
-        case UZ_OP_CHAIN:
-            return uz_chain_run(static_cast<const uz_chain_op*>(p[0]), static_cast<const int32_t*>(p[1]), i[0], i[2], i[1], p[2], st);
-        case UZ_OP_CHAIN_PACK:
-            return uz_chain_pack_weights(static_cast<const int64_t*>(p[0]), i[0], i[1], CFP(1), st);
+                                I(nslab), uz_conv_bwd_weight_slabs(I(cin), I(cout), I(N), I(H), I(W), I(ks)));
+            if (I(b16) && I(ks) == 1) return uz_conv1x1_bwd_weight_b16(P(x), I(cin), I(ctot_x), CFP(dy), I(cout), I(ctot_dy), FP(dw), FP(db), I(N), I(H), I(W), P(workspace), n, B16(x), st);
+            if (I(b16)) return uz_conv_bwd_weight_b16(P(x), I(cin), I(ctot_x), P(dy), I(cout), I(ctot_dy), FP(dw), I(N), I(H), I(W), I(ks), P(workspace), n, B16(x), B16(dy), I(slabs_only) ? FP(slabs) : nullptr, st);
+            return uz_conv_bwd_weight_ex(CFP(x), I(cin), I(ctot_x), CFP(dy), I(cout), I(ctot_dy), FP(dw), FP(db), I(N), I(H), I(W), I(ks), CFP(x_amax), CFP(dy_amax), P(workspace), n,
+                                         I(x_packed), CFP(x_amax2), I(x_seg2_c0), I(dy_packed), I(slabs_only) ? FP(slabs) : nullptr, st);
+        }
+        case UZ_OP_BN_RELU_FWD: { using namespace slot::BN_RELU_FWD;
+            if (I(b16)) return uz_bn_relu_fwd_b16(P(y), I(C), I(ctot_y), CFP(gamma), CFP(beta), FP(running_mean), FP(running_var), FP(save), P(a), I(ctot_a), I(N), I(H), I(W), F(eps), F(momentum), I(training), I(relu), P(workspace), CFP(bn_partials), I(npart), B16(y), B16(a), st);
+            if (I(nslab) > 1) return uz_bn_relu_fwd_slabs(CFP(slabs), I(nslab), CFP(conv_bias), FP(y), I(C), I(ctot_y), CFP(gamma), CFP(beta), FP(running_mean), FP(running_var), FP(save), FP(a), I(ctot_a), I(N), I(H), I(W), F(eps), F(momentum), I(training), I(relu), FP(a_amax), st);
+            // phase (Plan._bn_offchain_pass): 1 statistics only, 2 apply only
+            if (I(phase)) return uz_bn_relu_fwd_phase(CFP(y), I(C), I(ctot_y), CFP(gamma), CFP(beta), FP(running_mean), FP(running_var), FP(save), FP(a), I(ctot_a), I(N), I(H), I(W), F(eps), F(momentum), I(relu), FP(a_amax), CFP(bn_partials), I(npart), I(a_packed), I(phase), st);
+            // (save holds 4 C floats in plans; a_packed = write the activation as split storage)
+            return uz_bn_relu_fwd_ex(CFP(y), I(C), I(ctot_y), CFP(gamma), CFP(beta), FP(running_mean), FP(running_var), FP(save), FP(a), I(ctot_a), I(N), I(H), I(W), F(eps), F(momentum), I(training), I(relu), FP(a_amax), P(workspace), CFP(bn_partials), I(npart), I(a_packed), st);
+        }
+        case UZ_OP_BN_RELU_BWD: { using namespace slot::BN_RELU_BWD;
+            // da_partials / npart = reduction partials left by the data gradient that wrote dA last, dy_packed = write dy as split storage
+            // dbias_rows: dbias holds the rows for the conv-bias gradient's partial sums instead of the gradient itself (added by UZ_OP_CHAN_SUM_TABLE)
+            // nslab > 0: da_partials holds that many split-K slabs of dA left by the data gradient (small planes) instead of reduction partials
+            if (I(b16)) return uz_bn_relu_bwd_b16(P(da), I(ctot_da), P(y), I(C), I(ctot_y), CFP(gamma), CFP(beta), CFP(save), P(dy), I(ctot_dy), FP(dgamma), FP(dbeta), FP(dbias), I(N), I(H), I(W), I(relu), P(workspace), B16(da), B16(y), B16(dy), st);
+            return uz_bn_relu_bwd_ex(CFP(da), I(ctot_da), CFP(y), I(C), I(ctot_y), CFP(gamma), CFP(beta), CFP(save), FP(dy), I(ctot_dy), FP(dgamma), FP(dbeta), I(dbias_rows) ? nullptr : FP(dbias), I(N), I(H), I(W), I(relu), FP(dy_amax), P(workspace),
+                                     I(nslab) ? nullptr : CFP(da_partials), I(npart), I(dy_packed), I(dbias_rows) ? static_cast<double*>(P(dbias)) : nullptr, I(nslab) ? CFP(da_partials) : nullptr, I(nslab), st);
+        }
+        case UZ_OP_RELU_BWD: { using namespace slot::RELU_BWD;
+            return uz_relu_bwd(CFP(da), I(ctot_da), CFP(a), I(C), I(ctot_a), FP(dy), I(ctot_dy), FP(dbias), I(N), I(H), I(W), FP(dy_amax), P(workspace), st);
+        }
+        case UZ_OP_AVGPOOL_FWD: { using namespace slot::AVGPOOL_FWD;
+            return uz_avgpool2_fwd_ex(CFP(x), I(C), I(ctot_x), FP(y), I(ctot_y), I(N), I(H), I(W), CFP(x_amax), FP(y_amax), I(y_packed), st);
+        }
+        case UZ_OP_AVGPOOL_BWD: { using namespace slot::AVGPOOL_BWD;
+            if (P(a)) return uz_avgpool2_bwd_relu(CFP(dy), I(C), I(ctot_dy), FP(dx), I(ctot_dx), I(N), I(H), I(W), I(accumulate), CFP(a), I(ctot_a), static_cast<double*>(P(partials)), FP(dx_amax), st);
+            return uz_avgpool2_bwd(CFP(dy), I(C), I(ctot_dy), FP(dx), I(ctot_dx), I(N), I(H), I(W), I(accumulate), st);
+        }
+        case UZ_OP_BILINEAR_FWD: { using namespace slot::BILINEAR_FWD;
+            if (I(b16)) return uz_bilinear2x_fwd_b16(CFP(x), I(C), I(ctot_x), P(y), I(ctot_y), I(N), I(H), I(W), I(align_corners), B16(y), st);      // bf16 storage of the high-resolution output
+            return uz_bilinear2x_fwd_ex(CFP(x), I(C), I(ctot_x), FP(y), I(ctot_y), I(N), I(H), I(W), I(align_corners), CFP(x_amax), FP(y_amax), I(y_packed), st);
+        }
+        case UZ_OP_BILINEAR_BWD: { using namespace slot::BILINEAR_BWD;
+            if (I(b16)) return uz_bilinear2x_bwd_b16(P(dy), I(C), I(ctot_dy), FP(dx), I(ctot_dx), I(N), I(H), I(W), I(align_corners), I(accumulate), B16(dy), st);      // bf16 storage of the incoming (high-resolution) gradient
+            if (P(a)) return uz_bilinear2x_bwd_relu(CFP(dy), I(C), I(ctot_dy), FP(dx), I(ctot_dx), I(N), I(H), I(W), I(align_corners), I(accumulate), CFP(a), I(ctot_a), static_cast<double*>(P(partials)), FP(dx_amax), st);
+            return uz_bilinear2x_bwd(CFP(dy), I(C), I(ctot_dy), FP(dx), I(ctot_dx), I(N), I(H), I(W), I(align_corners), I(accumulate), st);
+        }
+        case UZ_OP_NEAREST_FWD: { using namespace slot::NEAREST_FWD;
+            return uz_nearest_fwd(CFP(x), I(C), I(ctot_x), FP(y), I(ctot_y), I(N), I(H), I(W), I(factor), st);
+        }
+        case UZ_OP_NEAREST_BWD: { using namespace slot::NEAREST_BWD;
+            return uz_nearest_bwd(CFP(dy), I(C), I(ctot_dy), FP(dx), I(ctot_dx), I(N), I(H), I(W), I(factor), I(accumulate), st);
+        }
+        case UZ_OP_SPATIAL_MEAN_FWD: { using namespace slot::SPATIAL_MEAN_FWD;
+            return uz_spatial_mean_fwd(CFP(x), I(C), I(ctot_x), FP(y), I(N), I(H), I(W), st);
+        }
+        case UZ_OP_SPATIAL_MEAN_BWD: { using namespace slot::SPATIAL_MEAN_BWD;
+            return uz_spatial_mean_bwd(CFP(dy), I(C), FP(dx), I(ctot_dx), I(N), I(H), I(W), I(accumulate), st);
+        }
+        case UZ_OP_POSTERIOR_INPUT: { using namespace slot::POSTERIOR_INPUT;
+            return uz_posterior_input(CFP(patch), I(C), CFP(mask), I(nlabels), FP(out), I(N), I(H), I(W), st);
+        }
+        case UZ_OP_LATENT_FWD: { using namespace slot::LATENT_FWD;
+            return uz_latent_sample_fwd(CFP(mu), CFP(pre), CFP(eps), FP(sigma), FP(z), n, I(act), st);
+        }
+        case UZ_OP_LATENT_BWD: { using namespace slot::LATENT_BWD;
+            return uz_latent_sample_bwd(CFP(kl_dmu), CFP(kl_dsigma), CFP(dz), CFP(eps), CFP(sigma), FP(dmu), FP(dpre), n, I(act), st);
+        }
+        case UZ_OP_KL_FWD: { using namespace slot::KL_FWD;
+            return uz_kl_fwd_ws(CFP(q_mu), CFP(q_sigma), CFP(p_mu), CFP(p_sigma), I(n), I(per), F(weight), FP(term), P(workspace), st);
+        }
+        case UZ_OP_KL_BWD: { using namespace slot::KL_BWD;
+            return uz_kl_bwd(CFP(q_mu), CFP(q_sigma), CFP(p_mu), CFP(p_sigma), I(n), I(per), F(weight), CFP(scale), FP(dq_mu), FP(dq_sigma), FP(dp_mu), FP(dp_sigma), st);
+        }
+        case UZ_OP_CE_FWD: { using namespace slot::CE_FWD;
+            return uz_residual_ce_fwd(static_cast<const float* const*>(P(logits)), I(L), I(K), CFP(mask), I(N), I(H), I(W), FP(terms), P(workspace), st);
+        }
+        case UZ_OP_CE_BWD: { using namespace slot::CE_BWD;
+            return uz_residual_ce_bwd(static_cast<const float* const*>(P(logits)), static_cast<float* const*>(P(dlogits)), I(L), I(K), CFP(mask), I(N), I(H), I(W), CFP(scale), st);
+        }
+        case UZ_OP_SUM_TERMS: { using namespace slot::SUM_TERMS;
+            return uz_sum_terms(CFP(terms), I(n), FP(total), st);
+        }
+        case UZ_OP_ACC_SOFTMAX_ARGMAX: { using namespace slot::ACC_SOFTMAX_ARGMAX;
+            return uz_accumulate_softmax_argmax(static_cast<const float* const*>(P(logits)), I(L), I(K), I(N), I(H), I(W), FP(acc), FP(soft), static_cast<uint8_t*>(P(label)), st);
+        }
+        case UZ_OP_ADAM: { using namespace slot::ADAM;
+            return uz_adam_step(FP(params), CFP(grads), FP(exp_avg), FP(exp_avg_sq), n, (int64_t)I(step), F(beta1), F(beta2), F(eps), F(weight_decay), *reinterpret_cast<const float*>(&I(lr_bits)), 1.0f, st);
+        }
+        case UZ_OP_AXPY: { using namespace slot::AXPY;
+            return uz_axpy(FP(y), CFP(x), F(alpha), n, st);
+        }
+        case UZ_OP_SCALE: { using namespace slot::SCALE;
+            return uz_scale(FP(x), F(alpha), n, st);
+        }
+        case UZ_OP_L2_NORMS: { using namespace slot::L2_NORMS;
+            return uz_l2_norms(CFP(params), static_cast<const int64_t*>(P(table)), I(n), FP(norms), st);
+        }
+        case UZ_OP_L2_NORMS_BWD: { using namespace slot::L2_NORMS_BWD;
+            return uz_l2_norms_bwd(CFP(params), static_cast<const int64_t*>(P(table)), I(n), CFP(norms), CFP(scale), FP(grads), st);
+        }
+        case UZ_OP_CHAN_SUM_TABLE: { using namespace slot::CHAN_SUM_TABLE;
+            return uz_chan_sum_table(static_cast<const int64_t*>(P(table)), I(n_entries), I(max_channels), st);
+        }
+        case UZ_OP_WGRAD_REDUCE_TABLE: { using namespace slot::WGRAD_REDUCE_TABLE;
+            return uz_wgrad_reduce_table(static_cast<const int64_t*>(P(table)), I(n_layers), I(total_blocks), st);
+        }
+        case UZ_OP_CHAN_SUM_PARTIALS: { using namespace slot::CHAN_SUM_PARTIALS;
+            return I(doubles) ? uz_chan_sum_partials_d(static_cast<const double*>(P(partials)), I(n_rows), I(C), FP(out), st) : uz_chan_sum_partials(CFP(partials), I(n_rows), I(C), FP(out), st);
+        }
+        case UZ_OP_PACK_WEIGHTS: { using namespace slot::PACK_WEIGHTS;
+            return uz_conv_pack_weights(static_cast<const int64_t*>(P(table)), I(n_layers), I(total_rows), CFP(w_amax), st);
+        }
+        case UZ_OP_MEMSET: { using namespace slot::MEMSET;
+            return uz_zero_f32(FP(dst), n / 4, st);               /* n = bytes, always whole floats */
+        }
+        case UZ_OP_COPY: { using namespace slot::COPY;
+            return uz_copy_f32(FP(dst), CFP(src), n / 4, st);
+        }
+        case UZ_OP_BCAST_CHANNELS: { using namespace slot::BCAST_CHANNELS;
+            return uz_bcast_channels_fwd(CFP(z), I(L), FP(out), I(ctot_out), I(N), I(H), I(W), st);
+        }
+        case UZ_OP_BCAST_CHANNELS_BWD: { using namespace slot::BCAST_CHANNELS_BWD;
+            return uz_bcast_channels_bwd(CFP(dout), I(ctot_dout), I(L), FP(dz), I(N), I(H), I(W), st);
+        }
+        case UZ_OP_ABSMAX_COPY: { using namespace slot::ABSMAX_COPY;
+            return uz_absmax_copy(CFP(src_slot), FP(dst_slot), st);
+        }
+        case UZ_OP_W3D_PERMUTE: { using namespace slot::W3D_PERMUTE;
+            return uz_w3d_permute(CFP(src), FP(dst), I(cout), I(cin), I(mode), st);
+        }
+        case UZ_OP_AVGPOOL3D_FWD: { using namespace slot::AVGPOOL3D_FWD;
+            if (I(b16)) return uz_avgpool3d_fwd_b16(P(x), I(C), I(ctot_x), P(y), I(ctot_y), I(D), I(H), I(W), B16(x), B16(y), st);
+            return uz_avgpool3d_fwd(CFP(x), I(C), I(ctot_x), FP(y), I(ctot_y), I(D), I(H), I(W), st);
+        }
+        case UZ_OP_AVGPOOL3D_BWD: { using namespace slot::AVGPOOL3D_BWD;
+            if (I(b16)) return uz_avgpool3d_bwd_b16(P(dy), I(C), I(ctot_dy), P(dx), I(ctot_dx), I(D), I(H), I(W), I(accumulate), B16(dy), B16(dx), st);
+            return uz_avgpool3d_bwd(CFP(dy), I(C), I(ctot_dy), FP(dx), I(ctot_dx), I(D), I(H), I(W), I(accumulate), st);
+        }
+        case UZ_OP_DEPTH_LERP_FWD: { using namespace slot::DEPTH_LERP_FWD;
+            if (I(b16)) return uz_depth_lerp2x_fwd_b16(P(x), I(C), I(ctot_x), P(y), I(ctot_y), I(D), I(H), I(W), B16(x), B16(y), st);
+            return uz_depth_lerp2x_fwd(CFP(x), I(C), I(ctot_x), FP(y), I(ctot_y), I(D), I(H), I(W), st);
+        }
+        case UZ_OP_DEPTH_LERP_BWD: { using namespace slot::DEPTH_LERP_BWD;
+            if (I(b16)) return uz_depth_lerp2x_bwd_b16(P(dy), I(C), I(ctot_dy), P(dx), I(ctot_dx), I(D), I(H), I(W), I(accumulate), B16(dy), B16(dx), st);
+            return uz_depth_lerp2x_bwd(CFP(dy), I(C), I(ctot_dy), FP(dx), I(ctot_dx), I(D), I(H), I(W), I(accumulate), st);
+        }
+        case UZ_OP_NEAREST3D_FWD: { using namespace slot::NEAREST3D_FWD;
+            return uz_nearest3d_fwd(CFP(x), I(C), I(ctot_x), FP(y), I(ctot_y), I(D), I(H), I(W), I(factor), I(factor_z), st);
+        }
+        case UZ_OP_NEAREST3D_BWD: { using namespace slot::NEAREST3D_BWD;
+            return uz_nearest3d_bwd(CFP(dy), I(C), I(ctot_dy), FP(dx), I(ctot_dx), I(D), I(H), I(W), I(factor), I(factor_z), I(accumulate), st);
+        }
+        case UZ_OP_ADD_VIEWS: { using namespace slot::ADD_VIEWS;
+            return uz_add_views(CFP(a), I(ctot_a), CFP(b), I(ctot_b), FP(y), I(ctot_y), I(C), I(N), I(H), I(W), F(alpha), I(accumulate), CFP(a_amax), CFP(b_amax), FP(y_amax), st);
+        }
+        case UZ_OP_ABSMAX: { using namespace slot::ABSMAX;
+            return uz_absmax(CFP(src), n, FP(slot), st);
+        }
+        case UZ_OP_EVENT_RECORD: { using namespace slot::EVENT_RECORD;
+            return uz_event_record(P(event), st);
+        }
+        case UZ_OP_LATENT_HEADS_FWD: { using namespace slot::LATENT_HEADS_FWD;
+            return uz_latent_heads_fwd(CFP(h), I(cin), I(ctot_h), CFP(w_mu), CFP(b_mu), CFP(w_sigma), CFP(b_sigma), CFP(eps), FP(mu), FP(pre), FP(sigma), FP(z), I(L), I(N), I(H), I(W), I(act), st);
+        }
+        case UZ_OP_LATENT_HEADS_BWD_DATA: { using namespace slot::LATENT_HEADS_BWD_DATA;
+            return uz_latent_heads_bwd_data(CFP(dy_a), CFP(dy_b), I(L), CFP(w_a), CFP(w_b), FP(dh), I(cin), I(ctot_h), I(N), I(H), I(W), I(accumulate), st);
+        }
+        case UZ_OP_LATENT_HEADS_BWD_WEIGHT: { using namespace slot::LATENT_HEADS_BWD_WEIGHT;
+            return uz_latent_heads_bwd_weight(CFP(h), I(cin), I(ctot_h), CFP(dy_a), CFP(dy_b), I(L), FP(dw_a), FP(db_a), FP(dw_b), FP(db_b), I(N), I(H), I(W), P(workspace), n, st);
+        }
+        case UZ_OP_CHAIN: { using namespace slot::CHAIN;
+            return uz_chain_run(static_cast<const uz_chain_op*>(P(ops)), static_cast<const int32_t*>(P(phases)), I(n_phases), I(n_sub_ops), I(n_workgroups), P(state), st);
+        }
+        case UZ_OP_CHAIN_PACK: { using namespace slot::CHAIN_PACK;
+            return uz_chain_pack_weights(static_cast<const int64_t*>(P(table)), I(n_layers), I(total_blocks), CFP(w_amax), st);
+        }
         default:
             return uz::fail("run_tape: unknown op code %d", o.code);
     }
+}
+#undef I
+#undef F
+#undef P
 #undef FP
 #undef CFP
-}
+#undef B16
 
 extern "C" int uz_run_tape(const uz_op* ops, int n_ops, void* stream) {
     for (int k = 0; k < n_ops; ++k) {
