@@ -710,6 +710,56 @@ int    uz_augment_volume(const float* img, const uint8_t* lbl, int C, int X, int
                          float* x_out, float* y_eval, uint8_t* y_raw, void* stream);
 int    uz_augment_volume_route(int C, int X, int Y, int Z, int align_img, int* out2);
 
+/* ---------------------------------------------------------------- volume scores (data/bratsUtils.py:6-24,57-84)
+ * The numbers a BraTS validation reports, of label volumes that are already in HBM (PHISeg3D.predict's samples and mean label, the
+ * y_raw of uz_augment_volume).  All volumes are (D, H, W) uint8, W fastest, unit voxel spacing (the reference passes none).
+ *
+ * uz_vol_edt_sq: d2[v] = min over the voxels u with seeds[u] != 0 of |v - u|^2, an EXACT integer, INT32_MAX everywhere when no voxel
+ * is a seed.  Replaces scipy.ndimage.distance_transform_edt(~seeds) inside MedPy 0.4.0's __surface_distances (bratsUtils.py:78-79),
+ * which getHd95 runs on the host twice per region and sample.  Three separable passes, W, H, D, all in unsigned integer arithmetic:
+ * the W pass is two scans per row (one wave per row), the H and D passes evaluate out[i] = min_j (g[j] + (i - j)^2) directly from a
+ * tile of 64 neighbouring columns x up to 128 axis positions in LDS (a longer axis is walked in chunks of 128 j).  The sentinel of "no
+ * seed" between the passes is 2^30 and every pass clamps what it stores to it, so g[j] + (i - j)^2 < 2^31 as long as
+ * D^2 + H^2 + W^2 <= 2^30: that is the limit (240 x 240 x 155: 139 225).  `workspace`: uz_vol_edt_sq_workspace bytes (one int32 volume),
+ * 4-byte aligned like d2.  Refused (-1, nothing written): a null pointer, an empty axis, D*H*W >= 2^31, the limit above, misalignment.
+ *
+ * uz_vol_region_scores: N label volumes pred (N, D, H, W) against ONE label volume ref for R regions.  A region is a SET of label
+ * values, a bit mask in HOST memory: the voxel with label v belongs to region r of pred when bit v of pred_sets[r] is 1 (ref_sets[r]
+ * for ref); a value >= 32 belongs to no region.  Raw BraTS labels: WT = bits {1, 2, 4}, TC = {1, 4}, ET = {4} (getWTMask / getTCMask /
+ * getETMask, bratsUtils.py:86-93).  Outputs, row n, region r:
+ *   counts (N, R, 4) int64 = {tp, |pred|, |ref|, P = D*H*W}, exact (integer atomics);
+ *   scores (N, R, 4) fp64  = {dice, sensitivity, specificity, hd95}, each from the integer counts with one fp64 division:
+ *     dice        = 2 tp / (|pred| + |ref|), 1 when both are empty (bratsUtils.py:19-21 with the NaN fix of :15);
+ *     sensitivity = tp / |ref|, 1 when |ref| = 0 (:57-65);
+ *     specificity = (P - |pred| - |ref| + tp) / (P - |ref|) (:67-72); NaN when |ref| = P, as the reference's 0 / 0 is;
+ *     hd95        = bratsUtils.py:74-84: -1 when |pred| = 0 or |ref| = 0; else numpy.percentile(., 95) (linear rule: h = 0.95 (n - 1),
+ *                   lo = floor(h), v[lo] + (h - lo)(v[lo + 1] - v[lo]) in fp64) of the n surface distances of both directions together:
+ *                   sqrt(d2) of the ref border's transform at the voxels of the pred border, and the reverse.  The border of a mask
+ *                   is its voxels with one of the six face neighbours outside the mask or outside the volume (binary_erosion with
+ *                   connectivity 1 and border_value 0).  The two order statistics are found exactly: an integer histogram over d2
+ *                   (per-workgroup LDS part for d2 < 1024, integer atomics beyond it) and a prefix walk.
+ *   Exactness: the reference sums 0 / 1 floats in fp32 and is therefore inexact above 2^24 voxels of a region; this call is exact
+ *   there and equal to the reference below that size.  No float atomics anywhere: a repeated call is bit-equal.
+ * The reference border's transform is built once per region and shared by the N rows: a call with want_hd95 runs R (N + 1)
+ * transforms.  With want_hd95 == 0 no transform runs, the workspace shrinks to 16 bytes and the hd95 column is NaN.
+ * `workspace`: uz_vol_region_scores_workspace bytes (three int32 volumes and the histogram), 16-byte aligned.
+ * Refused (-1, uz_last_error names the reason, nothing written): a null pointer (scores, counts and workspace are all required),
+ * N < 1 or N > UZ_VOL_MAX_ROWS, R < 1 or R > UZ_VOL_MAX_REGIONS, the size limits of uz_vol_edt_sq, with want_hd95
+ * D^2 + H^2 + W^2 > UZ_VOL_HD95_MAX_SQ (the histogram has one bin per squared distance), a workspace off 16 bytes, counts or scores
+ * off 8.  The *_workspace functions return 0 for such sizes.
+ * uz_vol_region_scores_route (host only, like uz_vol_route) answers from the predicates the launches use: out4[0], out4[1] = form of
+ * the H and the D pass of a transform of this volume (0 the whole axis in one LDS tile, 1 chunks of 128), out4[2] = workgroups of
+ * the widest launch of the call (pointers taken as 4-byte aligned), out4[3] = transforms the call runs: R (N + 1), or 0 without hd95. */
+#define UZ_VOL_MAX_REGIONS 8
+#define UZ_VOL_MAX_ROWS 65536
+#define UZ_VOL_HD95_MAX_SQ (1 << 22)
+size_t uz_vol_edt_sq_workspace(int D, int H, int W);
+int    uz_vol_edt_sq(const uint8_t* seeds, int D, int H, int W, int32_t* d2, void* workspace, void* stream);
+size_t uz_vol_region_scores_workspace(int N, int R, int D, int H, int W, int want_hd95);
+int    uz_vol_region_scores(const uint8_t* pred, int N, const uint32_t* pred_sets, const uint8_t* ref, const uint32_t* ref_sets, int R,
+                            int D, int H, int W, int want_hd95, void* workspace, int64_t* counts, double* scores, void* stream);
+int    uz_vol_region_scores_route(int N, int R, int D, int H, int W, int want_hd95, int* out4);
+
 /* ---------------------------------------------------------------- volumes (models/phiseg3D.py), one sample
  * A volume is stored [D + 2][C][H][W] (zero slice before and after the D real ones) = a batch of D 2-D images.  Conv3d(3x3x3,
  * pad 1) (phiseg3D.py:24) then is uz_conv_fwd / uz_conv_bwd_* with the depth window as 3 C input channels (pointer = slice d-1,

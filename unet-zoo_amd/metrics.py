@@ -127,3 +127,78 @@ def score_prediction(pred, annotations, return_counts=False):
                                   ncc_pairs.data_ptr() if soft is not None else None, ncc.data_ptr() if soft is not None else None,
                                   dice.data_ptr(), _stream(labels)), "score_samples")
     return Scores(ged=ged, dice=dice, ncc=ncc if soft is not None else None, ncc_pairs=ncc_pairs, counts=counts, packed=packed)
+
+
+# --------------------------------------------------------------------------- N label volumes against one reference: the BraTS region scores
+BRATS_REGIONS = ((1, 2, 4), (1, 4), (4,))          # raw BraTS labels: whole tumour, tumour core, enhancing tumour (bratsUtils.py:86-93)
+BRATS_REGION_NAMES = ("WT", "TC", "ET")
+
+VolumeScores = collections.namedtuple("VolumeScores", "dice sensitivity specificity hd95 counts")
+VolumeScores.__doc__ = """What score_volume returns, all on the device: dice, sensitivity, specificity, hd95 (N, R) fp64 - views of one (N, R, 4)
+buffer - and counts (N, R, 4) int64 = {tp, |pred|, |ref|, voxels}.  hd95 is -1 where a mask is empty and NaN when it was not asked for."""
+
+_volume_ws = {}                                     # workspace per (device, N, R, D, H, W, hd95): every call runs on the caller's current stream
+
+
+def _region_sets(regions, what):
+    sets = []
+    for reg in regions:
+        m = 0
+        for v in reg:
+            v = int(v)
+            if not 0 <= v < 32:
+                raise ValueError(f"{what}: label value {v} in region {tuple(reg)} - a region is a set of values 0 .. 31")
+            m |= 1 << v
+        sets.append(m)
+    return sets
+
+
+def score_volume(pred, reference, pred_regions, ref_regions=None, hd95=True):
+    """Dice, sensitivity, specificity and HD95 (bratsUtils.py:6-24,57-84) of N label volumes against ONE reference volume, for R regions
+    given as sequences of label-value tuples (BRATS_REGIONS for raw BraTS labels; ref_regions defaults to pred_regions, give both when the
+    prediction's labels are class indices and the reference's raw values) - one uz_vol_region_scores call (csrc/volscore.hip): no host
+    round trip, no synchronisation.  pred: a Prediction of PHISeg3D.predict - the rows are its S samples, then mean_label, N = S + 1 - or
+    a uint8 tensor (N, D, H, W); reference: uint8 (D, H, W) on the same device, for instance the y_raw of BratsDataset.  Returns a
+    VolumeScores of device tensors."""
+    if hasattr(pred, "labels") and hasattr(pred, "mean_label"):
+        labels, mean_label = pred.labels, pred.mean_label
+        if labels.dtype != torch.uint8 or mean_label.dtype != torch.uint8:
+            raise TypeError("Prediction.labels and Prediction.mean_label must be uint8")
+        if labels.dim() != 5 or int(labels.shape[1]) != 1 or tuple(mean_label.shape) != tuple(labels.shape[1:]):
+            raise ValueError(f"Prediction of one volume expected: labels (S, 1, D, H, W) and mean_label (1, D, H, W), got {tuple(labels.shape)} and {tuple(mean_label.shape)}")
+        rows = torch.cat([labels[:, 0], mean_label], 0)
+    else:
+        rows = pred
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8:
+            raise TypeError("pred must be a Prediction or a uint8 tensor (N, D, H, W)")
+        if rows.dim() != 4:
+            raise ValueError(f"pred {tuple(rows.shape)} is not (N, D, H, W)")
+    if not isinstance(reference, torch.Tensor) or reference.dtype != torch.uint8:
+        raise TypeError("reference must be a uint8 tensor (D, H, W)")
+    if tuple(reference.shape) != tuple(rows.shape[1:]):
+        raise ValueError(f"reference {tuple(reference.shape)} does not match the volumes {tuple(rows.shape[1:])} of pred")
+    if reference.device != rows.device:
+        raise ValueError("reference must be on the device of pred")
+    ref_regions = pred_regions if ref_regions is None else ref_regions
+    if len(ref_regions) != len(pred_regions):
+        raise ValueError(f"{len(pred_regions)} regions of pred against {len(ref_regions)} of the reference")
+    psets, rsets = _region_sets(pred_regions, "pred_regions"), _region_sets(ref_regions, "ref_regions")
+    N, D, H, W = (int(d) for d in rows.shape)
+    R = len(psets)
+    L, dev = _ffi.lib(), rows.device
+    nbytes = L.uz_vol_region_scores_workspace(N, R, D, H, W, int(bool(hd95)))
+    if nbytes == 0:
+        raise _ffi.UzError(f"score_volume: sizes refused (N {N} R {R} volume {D} x {H} x {W}; 1 <= R <= 8, D*H*W < 2^31, "
+                           "D^2 + H^2 + W^2 <= 2^22 with hd95)")
+    rows, reference = rows.contiguous(), reference.contiguous()
+    key = (dev, N, R, D, H, W, bool(hd95))
+    ws = _volume_ws.get(key)
+    if ws is None:
+        _volume_ws.clear()                           # one shape at a time: a validation loop scores volumes of one size
+        ws = _volume_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    scores = torch.empty(N, R, 4, dtype=torch.float64, device=dev)
+    counts = torch.empty(N, R, 4, dtype=torch.int64, device=dev)
+    U32 = C.c_uint32 * R
+    _ffi.check(L.uz_vol_region_scores(rows.data_ptr(), N, U32(*psets), reference.data_ptr(), U32(*rsets), R, D, H, W, int(bool(hd95)),
+                                      ws.data_ptr(), counts.data_ptr(), scores.data_ptr(), _stream(rows)), "vol_region_scores")
+    return VolumeScores(dice=scores[..., 0], sensitivity=scores[..., 1], specificity=scores[..., 2], hd95=scores[..., 3], counts=counts)
