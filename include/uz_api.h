@@ -434,6 +434,39 @@ int uz_vol_sample_accum(const float* const* s_ptrs, const int* ctot, const int* 
                         uint8_t* labels, float* soft, double* acc, int first, void* stream);
 int uz_vol_sample_finish(const double* acc, int K, int S, int D, int H, int W,
                          float* mean_soft, uint8_t* mean_label, float* entropy, void* stream);
+/* A whole volume (D, H, W) from overlapping windows (PHISeg3D.predict_volume; csrc/volwindow.hip).  A window has extent
+ * (wd, wh, ww) and origin (oz, oy, ox) >= 0 in the volume and may hang over its far faces; window voxel (z, y, x) is volume voxel
+ * (oz + z, oy + y, ox + x).
+ * uz_vol_window_gather: src (C, D, H, W) fp32, dense -> dst, the C-channel slice of a plan volume [wd][Ctot][wh][ww] (Plan.vol
+ *   layout; the pointer addresses channel 0 of the slice in real slice 0).  Every element of the slice is written once: the
+ *   source voxel, or 0 where the window hangs over the volume.  src is not written.
+ * uz_vol_window_accum, one sample of one window:
+ *   s_ptrs, ctot, f, fz   HOST arrays of L entries, as uz_vol_sample_accum takes them, for a volume of the WINDOW's extent: level l
+ *                         is [wd / fz[l]][ctot[l]][wh / f[l]][ww / f[l]] and window voxel (z, y, x) reads (z / fz, y / f, x / f).
+ *                         The logits are summed in fp32 in the level order of uz_sample_stats; everything behind the sum is fp64
+ *                         (max-shifted softmax p_k).  The inputs are not written.
+ *   tz, ty, tx            DEVICE tables of wd, wh, ww fp64 blend weights; the voxel's weight is (tz[z] * ty[y]) * tx[x]
+ *   acc  (K, D, H, W) fp64, THIS sample's accumulator: acc[k][voxel] += weight * p_k (a product and a sum, each rounded once)
+ *   wsum (D, H, W) fp64: wsum[voxel] += weight when add_weight != 0 - the caller sets it for ONE sample of each window
+ *   Only the window voxels inside the volume are touched.  The caller zeroes acc and wsum before the first window.
+ * uz_vol_window_finish, once, for all S samples: acc (S, K, D, H, W), wsum (D, H, W) ->
+ *   labels (S, D, H, W) uint8 = first maximum of acc_s;  p_s = acc_s / wsum;  soft (S, K, D, H, W) = fp32(p_s), nullable;
+ *   mean = (sum_s p_s) / S, added in the order s = 0 .. S-1;  mean_soft (K, D, H, W) = fp32(mean);  mean_label (D, H, W) = first
+ *   maximum of the unrounded mean, entropy (D, H, W) = -sum_k mean_k ln mean_k (a term with mean_k = 0 is 0); both nullable.
+ * No atomics: launches on one stream serialise the adds to a voxel, so windows fed in a fixed order give the same bits every time.
+ * One element per thread, one form for every shape and alignment.  1 <= K <= 8, 1 <= L <= 8, D H W < 2^31, wd wh ww < 2^31 (gather:
+ * C D H W and wd C wh ww < 2^31).  Refused by the host part before any launch (-1, uz_last_error names the reason, nothing is
+ * written): a null pointer (wsum too, whatever add_weight says), a factor below 1, a window that is not level size x factor,
+ * ctot < K (gather: Ctot < C), an origin below 0, an extent or size below 1.  A voxel that no window reached (wsum == 0) is data the
+ * host part cannot see: uz_vol_window_finish gives it label 0, probabilities 0 and entropy 0 - never NaN; covering the volume is
+ * the caller's duty (models/phiseg3D.py window_grid does).                                                                       */
+int uz_vol_window_gather(const float* src, int C, int D, int H, int W, int oz, int oy, int ox,
+                         float* dst, int Ctot, int wd, int wh, int ww, void* stream);
+int uz_vol_window_accum(const float* const* s_ptrs, const int* ctot, const int* f, const int* fz, int L, int K,
+                        int wd, int wh, int ww, int oz, int oy, int ox, int D, int H, int W,
+                        const double* tz, const double* ty, const double* tx, double* acc, double* wsum, int add_weight, void* stream);
+int uz_vol_window_finish(const double* acc, const double* wsum, int K, int S, int D, int H, int W,
+                         uint8_t* labels, float* soft, float* mean_soft, uint8_t* mean_label, float* entropy, void* stream);
 /* Fcomb (probabilistic_unet.py:185-199) in eval mode for S latent draws per image, features read once (ProbabilisticUnet.predict;
  * csrc/fcomb.hip).
  *   feat      (B, C of CtotF, H, W), C == 32

@@ -29,40 +29,6 @@ __global__ __launch_bounds__(256) void batch_repeat_k(const float* __restrict__ 
     for (int s = 0; s < S; ++s) *reinterpret_cast<T*>(d + (size_t)s * B * strideY) = v;
 }
 
-// The per-voxel arithmetic every statistics kernel below shares.  The logits are summed in fp32 like acc_softmax_argmax_k
-// (pointwise.hip); everything behind the sum is fp64 and rounded once on the way out.  In fp32 a sample that saturates
-// (p = 1 - 1e-10) rounds to exactly 1, and a pixel whose samples saturate in opposite directions ends in an exact tie of its mean
-// probabilities that is none: the mean label would be a coin the first class always wins.
-template <int K>
-__device__ __forceinline__ int sample_softmax(const float (&a)[K], double (&sv)[K]) {
-    float mx = a[0];
-    int best = 0;
-#pragma unroll
-    for (int k = 1; k < K; ++k) {
-        if (a[k] > mx) { mx = a[k]; best = k; }                                     // first maximum wins
-    }
-    double se = 0.0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { sv[k] = exp((double)a[k] - (double)mx); se += sv[k]; }
-#pragma unroll
-    for (int k = 0; k < K; ++k) sv[k] = sv[k] / se;
-    return best;
-}
-// m: the sum of S samples' probabilities.  p = m / S, its first maximum, its entropy (a class no sample gave any weight adds nothing)
-template <int K>
-__device__ __forceinline__ int mean_stats(const double (&m)[K], int S, double (&p)[K], double& h) {
-    int best = 0;
-    double bv = 0.0;
-    h = 0.0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        p[k] = m[k] / (double)S;
-        if (k == 0 || p[k] > bv) { bv = p[k]; best = k; }
-        if (p[k] > 0.0) h -= p[k] * log(p[k]);
-    }
-    return best;
-}
-
 // One thread owns pixel q of image b and walks its S samples in order: consecutive lanes read consecutive floats of every
 // (level, sample, class) plane, the running mean stays in registers, every output is written once.
 // The kernel waits on its loads, K exponentials per sample do not show.
@@ -85,7 +51,7 @@ __global__ __launch_bounds__(64) void sample_stats_k(const float* const* __restr
 #pragma unroll
             for (int k = 0; k < K; ++k) a[k] += sp[l][base + (size_t)k * HW];
         double sv[K];
-        const int best = sample_softmax<K>(a, sv);
+        const int best = uz::sample_softmax<K>(a, sv);
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             m[k] += sv[k];                                                          // ordered: s = 0 .. S-1, bit-repeatable
@@ -94,7 +60,7 @@ __global__ __launch_bounds__(64) void sample_stats_k(const float* const* __restr
         if (labels) labels[row * HW + q] = (uint8_t)best;
     }
     double p[K], h;
-    const int best = mean_stats<K>(m, S, p, h);
+    const int best = uz::mean_stats<K>(m, S, p, h);
 #pragma unroll
     for (int k = 0; k < K; ++k) mean_soft[((size_t)b * K + k) * HW + q] = (float)p[k];
     if (mean_label) mean_label[(size_t)b * HW + q] = (uint8_t)best;
@@ -103,18 +69,14 @@ __global__ __launch_bounds__(64) void sample_stats_k(const float* const* __restr
 
 // ---- volumes.  A level is [D_l][Ctot_l][H_l][W_l] (Plan.vol: the pointer addresses real slice 0); voxel (od, oy, ox) of the full volume
 // reads its element (od / fz, oy / f, ox / f), the index of nearest3d_fwd_k (vol.hip).  The table travels as a kernel argument.
-constexpr int VOL_LEVELS_MAX = 8;
-struct VolLevels {
-    const float* p[VOL_LEVELS_MAX];
-    int ctot[VOL_LEVELS_MAX], f[VOL_LEVELS_MAX], fz[VOL_LEVELS_MAX];
-};
+// (uz::VolLevels, sample_softmax, mean_stats: uz_common.h - shared with volwindow.hip)
 
 // One voxel per thread, consecutive lanes consecutive voxels of a row: the finest level, the label store and the running sum are
 // coalesced; the coarser levels repeat an element over f lanes and come out of cache.  The outputs are dense (K, D, H, W) / (D, H, W).
 // (A form with four voxels per thread - float4 loads, one 4-byte label store, double2 traffic of the sum - was built and measured:
 // 20.0 against 21.5 us for a 128 x 128 x 64 volume, and no gain in the finish kernel, beside 8.4 ms of plan per sample; it was dropped.)
 template <int K>
-__global__ __launch_bounds__(64) void vol_sample_accum_k(VolLevels lv, int L, int D, int H, int W, uint8_t* __restrict__ labels,
+__global__ __launch_bounds__(64) void vol_sample_accum_k(uz::VolLevels lv, int L, int D, int H, int W, uint8_t* __restrict__ labels,
                                                           float* __restrict__ soft, double* __restrict__ acc, int first) {
     const int HW = H * W, n = D * HW;
     const long long q64 = (long long)blockIdx.x * 64 + threadIdx.x;                // (the last workgroup of a 2^31 - 1 voxel volume)
@@ -132,7 +94,7 @@ __global__ __launch_bounds__(64) void vol_sample_accum_k(VolLevels lv, int L, in
         }
     }
     double sv[K];
-    labels[q] = (uint8_t)sample_softmax<K>(a, sv);
+    labels[q] = (uint8_t)uz::sample_softmax<K>(a, sv);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const size_t o = (size_t)k * n + q;
@@ -150,7 +112,7 @@ __global__ __launch_bounds__(64) void vol_sample_finish_k(const double* __restri
     double m[K], p[K], h;
 #pragma unroll
     for (int k = 0; k < K; ++k) m[k] = acc[(size_t)k * n + q];
-    const int best = mean_stats<K>(m, S, p, h);
+    const int best = uz::mean_stats<K>(m, S, p, h);
 #pragma unroll
     for (int k = 0; k < K; ++k) mean_soft[(size_t)k * n + q] = (float)p[k];
     if (mean_label) mean_label[q] = (uint8_t)best;
@@ -164,7 +126,7 @@ void launch_stats(dim3 grid, hipStream_t st, const float* const* sp, int L, int 
 }
 
 template <int K>
-void launch_vol_accum(int groups, hipStream_t st, const VolLevels& lv, int L, int D, int H, int W, uint8_t* labels, float* soft, double* acc, int first) {
+void launch_vol_accum(int groups, hipStream_t st, const uz::VolLevels& lv, int L, int D, int H, int W, uint8_t* labels, float* soft, double* acc, int first) {
     hipLaunchKernelGGL(vol_sample_accum_k<K>, dim3(groups), dim3(64), 0, st, lv, L, D, H, W, labels, soft, acc, first);
 }
 template <int K>
@@ -212,11 +174,11 @@ extern "C" int uz_sample_stats(const float* const* s_ptrs, int L, int K, int B, 
 extern "C" int uz_vol_sample_accum(const float* const* s_ptrs, const int* ctot, const int* f, const int* fz, int L, int K, int D, int H, int W,
                                    uint8_t* labels, float* soft, double* acc, int first, void* stream) {
     UZ_REQUIRE(K >= 1 && K <= 8, "vol_sample_accum: 1..8 classes supported (got %d)", K);
-    UZ_REQUIRE(L >= 1 && L <= VOL_LEVELS_MAX, "vol_sample_accum: 1..8 levels supported (got %d)", L);
+    UZ_REQUIRE(L >= 1 && L <= uz::VOL_LEVELS_MAX, "vol_sample_accum: 1..8 levels supported (got %d)", L);
     UZ_REQUIRE(s_ptrs && ctot && f && fz && labels && acc && D > 0 && H > 0 && W > 0, "vol_sample_accum: bad arguments");
     const long long n = (long long)D * H * W;
     UZ_REQUIRE(n < (1ll << 31), "vol_sample_accum: volume too large");
-    VolLevels lv = {};
+    uz::VolLevels lv = {};
     for (int l = 0; l < L; ++l) {
         UZ_REQUIRE(s_ptrs[l], "vol_sample_accum: level %d is a null pointer", l);
         UZ_REQUIRE(f[l] >= 1 && fz[l] >= 1 && ctot[l] >= K, "vol_sample_accum: level %d: factors below 1 or fewer channels than classes", l);

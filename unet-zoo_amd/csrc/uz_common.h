@@ -104,6 +104,47 @@ __device__ __forceinline__ float ncc_of_sums(const double (&s)[5], int HW) {
     return (float)((s[4] / n - ma * mv) / (sa * sv));
 }
 
+// The per-voxel arithmetic every statistics kernel shares (predict.hip, volwindow.hip).  The logits are summed in fp32 like acc_softmax_argmax_k
+// (pointwise.hip); everything behind the sum is fp64 and rounded once on the way out.  In fp32 a sample that saturates
+// (p = 1 - 1e-10) rounds to exactly 1, and a pixel whose samples saturate in opposite directions ends in an exact tie of its mean
+// probabilities that is none: the mean label would be a coin the first class always wins.
+template <int K>
+__device__ __forceinline__ int sample_softmax(const float (&a)[K], double (&sv)[K]) {
+    float mx = a[0];
+    int best = 0;
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+        if (a[k] > mx) { mx = a[k]; best = k; }                                     // first maximum wins
+    }
+    double se = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { sv[k] = exp((double)a[k] - (double)mx); se += sv[k]; }
+#pragma unroll
+    for (int k = 0; k < K; ++k) sv[k] = sv[k] / se;
+    return best;
+}
+// m: the sum of S samples' probabilities.  p = m / S, its first maximum, its entropy (a class no sample gave any weight adds nothing)
+template <int K>
+__device__ __forceinline__ int mean_stats(const double (&m)[K], int S, double (&p)[K], double& h) {
+    int best = 0;
+    double bv = 0.0;
+    h = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        p[k] = m[k] / (double)S;
+        if (k == 0 || p[k] > bv) { bv = p[k]; best = k; }
+        if (p[k] > 0.0) h -= p[k] * log(p[k]);
+    }
+    return best;
+}
+
+// The level table of the volume statistics kernels (predict.hip, volwindow.hip); it travels as a kernel argument.
+constexpr int VOL_LEVELS_MAX = 8;
+struct VolLevels {
+    const float* p[VOL_LEVELS_MAX];
+    int ctot[VOL_LEVELS_MAX], f[VOL_LEVELS_MAX], fz[VOL_LEVELS_MAX];
+};
+
 // conv_split.hip: 3x3 forward / data gradient on the fp16 matrix pipe with two-piece split operands (fp32-accurate)
 bool conv_split_ok(int Kc, int Mc, int N, int H, int W, int ks, int dgrad);
 size_t conv_split_workspace(int Kc, int Mc, int N, int H, int W);

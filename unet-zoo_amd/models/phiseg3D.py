@@ -13,7 +13,8 @@ First slice, with these limits stated up front:
   * the reference's own forward raises at its last line (:398 hands a 2-element `size` to a 5-D `interpolate`); the evident
     intent - nearest resize of every level to the full volume - is what runs here, and parity is pinned on everything up to
     the un-resized level logits `s_in` (Posterior, prior, Likelihood), which the reference does execute.
-Beyond the reference: predict(patch, n_samples) - samples, mean probabilities and an uncertainty map of a volume without a label mask.
+Beyond the reference: predict(patch, n_samples) - samples, mean probabilities and an uncertainty map of a volume without a label mask -
+and predict_volume(volume, n_samples, window, stride, blend): the same for a volume of any size, from blended windows.
 """
 import ctypes as C
 
@@ -27,6 +28,58 @@ from .phiseg import Prediction
 def phiseg3d_spec(input_channels, num_classes, num_filters, latent_levels, reversible=False):
     nf = list(num_filters)
     return lift3(hier_spec(input_channels, num_classes, num_classes, nf, len(nf), latent_levels, reversible, PHISeg3D.rev_depths))
+
+
+BLENDS = ("gaussian", "uniform")
+
+
+def default_stride(window, g):
+    """Half the window per axis, rounded down to a multiple of g, and at least g."""
+    return tuple(max(g, (int(w) // 2) // g * g) for w in window)
+
+
+def window_grid(dhw, window, stride, g):
+    """The windows predict_volume() visits on a volume of size dhw = (D, H, W); pure host arithmetic.  g = 2^(levels-1): what every
+    side of a plan's volume must divide by.  window: three positive multiples of g; stride: three multiples of g with
+    g <= stride <= window, or None for default_stride.  Per axis of length n, with P = ceil(n / g) g: if P <= w ONE window of extent P
+    at origin 0 (the window shrinks); else windows of extent w at 0, s, 2s, ... < P - w and at P - w.  Returns (padded, extent,
+    origins): the padded size (P_D, P_H, P_W), the extent of every window and the origins (oz, oy, ox) in the order of the visits - D
+    slowest, W fastest.  Every origin is a multiple of g, the windows cover the padded volume and the last one of an axis ends at P."""
+    if g < 1 or g & (g - 1):
+        raise ValueError(f"window_grid: g must be a power of two, got {g}")
+    if len(dhw) != 3 or any(int(n) < 1 for n in dhw):
+        raise ValueError(f"window_grid: the volume needs three sides >= 1, got {tuple(dhw)}")
+    if window is None or len(window) != 3 or any(int(w) != w or w < g or w % g for w in window):
+        raise ValueError(f"window_grid: every side of the window must be a positive multiple of {g}, got {window}")
+    window = tuple(int(w) for w in window)
+    if stride is None:
+        stride = default_stride(window, g)
+    if len(stride) != 3 or any(int(s) != s or s % g or s < g or s > w for s, w in zip(stride, window)):
+        raise ValueError(f"window_grid: every stride must be a multiple of {g} with {g} <= stride <= window {window}, got {tuple(stride)}")
+    padded, extent, axes = [], [], []
+    for n, w, s in zip(dhw, window, stride):
+        P = -(-int(n) // g) * g
+        padded.append(P)
+        if P <= w:
+            extent.append(P)
+            axes.append([0])
+        else:
+            extent.append(w)
+            axes.append(list(range(0, P - w, int(s))) + [P - w])
+    return tuple(padded), tuple(extent), [(z, y, x) for z in axes[0] for y in axes[1] for x in axes[2]]
+
+
+def blend_tables(extent, blend):
+    """Per axis the fp64 weight table of a window of this extent: "gaussian" t[i] = exp(-0.5 ((i - (w - 1) / 2) / (w / 8))^2),
+    "uniform" t[i] = 1.  A voxel's weight is (tz * ty) * tx."""
+    import numpy as np
+    if blend not in BLENDS:
+        raise ValueError(f"blend must be one of {BLENDS}, got {blend!r}")
+    out = []
+    for w in extent:
+        i = np.arange(int(w), dtype=np.float64)
+        out.append(np.exp(-0.5 * ((i - (w - 1) / 2.0) / (w / 8.0)) ** 2) if blend == "gaussian" else np.ones(int(w), np.float64))
+    return out
 
 
 class PHISeg3D(HierarchicalModel):
@@ -145,18 +198,47 @@ class PHISeg3D(HierarchicalModel):
         self.s_in_list = [V(v) for v in io["s_in"]]
         return self._publish(plan)
 
-    def _predict_state(self, draw, D, H, W):
-        """What predict() keeps with its draw plan between calls (plan.host): the fp64 running sum and the host tables of
-        uz_vol_sample_accum - level pointers, channel counts and the two resize factors, finest level first."""
-        st = draw.host.get("vol_stats")
-        if st is None:
+    def _level_tables(self, draw, D, H, W):
+        """The host tables of uz_vol_sample_accum / uz_vol_window_accum for a draw plan of extent (D, H, W), kept with the plan
+        (plan.host): level pointers, channel counts and the two resize factors, finest level first."""
+        tb = draw.host.get("vol_levels")
+        if tb is None:
             lv = draw.io["s_in"]
             n = len(lv)
-            st = draw.host["vol_stats"] = dict(
-                acc=torch.empty(self.num_classes, D, H, W, dtype=torch.float64, device=self.device),
+            tb = draw.host["vol_levels"] = dict(
                 ptrs=(C.c_void_p * n)(*[draw._resolve(v) for v in lv]), ctot=(C.c_int * n)(*[v.Ctot for v in lv]),
                 f=(C.c_int * n)(*[H // v.H for v in lv]), fz=(C.c_int * n)(*[D // v.N for v in lv]))
+        return tb
+
+    def _predict_state(self, draw, D, H, W):
+        """What predict() keeps with its draw plan between calls (plan.host): the fp64 running sum and the level tables."""
+        st = draw.host.get("vol_stats")
+        if st is None:
+            st = draw.host["vol_stats"] = dict(self._level_tables(draw, D, H, W),
+                                               acc=torch.empty(self.num_classes, D, H, W, dtype=torch.float64, device=self.device))
         return st
+
+    def _predict_plans(self, D, H, W):
+        return (self._plan(("trunk", D, H, W), lambda: self._build_predict(D, H, W, "trunk")),
+                self._plan(("draw", D, H, W), lambda: self._build_predict(D, H, W, "draw")))
+
+    def _run_trunk(self, trunk, draw):
+        """The trunk plan on the patch its input holds, and its feature maps handed to the draw plan (predict(), predict_volume())."""
+        L, st = _ffi.lib(), C.c_void_p(self._stream())
+        self._run(trunk, "fwd")
+        for src, dst in zip(trunk.io["feats"], draw.io["feats"]):
+            _ffi.check(L.uz_batch_repeat_fwd(trunk._resolve(src), src.C, src.Ctot, draw._resolve(dst), dst.Ctot, src.N, 1, src.H, src.W, st),
+                       "batch_repeat_fwd")
+
+    def _draw(self, draw, noise):
+        """One sample: the noise - drawn on the device, or `noise`, L tensors (1, 2, d_k, h_k, w_k), deepest first - and the draw plan."""
+        T = draw.tensor
+        for k, e in enumerate(draw.io["eps"]):
+            if noise is None:
+                self._fill_normal(T(e))
+            else:
+                T(e).copy_(self._to_slices(noise[k]))
+        self._run(draw, "fwd")
 
     def predict(self, patch, n_samples=1, eps=None, return_soft=False, return_levels=False):
         """Segment the volume `patch` (1, C, D, H, W) without a label mask: n_samples draws from the prior, from ONE pass of its
@@ -184,27 +266,18 @@ class PHISeg3D(HierarchicalModel):
         self._check_size(D, H, W)
         if eps is not None and len(eps) != nl:
             raise ValueError(f"predict() takes {nl} eps tensors (deepest level first), got {len(eps)}")
-        trunk = self._plan(("trunk", D, H, W), lambda: self._build_predict(D, H, W, "trunk"))
-        draw = self._plan(("draw", D, H, W), lambda: self._build_predict(D, H, W, "draw"))
+        trunk, draw = self._predict_plans(D, H, W)
         L, st = _ffi.lib(), C.c_void_p(self._stream())
         T, io = draw.tensor, draw.io
         trunk.tensor(trunk.io["patch"]).copy_(self._to_slices(patch))
-        self._run(trunk, "fwd")
-        for src, dst in zip(trunk.io["feats"], io["feats"]):
-            _ffi.check(L.uz_batch_repeat_fwd(trunk._resolve(src), src.C, src.Ctot, draw._resolve(dst), dst.Ctot, src.N, 1, src.H, src.W, st),
-                       "batch_repeat_fwd")
+        self._run_trunk(trunk, draw)
         host = self._predict_state(draw, D, H, W)
         out = Prediction(labels=torch.empty(S, 1, D, H, W, dtype=torch.uint8, device=dev), mean_soft=torch.empty(1, K, D, H, W, device=dev),
                          mean_label=torch.empty(1, D, H, W, dtype=torch.uint8, device=dev), entropy=torch.empty(1, D, H, W, device=dev),
                          levels=[torch.empty(S, 1, v.C, v.N, v.H, v.W, device=dev) for v in io["s_in"]] if return_levels else None,
                          soft=torch.empty(S, 1, K, D, H, W, device=dev) if return_soft else None)
         for s in range(S):
-            for k, e in enumerate(io["eps"]):
-                if eps is None:
-                    self._fill_normal(T(e))
-                else:
-                    T(e).copy_(self._to_slices(eps[k][s:s + 1]))
-            self._run(draw, "fwd")
+            self._draw(draw, None if eps is None else [e[s:s + 1] for e in eps])
             _ffi.check(L.uz_vol_sample_accum(host["ptrs"], host["ctot"], host["f"], host["fz"], nl, K, D, H, W, out.labels[s].data_ptr(),
                                              out.soft[s].data_ptr() if return_soft else None, host["acc"].data_ptr(), int(s == 0), st),
                        "vol_sample_accum")
@@ -218,6 +291,88 @@ class PHISeg3D(HierarchicalModel):
         self.prior_mu = [V(io["prior"][k].mu) for k in order]
         self.prior_sigma = [V(io["prior"][k].sigma) for k in order]
         self.prior_latent_space = [V(io["prior_z"][k]) for k in order]
+        return out
+
+    def window_plan(self, dhw, window=None, stride=None):
+        """window_grid() with this model's defaults: window = image_size[1:], stride = half of it (default_stride), g = 2^(levels-1)."""
+        g = 1 << (len(self.num_filters) - 1)
+        if window is None:
+            window = tuple(self.image_size[1:])
+            if len(window) != 3:
+                raise ValueError(f"predict_volume() needs a window: image_size {tuple(self.image_size)} names no (D, H, W)")
+        return window_grid(dhw, window, stride, g)
+
+    def predict_volume(self, volume, n_samples=1, window=None, stride=None, blend="gaussian", eps=None, return_soft=False):
+        """predict() for a volume of ANY size (1, C, D, H, W): the net runs on overlapping windows of the size it was trained at and
+        the windows' probabilities are blended.  window defaults to image_size[1:], stride to half of it; window_grid() says where the
+        windows lie (a window no smaller than the volume rounded up to 2^(levels-1) is the plain pad-to-divisible route: one window),
+        blend_tables() how they are weighted ("gaussian" | "uniform").  Voxels of a window beyond the volume are read as 0 and never
+        written.  The samples are coherent across windows: ONE noise field per latent level is drawn per call - with predict()'s
+        generator, shaped as predict() takes `eps` for the padded volume, n_samples rows - and every window receives its crop; `eps`
+        (L tensors, deepest first, those shapes) injects the fields.  Order of work: per window the gather (uz_vol_window_gather), the
+        trunk plan ONCE and the hand-over of its features, then per sample the noise crop, the draw plan and uz_vol_window_accum; after
+        the last window one uz_vol_window_finish.  The plans are predict()'s, keyed by the window's extent.  Kept with the draw plan
+        between calls and zeroed at the start of each: S accumulators (K, D, H, W) and one weight sum (D, H, W), all fp64 =
+        8 (S K + 1) D H W bytes - the accumulators 3.4 GB, the weight sum 71 MB at 240 x 240 x 155, K = 3, S = 16.  Returns predict()'s Prediction for (D, H, W) (levels = None);
+        sample s: p_s = sum_windows weight * softmax / sum_windows weight, labels its first maximum, mean_soft the mean over the samples,
+        mean_label / entropy from the unrounded mean.  prior_mu / prior_sigma / prior_latent_space are left as they are."""
+        S, nl, K, R = int(n_samples), self.latent_levels, self.num_classes, len(self.num_filters)
+        if S < 1:
+            raise ValueError("predict_volume() needs n_samples >= 1")
+        if volume.dim() != 5 or volume.shape[0] != 1 or volume.shape[1] != self.input_channels:
+            raise ValueError(f"predict_volume() takes one volume (1, {self.input_channels}, D, H, W), got {tuple(volume.shape)}")
+        D, H, W = self._dims(volume)
+        padded, extent, origins = self.window_plan((D, H, W), window, stride)
+        tables = blend_tables(extent, blend)
+        shapes = [(S, 2, *(n >> (R - 1 - k) for n in padded)) for k in range(nl)]             # deepest level first
+        if eps is not None and (len(eps) != nl or [tuple(e.shape) for e in eps] != shapes):
+            raise ValueError(f"predict_volume() takes {nl} eps tensors of the shapes {shapes} (deepest level first), got "
+                             f"{[tuple(e.shape) for e in eps]}")
+        self._require_gpu()
+        if self.training:
+            raise RuntimeError("predict() needs eval mode: with batch statistics the contracting path of a volume is not shared by its samples")
+        if self.reversible:
+            raise NotImplementedError("predict() is not built for the reversible variant")
+        dev = self.device
+        ed, eh, ew = extent
+        trunk, draw = self._predict_plans(ed, eh, ew)
+        L, st = _ffi.lib(), C.c_void_p(self._stream())
+        tb = self._level_tables(draw, ed, eh, ew)
+        state = draw.host.get("vol_window")
+        if state is None or state["key"] != (S, D, H, W):
+            state = None                                                                        # free the old ones first
+            draw.host.pop("vol_window", None)
+            state = draw.host["vol_window"] = dict(key=(S, D, H, W), acc=torch.empty(S, K, D, H, W, dtype=torch.float64, device=dev),
+                                                   wsum=torch.empty(D, H, W, dtype=torch.float64, device=dev))
+        wt = draw.host.setdefault("vol_blend", {}).get(blend)
+        if wt is None:
+            wt = draw.host["vol_blend"][blend] = [torch.from_numpy(t).to(dev) for t in tables]
+        acc, wsum = state["acc"], state["wsum"]
+        acc.zero_()
+        wsum.zero_()
+        src = volume[0].to(torch.float32).contiguous()
+        if eps is None:
+            eps = [self._fill_normal(torch.empty(shape, device=dev)) for shape in shapes]
+        patch = trunk.io["patch"]
+        for oz, oy, ox in origins:
+            _ffi.check(L.uz_vol_window_gather(src.data_ptr(), self.input_channels, D, H, W, oz, oy, ox, trunk._resolve(patch), patch.Ctot,
+                                              ed, eh, ew, st), "vol_window_gather")
+            self._run_trunk(trunk, draw)
+            for s in range(S):
+                noise = []
+                for k, e in enumerate(eps):
+                    sh = R - 1 - k                                                              # origins are multiples of 2^(R-1)
+                    noise.append(e[s:s + 1, :, oz >> sh:(oz + ed) >> sh, oy >> sh:(oy + eh) >> sh, ox >> sh:(ox + ew) >> sh])
+                self._draw(draw, noise)
+                _ffi.check(L.uz_vol_window_accum(tb["ptrs"], tb["ctot"], tb["f"], tb["fz"], nl, K, ed, eh, ew, oz, oy, ox, D, H, W,
+                                                 wt[0].data_ptr(), wt[1].data_ptr(), wt[2].data_ptr(), acc[s].data_ptr(), wsum.data_ptr(),
+                                                 int(s == 0), st), "vol_window_accum")
+        out = Prediction(labels=torch.empty(S, 1, D, H, W, dtype=torch.uint8, device=dev), mean_soft=torch.empty(1, K, D, H, W, device=dev),
+                         mean_label=torch.empty(1, D, H, W, dtype=torch.uint8, device=dev), entropy=torch.empty(1, D, H, W, device=dev),
+                         levels=None, soft=torch.empty(S, 1, K, D, H, W, device=dev) if return_soft else None)
+        _ffi.check(L.uz_vol_window_finish(acc.data_ptr(), wsum.data_ptr(), K, S, D, H, W, out.labels.data_ptr(),
+                                          out.soft.data_ptr() if return_soft else None, out.mean_soft.data_ptr(), out.mean_label.data_ptr(),
+                                          out.entropy.data_ptr(), st), "vol_window_finish")
         return out
 
     def _publish_loss(self, total, terms):
