@@ -78,10 +78,15 @@ int uz_conv_fwd(const float* x, int Cin, int CinTot,
                 void* workspace, size_t workspace_bytes, void* stream);
 /* Weight images of the split path packed ONCE per step for a whole tape (instead of inside every call): the caller keeps a
  * buffer of uz_conv_packed_bytes() per (layer, direction), describes them in a device table of 8 int64 per layer
- * {w address, image address, Mc, Kc, wCi, uz_conv_pack_cot(), dgrad, first row} with rows counted by uz_conv_pack_rows()
+ * {w address, image address, Mc, Kc, wCi, uz_conv_pack_cot(), flags, first row} with rows counted by uz_conv_pack_rows()
  * (Mc / Kc = output / contraction channels of the direction: forward Cout / Cin, data gradient Cin / Cout; wCi = Cin), runs
  * uz_conv_pack_weights once (w_amax = the bound every image is scaled with) and hands each image to the *_packed calls,
- * which are otherwise uz_conv_fwd / uz_conv_bwd_data (packed_w may be NULL: same behaviour as those).                      */
+ * which are otherwise uz_conv_fwd / uz_conv_bwd_data (packed_w may be NULL: same behaviour as those).
+ * flags: bit 0 = data gradient; bit 1 = w is a Conv3d parameter [Cout][C][3][3][3] read straight into the depth-window layout
+ * (volumes section below) - the image uz_w3d_permute mode 0 / mode 1 and a row without the bit would give, byte for byte.
+ * Such a row is sized for the 2-D call of the window: forward Mc = Cout, Kc = 3 C with contraction index k = kd C + ci;
+ * data gradient Mc = C, Kc = 3 Cout with k = j Cout + co and kd = 2 - j, where the kernel takes Cout as Kc / 3.  wCi is the
+ * parameter's own second dimension C in both directions - not the 2-D call's Cin = 3 C.                                     */
 size_t uz_conv_packed_bytes(int Cin, int Cout, int W, int dgrad);
 int uz_conv_pack_rows(int Cin, int Cout, int W, int dgrad);
 int uz_conv_pack_cot(int Cin, int Cout, int W, int dgrad);

@@ -621,7 +621,7 @@ extern "C" int uz_conv_fwd_b16(const void* x, int Cin, int CinTot, const float* 
                                void* y, int Cout, int CoutTot, int N, int H, int W, int ks,
                                void* workspace, size_t workspace_bytes, const void* packed_w, float* bn_partials,
                                int x_b16, int y_b16, void* stream) {
-    UZ_REQUIRE(ks == 3 && uz::conv_np() == 1 && uz_conv_route(0, Cin, Cout, N, H, W, ks) == 1,
+    UZ_REQUIRE(ks == 3 && uz::conv_np() == 1 && uz_conv_route(0, Cin, Cout, N, H, W, ks) == 1 && (!(x_b16 || y_b16) || uz_conv_split_parts(0, Cin, Cout, N, H, W) == 1),
                "conv_fwd_b16: bf16 storage needs uz_set_conv_math(3) and a 3x3 shape on the matrix-pipe path (unsplit chunk loop)");
     UZ_REQUIRE(workspace && workspace_bytes >= uz::conv_split_workspace(Cin, Cout, N, H, W), "conv_fwd_b16: workspace too small");
     UZ_REQUIRE(!bn_partials || uz_conv_bn_partials(Cin, Cout, N, H, W, ks) > 0, "conv_fwd_b16: this shape writes no fused statistics (uz_conv_bn_partials() == 0)");
@@ -633,7 +633,7 @@ extern "C" int uz_conv_fwd_b16(const void* x, int Cin, int CinTot, const float* 
 extern "C" int uz_conv_bwd_data_b16(const void* dy, int Cout, int CoutTot, const float* w, void* dx, int Cin, int CinTot,
                                     int N, int H, int W, int ks, int accumulate,
                                     void* workspace, size_t workspace_bytes, const void* packed_w, int dy_b16, int dx_b16, void* stream) {
-    UZ_REQUIRE(ks == 3 && uz::conv_np() == 1 && uz_conv_route(1, Cin, Cout, N, H, W, ks) == 1,
+    UZ_REQUIRE(ks == 3 && uz::conv_np() == 1 && uz_conv_route(1, Cin, Cout, N, H, W, ks) == 1 && (!(dy_b16 || dx_b16) || uz_conv_split_parts(1, Cin, Cout, N, H, W) == 1),
                "conv_bwd_data_b16: bf16 storage needs uz_set_conv_math(3) and a 3x3 shape on the matrix-pipe path (unsplit chunk loop)");
     UZ_REQUIRE(workspace && workspace_bytes >= uz::conv_split_workspace(Cout, Cin, N, H, W), "conv_bwd_data_b16: workspace too small");
     uz::SplitOpts o;
