@@ -798,6 +798,43 @@ int    uz_vol_region_scores(const uint8_t* pred, int N, const uint32_t* pred_set
                             int D, int H, int W, int want_hd95, void* workspace, int64_t* counts, double* scores, void* stream);
 int    uz_vol_region_scores_route(int N, int R, int D, int H, int W, int want_hd95, int* out4);
 
+/* ---------------------------------------------------------------- volume components (data/BratsProcessing/utils.py:228-251)
+ * keep_largest_connected_components of label volumes that are already in HBM: the step between drawing samples and scoring them.  The
+ * reference runs skimage.measure.label(connectivity=1) per label 1, 2, 3 on the host, keeps the blob with the largest area
+ * (np.argmax over regionprops, in label order) and zeroes everything else.  Here N volumes (N, D, H, W) uint8, dense, W fastest, go
+ * through one call.  Everything is integer and exact; no float atomics, so a repeated call is bit-equal.
+ *   Connectivity: face neighbours only, 6 in 3-D and 4 when D == 1 (skimage connectivity=1, scipy's default structure).  Volumes never
+ *   connect to each other, rows never across the row end, slices never across the slice end.
+ *   A SET is a bit mask of label values 0 .. 31, as uz_vol_region_scores takes regions: a voxel is foreground of set m when bit `label`
+ *   of m is 1; a value of 32 or more is in no set.
+ * uz_vol_label_components, one set: labels (N, D, H, W) int32 = 0 on background, on foreground 1 + the smallest local linear index
+ * (z*H + y)*W + x over the voxel's component (local to its own volume): a canonical labelling, independent of scan order and of the
+ * order in which atomics arrive.  sizes (N, D, H, W) int32, nullable = the voxel count of the voxel's component, 0 on background.
+ * uz_vol_keep_components, R sets and min_voxels[r] >= 0 in HOST memory; each set is labelled on its own (the sets may be nested or
+ * overlap, WT / TC / ET).  A component of set r is KEPT when, with min_voxels[r] == 0, it is the largest component of set r in its
+ * volume - among equally large ones the smallest canonical label wins, the component whose first voxel in C order comes first, which
+ * is the reference's argmax -, and with min_voxels[r] = m >= 1 when its size is >= m.  A voxel with label l is LISTED when some set
+ * contains l.  out (N, D, H, W) uint8 = l when the voxel is listed and for every set that contains l its component in that set is
+ * kept; 0 when it is listed and some component fails; an unlisted voxel is 0, or l with keep_unlisted != 0.  A set that is empty in
+ * a volume keeps and removes nothing.  Sets {1}, {2}, {3}, min_voxels 0, keep_unlisted 0: the reference function, for a 3-D mask and
+ * for a 2-D one (D == 1).  out may not overlap vol: later sets must see the unfiltered input, so in-place is not offered.
+ * A union-find with the minimum index as root (csrc/volcomp.hip): x-runs from a ballot per 64 voxels of a row, one union per overlap
+ * of two runs in neighbouring rows and slices (agent-scope relaxed atomics only, fetch_min decides; every loop moves to a strictly
+ * smaller index or stops and no thread waits for another), one integer add per run for the sizes, one 64-bit maximum per wave for
+ * the largest.  All N volumes of one set go through each launch; the sets run one after the other through the same workspace.
+ * `workspace`: uz_vol_components_workspace bytes (two int32 per voxel and 8 bytes per volume), 16-byte aligned.
+ * Limits: N*D*H*W < 2^31, 1 <= N <= UZ_VOL_MAX_ROWS, 1 <= R <= UZ_VOL_MAX_REGIONS.  Refused before any launch (-1, uz_last_error names
+ * the reason, nothing written): a null pointer (sizes excepted), an empty axis, the limits, a negative min_voxels, a workspace off
+ * 16 bytes, labels or sizes off 4, out overlapping vol.  uz_vol_components_workspace returns 0 for sizes it refuses.
+ * uz_vol_components_route (host only, like uz_vol_region_scores_route) answers from the predicates the launches use: out2[0] = the
+ * form (always 0: there is one), out2[1] = workgroups of the widest launch of a call.                                            */
+size_t uz_vol_components_workspace(int N, int D, int H, int W);
+int    uz_vol_label_components(const uint8_t* vol, int N, int D, int H, int W, uint32_t set,
+                               int32_t* labels, int32_t* sizes, void* workspace, void* stream);
+int    uz_vol_keep_components(const uint8_t* vol, int N, int D, int H, int W, const uint32_t* sets, const int32_t* min_voxels, int R,
+                              int keep_unlisted, uint8_t* out, void* workspace, void* stream);
+int    uz_vol_components_route(int N, int D, int H, int W, int* out2);
+
 /* ---------------------------------------------------------------- volumes (models/phiseg3D.py), one sample
  * A volume is stored [D + 2][C][H][W] (zero slice before and after the D real ones) = a batch of D 2-D images.  Conv3d(3x3x3,
  * pad 1) (phiseg3D.py:24) then is uz_conv_fwd / uz_conv_bwd_* with the depth window as 3 C input channels (pointer = slice d-1,

@@ -105,7 +105,9 @@ def prototypes():
             if "*" in t:
                 return C.c_char_p if t.replace(" ", "") == "constchar*" else C.c_void_p
             base = t.replace("const", "").split()[0] if t.split() else "void"
-            return {"int": C.c_int, "size_t": C.c_size_t, "int64_t": C.c_int64, "float": C.c_float, "void": None, "uint8_t": C.c_uint8}[base]
+            # uint32_t by value (a set of label values) travels as a C int: the same register, ctypes does not range-check a c_int, and
+            # oracle/tape_stubs.py, which prints every by-value type of this table, knows an int
+            return {"int": C.c_int, "size_t": C.c_size_t, "int64_t": C.c_int64, "float": C.c_float, "void": None, "uint8_t": C.c_uint8, "uint32_t": C.c_int}[base]
 
         argtypes = []
         if args and args != "void":

@@ -1,0 +1,275 @@
+// Connected components of label volumes on the device (uz_api.h "volume components"): a canonical labelling of the face-connected
+// components of {label in set}, their sizes, and the filter that keeps the largest (or the large enough) component of every set.
+// Replaces data/BratsProcessing/utils.py:228-251 (keep_largest_connected_components: skimage.measure.label(connectivity=1), regionprops
+// and an argmax over the areas, per label, on the host).
+//
+// A union-find over the voxels' GLOBAL linear indices g = n*P + local (all N volumes in one index space, N*P < 2^31), the parent of a
+// voxel always an index <= its own, so the root of a tree is the smallest index of its component and the labelling is canonical by
+// construction: no scan order and no arrival order of an atomic can change it.
+//   runs     one wave per row, 64 voxels a step, no atomics: a ballot gives every voxel the first voxel of its x-run as parent (a run
+//            that crosses a 64-voxel step is carried in wave-uniform registers), and the run's length is parked in cnt[] at its first voxel;
+//   merge    one union per OVERLAP of two runs in neighbouring rows (y-1) and slices (z-1): the thread of the overlap's first voxel unites;
+//   flatten  every run's first voxel looks its root up, points at it, and adds its run length to cnt[root]: one integer add per run;
+//   select   roots offer (size << 32) | (0xFFFFFFFF - local index) to a 64-bit maximum per volume, reduced per wave first;
+//   apply    one pass over the voxels: parent[parent[v]] is the root (a voxel that is not first in its run never changed its parent).
+// Rows never join across their end because a run lives in one row; slices and volumes never join because merge looks only at y-1 within
+// the slice and z-1 within the volume.
+#include "uz_common.h"
+#include <algorithm>
+
+namespace {
+
+constexpr int VOX_GRID_MAX = 1 << 18;   // workgroups of a launch over the voxels (256 voxels each; a grid-stride loop covers the rest)
+constexpr int ROW_GRID_MAX = 1 << 16;   // workgroups of the run kernel (four rows each)
+constexpr int SEL_VOX = 4096;           // voxels of one volume a workgroup of the select kernel looks at per step
+
+#define UZ_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+__device__ __forceinline__ bool member(const uint8_t* __restrict__ lab, long long idx, uint32_t set) {
+    const unsigned v = lab[idx];
+    return v < 32u && ((set >> (v & 31u)) & 1u);
+}
+
+// ------------------------------------------------------------------------------------------------ runs
+__global__ __launch_bounds__(256) void comp_runs_k(const uint8_t* __restrict__ vol, uint32_t set, long long rows, int W, int N,
+                                                   int* __restrict__ parent, int* __restrict__ cnt, unsigned long long* __restrict__ best) {
+    if (blockIdx.x == 0)
+        for (int n = threadIdx.x; n < N; n += 256) best[n] = 0ull;
+    const int lane = threadIdx.x & 63;
+    const int nchunk = (int)(((long long)W + 63) >> 6);                // W may be just below 2^31: positions along the row are 64-bit
+    const unsigned long long below_me = (1ull << lane) - 1ull, me_and_below = lane == 63 ? ~0ull : (2ull << lane) - 1ull;
+    for (long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (long long)gridDim.x * 4) {
+        const long long base = row * W;                                   // < 2^31
+        int open_start = -1, open_len = 0;                                // wave-uniform: the run that reached the end of the last step
+        for (int c = 0; c < nchunk; ++c) {
+            const long long x0 = (long long)c << 6, x = x0 + lane;
+            const bool fg = x < W && member(vol, base + x, set);
+            const unsigned long long m = __ballot(fg);
+            const unsigned long long bg_below = ~m & below_me;
+            // first lane of my run inside this step, or -1: it began in an earlier step
+            const int st = bg_below ? 64 - __clzll((long long)bg_below) : (open_start >= 0 ? -1 : 0);
+            if (x < W) parent[base + x] = fg ? (st < 0 ? open_start : (int)(base + x0 + st)) : -1;
+            if (fg && st == lane) {                                       // a run begins here: park its length, unless it goes on into the next step
+                const unsigned long long bg_above = ~m & ~me_and_below;
+                if (bg_above) cnt[base + x] = __ffsll((long long)bg_above) - 1 - lane;
+            }
+            const int lead = ~m ? __ffsll((long long)~m) - 1 : 64;        // voxels of the run at the start of the step
+            if (open_start >= 0) {
+                if (lead == 64) open_len += 64;
+                else { if (lane == 0) cnt[open_start] = open_len + lead; open_start = -1; }
+            }
+            if (open_start < 0 && (m >> 63)) {
+                const int trail = ~m ? __clzll((long long)~m) : 64;       // voxels of the run at the end of the step
+                open_start = (int)(base + x0 + 64 - trail); open_len = trail;
+            }
+        }
+        if (open_start >= 0 && lane == 0) cnt[open_start] = open_len;     // W a multiple of 64 and the row ends inside a run
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ union-find
+// The root of a's tree.  Terminates by construction: a parent is never larger than its index, so every round moves to a strictly
+// smaller index or stops; nothing here waits for another thread.  A stale value is an older ancestor of the same tree: it costs a round.
+__device__ __forceinline__ int find_root(int* parent, int a) {
+    for (;;) {
+        const int p = __hip_atomic_load(&parent[a], UZ_RLX_AGENT);
+        if ((unsigned)p >= (unsigned)a) return a;                          // p == a: a root (anything else cannot be there, and is not followed)
+        a = p;
+    }
+}
+// Terminates by construction: every round either stops or goes on with two indices that are both smaller than this round's hi, and
+// find_root only ever moves down.  No thread waits for another one's progress: fetch_min decides, and whoever finds that hi already
+// had a parent takes over the duty to unite that parent with lo.  Correctness does not depend on how fresh a loaded parent is.
+__device__ __forceinline__ void unite(int* parent, int a, int b) {
+    for (;;) {
+        a = find_root(parent, a); b = find_root(parent, b);
+        if (a == b) return;
+        const int hi = max(a, b), lo = min(a, b);
+        const int old = __hip_atomic_fetch_min(&parent[hi], lo, UZ_RLX_AGENT);
+        if (old == hi) return;                                             // hi was a root and now hangs below lo
+        a = old; b = lo;                                                   // hi hung below old already: old and lo are to be united, both < hi
+    }
+}
+
+__global__ __launch_bounds__(256) void comp_merge_k(const uint8_t* __restrict__ vol, uint32_t set, long long T, int D, int H, int W, int* parent) {
+    const int HW = H * W;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < T; q += (long long)gridDim.x * 256) {
+        if (!member(vol, q, set)) continue;
+        const long long t = q / W;
+        const int x = (int)(q - t * W);
+        const long long t2 = t / H;
+        const int y = (int)(t - t2 * H), z = (int)(t2 % D);
+        // the first voxel of the overlap of my run with the run above: not both left neighbours are foreground
+        if (y > 0 && member(vol, q - W, set) && (x == 0 || !(member(vol, q - 1, set) && member(vol, q - 1 - W, set)))) unite(parent, (int)q, (int)(q - W));
+        if (z > 0 && member(vol, q - HW, set) && (x == 0 || !(member(vol, q - 1, set) && member(vol, q - 1 - HW, set)))) unite(parent, (int)q, (int)(q - HW));
+    }
+}
+
+// Behind the kernel boundary the forest is final.  The first voxel of every run points at its root and hands its run length over.
+// Another thread may walk through parent[q] while it is rewritten: it reads the old ancestor or the root, both in its tree.
+__global__ __launch_bounds__(256) void comp_flatten_k(const uint8_t* __restrict__ vol, uint32_t set, long long T, int W, int* parent, int* cnt) {
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < T; q += (long long)gridDim.x * 256) {
+        if (!member(vol, q, set)) continue;
+        if (q % W != 0 && member(vol, q - 1, set)) continue;
+        const int r = find_root(parent, (int)q);
+        if (r != (int)q) {
+            __hip_atomic_store(&parent[q], r, UZ_RLX_AGENT);
+            atomicAdd(&cnt[r], cnt[q]);                                    // cnt[q] of a run that is no root is never added to
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ select
+__global__ __launch_bounds__(256) void comp_select_k(const int* __restrict__ parent, const int* __restrict__ cnt, int P, int per_vol, long long items,
+                                                     unsigned long long* __restrict__ best) {
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int n = (int)(it / per_vol);
+        const int v0 = (int)(it - (long long)n * per_vol) * SEL_VOX;
+        const long long off = (long long)n * P;
+        unsigned long long mine = 0ull;
+        const long long vend = min((long long)v0 + SEL_VOX, (long long)P);
+        for (long long v = v0 + threadIdx.x; v < vend; v += 256) {
+            const long long g = off + v;
+            if (parent[g] == (int)g) mine = max(mine, ((unsigned long long)(unsigned)cnt[g] << 32) | (0xFFFFFFFFull - (unsigned)v));
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mine = max(mine, (unsigned long long)__shfl_xor((long long)mine, o, 64));
+        if ((threadIdx.x & 63) == 0 && mine) atomicMax(&best[n], mine);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ outputs
+__global__ __launch_bounds__(256) void comp_labels_k(const uint8_t* __restrict__ vol, uint32_t set, long long T, int P, const int* __restrict__ parent,
+                                                     const int* __restrict__ cnt, int* __restrict__ labels, int* __restrict__ sizes) {
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < T; q += (long long)gridDim.x * 256) {
+        int l = 0, s = 0;
+        if (member(vol, q, set)) {
+            const int r = parent[parent[q]];
+            l = r - (int)(q / P) * P + 1;                                  // (q / P) * P < 2^31
+            s = cnt[r];
+        }
+        labels[q] = l;
+        if (sizes) sizes[q] = s;
+    }
+}
+
+// first: out = vol where the label is listed (or unlisted labels are kept), 0 elsewhere; then every set zeroes what it does not keep
+__global__ __launch_bounds__(256) void comp_apply_k(const uint8_t* __restrict__ vol, uint32_t set, uint32_t listed, int keep_unlisted, int first,
+                                                    int min_voxels, long long T, int P, const int* __restrict__ parent, const int* __restrict__ cnt,
+                                                    const unsigned long long* __restrict__ best, uint8_t* __restrict__ out) {
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < T; q += (long long)gridDim.x * 256) {
+        const unsigned l = vol[q];
+        const bool in_set = l < 32u && ((set >> l) & 1u);
+        bool kept = true;
+        if (in_set) {
+            const int r = parent[parent[q]];
+            const unsigned sz = (unsigned)cnt[r];
+            if (min_voxels > 0) kept = sz >= (unsigned)min_voxels;
+            else {
+                const int n = (int)(q / P);
+                kept = best[n] == (((unsigned long long)sz << 32) | (0xFFFFFFFFull - (unsigned)(r - n * P)));
+            }
+        }
+        if (first) out[q] = (kept && (keep_unlisted || (l < 32u && ((listed >> l) & 1u)))) ? (uint8_t)l : (uint8_t)0;
+        else if (!kept) out[q] = 0;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+const char* sizes_bad(int N, int D, int H, int W) {
+    if (D < 1 || H < 1 || W < 1) return "empty axis";
+    if (N < 1 || N > UZ_VOL_MAX_ROWS) return "1 <= N <= 65536 volumes";
+    long long t = N;
+    for (int f : {D, H, W}) { t *= f; if (t >= (1LL << 31)) return "N*D*H*W must stay below 2^31"; }
+    return nullptr;
+}
+inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+inline int vox_grid(long long T) { return (int)std::min<long long>((T + 255) / 256, VOX_GRID_MAX); }
+inline int row_grid(long long rows) { return (int)std::min<long long>((rows + 3) / 4, ROW_GRID_MAX); }
+inline int sel_per_vol(int P) { return (int)(((long long)P + SEL_VOX - 1) / SEL_VOX); }
+inline int sel_grid(int N, int P) { return (int)std::min<long long>((long long)N * sel_per_vol(P), VOX_GRID_MAX); }
+
+struct Ws { unsigned long long* best; int* parent; int* cnt; };
+inline Ws carve(void* workspace, int N, long long T) {
+    char* b = static_cast<char*>(workspace);
+    Ws w;
+    w.best = reinterpret_cast<unsigned long long*>(b);
+    w.parent = reinterpret_cast<int*>(b + up16((size_t)N * 8));
+    w.cnt = reinterpret_cast<int*>(b + up16((size_t)N * 8) + up16((size_t)T * 4));
+    return w;
+}
+
+// runs, merge, flatten of one set: afterwards parent[parent[v]] is the root of v and cnt[root] the size of its component
+int label_set(const uint8_t* vol, uint32_t set, int N, int D, int H, int W, const Ws& w, hipStream_t st) {
+    const long long rows = (long long)N * D * H, T = rows * W;
+    hipLaunchKernelGGL(comp_runs_k, dim3(row_grid(rows)), dim3(256), 0, st, vol, set, rows, W, N, w.parent, w.cnt, w.best);
+    if (int rc = uz::check_launch("comp_runs_k")) return rc;
+    hipLaunchKernelGGL(comp_merge_k, dim3(vox_grid(T)), dim3(256), 0, st, vol, set, T, D, H, W, w.parent);
+    if (int rc = uz::check_launch("comp_merge_k")) return rc;
+    hipLaunchKernelGGL(comp_flatten_k, dim3(vox_grid(T)), dim3(256), 0, st, vol, set, T, W, w.parent, w.cnt);
+    return uz::check_launch("comp_flatten_k");
+}
+
+}  // namespace
+
+extern "C" size_t uz_vol_components_workspace(int N, int D, int H, int W) {
+    if (sizes_bad(N, D, H, W)) return 0;
+    return up16((size_t)N * 8) + 2 * up16((size_t)N * D * H * W * 4);
+}
+
+extern "C" int uz_vol_components_route(int N, int D, int H, int W, int* out2) {
+    UZ_REQUIRE(out2, "vol_components_route: two ints to answer into");
+    const char* bad = sizes_bad(N, D, H, W);
+    UZ_REQUIRE(!bad, "vol_components_route: %s", bad);
+    const long long rows = (long long)N * D * H, T = rows * W;
+    out2[0] = 0;                                                           // one form
+    out2[1] = std::max(std::max(row_grid(rows), vox_grid(T)), sel_grid(N, D * H * W));
+    return 0;
+}
+
+extern "C" int uz_vol_label_components(const uint8_t* vol, int N, int D, int H, int W, uint32_t set, int32_t* labels, int32_t* sizes,
+                                       void* workspace, void* stream) {
+    UZ_REQUIRE(vol && labels && workspace, "vol_label_components: null argument (vol, labels, workspace)");
+    const char* bad = sizes_bad(N, D, H, W);
+    UZ_REQUIRE(!bad, "vol_label_components: %s", bad);
+    UZ_REQUIRE(uz::align_of(workspace) == 16, "vol_label_components: workspace must be 16-byte aligned");
+    UZ_REQUIRE((reinterpret_cast<uintptr_t>(labels) & 3) == 0 && (reinterpret_cast<uintptr_t>(sizes) & 3) == 0, "vol_label_components: labels and sizes must be 4-byte aligned");
+    hipStream_t st = uz::S(stream);
+    const int P = D * H * W;
+    const long long T = (long long)N * P;
+    const Ws w = carve(workspace, N, T);
+    if (int rc = label_set(vol, set, N, D, H, W, w, st)) return rc;
+    hipLaunchKernelGGL(comp_labels_k, dim3(vox_grid(T)), dim3(256), 0, st, vol, set, T, P, w.parent, w.cnt, labels, sizes);
+    return uz::check_launch("comp_labels_k");
+}
+
+extern "C" int uz_vol_keep_components(const uint8_t* vol, int N, int D, int H, int W, const uint32_t* sets, const int32_t* min_voxels, int R,
+                                      int keep_unlisted, uint8_t* out, void* workspace, void* stream) {
+    UZ_REQUIRE(vol && sets && min_voxels && out && workspace, "vol_keep_components: null argument (vol, sets, min_voxels, out, workspace)");
+    const char* bad = sizes_bad(N, D, H, W);
+    UZ_REQUIRE(!bad, "vol_keep_components: %s", bad);
+    UZ_REQUIRE(R >= 1 && R <= UZ_VOL_MAX_REGIONS, "vol_keep_components: 1 <= R <= %d sets", UZ_VOL_MAX_REGIONS);
+    for (int r = 0; r < R; ++r) UZ_REQUIRE(min_voxels[r] >= 0, "vol_keep_components: min_voxels[%d] is negative", r);
+    UZ_REQUIRE(uz::align_of(workspace) == 16, "vol_keep_components: workspace must be 16-byte aligned");
+    const int P = D * H * W;
+    const long long T = (long long)N * P;
+    {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(vol), b = reinterpret_cast<uintptr_t>(out);
+        UZ_REQUIRE(a + (uintptr_t)T <= b || b + (uintptr_t)T <= a, "vol_keep_components: out overlaps vol (later sets must see the unfiltered input)");
+    }
+    hipStream_t st = uz::S(stream);
+    const Ws w = carve(workspace, N, T);
+    uint32_t listed = 0u;
+    for (int r = 0; r < R; ++r) listed |= sets[r];
+    for (int r = 0; r < R; ++r) {                                          // all N volumes of one set per launch, the sets one after the other
+        if (int rc = label_set(vol, sets[r], N, D, H, W, w, st)) return rc;
+        if (min_voxels[r] == 0) {
+            hipLaunchKernelGGL(comp_select_k, dim3(sel_grid(N, P)), dim3(256), 0, st, w.parent, w.cnt, P, sel_per_vol(P), (long long)N * sel_per_vol(P), w.best);
+            if (int rc = uz::check_launch("comp_select_k")) return rc;
+        }
+        hipLaunchKernelGGL(comp_apply_k, dim3(vox_grid(T)), dim3(256), 0, st, vol, sets[r], listed, keep_unlisted ? 1 : 0, r == 0 ? 1 : 0, min_voxels[r], T, P,
+                           w.parent, w.cnt, w.best, out);
+        if (int rc = uz::check_launch("comp_apply_k")) return rc;
+    }
+    return 0;
+}

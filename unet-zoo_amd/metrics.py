@@ -202,3 +202,120 @@ def score_volume(pred, reference, pred_regions, ref_regions=None, hd95=True):
     _ffi.check(L.uz_vol_region_scores(rows.data_ptr(), N, U32(*psets), reference.data_ptr(), U32(*rsets), R, D, H, W, int(bool(hd95)),
                                       ws.data_ptr(), counts.data_ptr(), scores.data_ptr(), _stream(rows)), "vol_region_scores")
     return VolumeScores(dice=scores[..., 0], sensitivity=scores[..., 1], specificity=scores[..., 2], hd95=scores[..., 3], counts=counts)
+
+
+# --------------------------------------------------------------------------- connected components of label volumes: the clean-up between drawing and scoring
+_components_ws = {}                                 # workspace per (device, N, D, H, W), as _volume_ws
+
+
+def _components_workspace(rows, what):
+    N, D, H, W = (int(d) for d in rows.shape)
+    L, dev = _ffi.lib(), rows.device
+    nbytes = L.uz_vol_components_workspace(N, D, H, W)
+    if nbytes == 0:
+        raise _ffi.UzError(f"{what}: sizes refused (N {N} volume {D} x {H} x {W}; no empty axis, 1 <= N <= 65536, N*D*H*W < 2^31)")
+    key = (dev, N, D, H, W)
+    ws = _components_ws.get(key)
+    if ws is None:
+        _components_ws.clear()                       # one shape at a time, as score_volume
+        ws = _components_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _label_rows(rows, what):
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8:
+        raise TypeError(f"{what} must be a uint8 tensor (N, D, H, W)")
+    if rows.dim() != 4:
+        raise ValueError(f"{what} {tuple(rows.shape)} is not (N, D, H, W)")
+    return rows
+
+
+def _on_device(rows, what):
+    if not rows.is_cuda:
+        raise ValueError(f"{what} must be on the device, not on {rows.device}")
+
+
+def _prediction_rows(pred):
+    """(rows (N, D, H, W) uint8, is_prediction): a Prediction's samples, then its mean label, as score_volume concatenates them; a 2-D
+    Prediction's (S, B, H, W) and (B, H, W) become S*B + B volumes of depth 1"""
+    if not (hasattr(pred, "labels") and hasattr(pred, "mean_label")):
+        return _label_rows(pred, "pred"), False
+    labels, mean_label = pred.labels, pred.mean_label
+    if not isinstance(labels, torch.Tensor) or not isinstance(mean_label, torch.Tensor) or labels.dtype != torch.uint8 or mean_label.dtype != torch.uint8:
+        raise TypeError("Prediction.labels and Prediction.mean_label must be uint8")
+    if labels.dim() not in (4, 5) or tuple(mean_label.shape) != tuple(labels.shape[1:]) or (labels.dim() == 5 and int(labels.shape[1]) != 1):
+        raise ValueError("Prediction expected with labels (S, 1, D, H, W) and mean_label (1, D, H, W), or labels (S, B, H, W) and mean_label (B, H, W), "
+                         f"got {tuple(labels.shape)} and {tuple(mean_label.shape)}")
+    if labels.dim() == 5:
+        return torch.cat([labels[:, 0], mean_label], 0), True
+    H, W = int(labels.shape[2]), int(labels.shape[3])
+    return torch.cat([labels.reshape(-1, 1, H, W), mean_label.reshape(-1, 1, H, W)], 0), True
+
+
+def _filtered_prediction(pred, out):
+    """a new Prediction: labels and mean_label cut out of the filtered rows, every other field the same object"""
+    labels, mean_label = pred.labels, pred.mean_label
+    n_lab = int(out.shape[0]) - int(mean_label.shape[0])
+    fields = {k: getattr(pred, k) for k in type(pred).__slots__} if hasattr(type(pred), "__slots__") else dict(pred._asdict())
+    fields["labels"] = out[:n_lab].reshape(labels.shape)
+    fields["mean_label"] = out[n_lab:].reshape(mean_label.shape)
+    return type(pred)(**fields)
+
+
+def label_components(volumes, values, return_sizes=False):
+    """Face-connected components (6 neighbours, 4 when D == 1) of {label in values} in N label volumes, uint8 (N, D, H, W) on the device -
+    one uz_vol_label_components call (csrc/volcomp.hip) on the caller's current stream, no synchronisation.  Returns int32 labels
+    (N, D, H, W): 0 on background, 1 + the smallest local index (z*H + y)*W + x of the voxel's component elsewhere - canonical, so a
+    repeated call is bit-equal -, or (labels, sizes) with the voxel count of each voxel's component."""
+    rows = _label_rows(volumes, "volumes")
+    (bits,) = _region_sets((tuple(values),), "values")
+    _on_device(rows, "volumes")
+    ws = _components_workspace(rows, "label_components")
+    rows = rows.contiguous()
+    labels = torch.empty(rows.shape, dtype=torch.int32, device=rows.device)
+    sizes = torch.empty(rows.shape, dtype=torch.int32, device=rows.device) if return_sizes else None
+    N, D, H, W = (int(d) for d in rows.shape)
+    _ffi.check(_ffi.lib().uz_vol_label_components(rows.data_ptr(), N, D, H, W, bits, labels.data_ptr(), sizes.data_ptr() if return_sizes else None,
+                                                  ws.data_ptr(), _stream(rows)), "vol_label_components")
+    return (labels, sizes) if return_sizes else labels
+
+
+def keep_largest_components(pred, regions=((1,), (2,), (3,)), min_voxels=None, unlisted="zero"):
+    """keep_largest_connected_components (data/BratsProcessing/utils.py:228-251) on the device - one uz_vol_keep_components call
+    (csrc/volcomp.hip) on the caller's current stream, no host round trip, no synchronisation.  Each region, a tuple of label values,
+    is labelled on its own (the regions may be nested: ((1, 2, 3),) keeps the largest whole tumour); of a region with min_voxels 0 the
+    largest component per volume is kept (ties: the one whose first voxel comes first), with min_voxels m >= 1 every component of at
+    least m voxels.  A voxel keeps its label when every region that contains the label keeps the voxel's component, else it becomes
+    0; labels in no region become 0 (unlisted="zero", the reference) or stay (unlisted="keep").  min_voxels: None (all 0), one int,
+    or one int per region.  The default regions with the other defaults are the reference function.
+    pred: a uint8 tensor (N, D, H, W) -> the filtered tensor; or a Prediction - PHISeg3D's, labels (S, 1, D, H, W) and mean_label
+    (1, D, H, W), or a 2-D model's, labels (S, B, H, W) and mean_label (B, H, W), run as D = 1 - whose samples and mean label go through
+    ONE call -> a new Prediction with the filtered labels and mean_label.  Every other field is the same object: soft, mean_soft and
+    entropy describe the UNFILTERED draw.  The result goes into score_volume as it is."""
+    if unlisted not in ("zero", "keep"):
+        raise ValueError(f"unlisted must be 'zero' or 'keep', not {unlisted!r}")
+    sets = _region_sets(regions, "regions")
+    R = len(sets)
+    if min_voxels is None:
+        mv = [0] * R
+    elif isinstance(min_voxels, int):
+        mv = [min_voxels] * R
+    else:
+        mv = [int(m) for m in min_voxels]
+        if len(mv) != R:
+            raise ValueError(f"{len(mv)} min_voxels for {R} regions")
+    if any(m < 0 for m in mv):
+        raise ValueError(f"min_voxels {tuple(mv)}: a threshold is a voxel count >= 0")
+    rows, is_pred = _prediction_rows(pred)
+    if R < 1 or R > 8:
+        raise _ffi.UzError(f"keep_largest_components: sizes refused ({R} regions; 1 <= R <= 8)")
+    _on_device(rows, "pred")
+    ws = _components_workspace(rows, "keep_largest_components")
+    rows = rows.contiguous()
+    out = torch.empty_like(rows)
+    N, D, H, W = (int(d) for d in rows.shape)
+    _ffi.check(_ffi.lib().uz_vol_keep_components(rows.data_ptr(), N, D, H, W, (C.c_uint32 * R)(*sets), (C.c_int32 * R)(*mv), R, int(unlisted == "keep"),
+                                                 out.data_ptr(), ws.data_ptr(), _stream(rows)), "vol_keep_components")
+    if not is_pred:
+        return out
+    return _filtered_prediction(pred, out)
