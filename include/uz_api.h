@@ -835,6 +835,54 @@ int    uz_vol_keep_components(const uint8_t* vol, int N, int D, int H, int W, co
                               int keep_unlisted, uint8_t* out, void* workspace, void* stream);
 int    uz_vol_components_route(int N, int D, int H, int W, int* out2);
 
+/* ---------------------------------------------------------------- volume uncertainty (the BraTS uncertainty task; calibration)
+ * Judges S sampled label volumes of ONE case as an uncertainty estimate against one reference, per region, from the votes of the
+ * samples: with S samples a voxel's region probability takes only the S + 1 values c / S, so one integer table per region holds
+ * everything.  Restates the BraTS uncertainty-task evaluation (filtered Dice, filtered true-positive and true-negative ratios over
+ * uncertainty thresholds, their areas, score = (AUC_dice + (1 - AUC_ftp) + (1 - AUC_ftn)) / 3) with the levels 0 .. S in the place
+ * of its thresholds 0 .. 100, and the usual reliability numbers (ECE, MCE, Brier) with one bin per vote count.  The reference
+ * project evaluates no uncertainty; bratsUtils.py:6-24,86-93 gives the Dice convention and the regions.
+ *   samples (S, D, H, W) uint8, dense, W fastest; decision and ref (D, H, W) uint8; pred_sets / ref_sets: R bit masks in HOST memory,
+ *   exactly as uz_vol_region_scores takes them (a value of 32 or more is in no set).  Per region r and voxel v:
+ *     c = number of samples s with samples[s][v] in pred_sets[r];   d = 1 when decision[v] is in pred_sets[r];
+ *     t = 1 when ref[v] is in ref_sets[r];   a = d ? S - c : c, the samples that contradict the decision: the uncertainty is a / S.
+ *   table (R, S+1, 2, 2) int64: table[r][c][d][t] = number of voxels; the entries of a region sum to P = D*H*W.
+ *   levels (R, S+1, 4) int64 = {tp_j, fp_j, fn_j, tn_j} over the voxels kept at level j, those with a <= j:
+ *     tp_j = sum_{c >= S-j} T[c][1][1], fp_j = sum_{c >= S-j} T[c][1][0], fn_j = sum_{c <= j} T[c][0][1], tn_j = sum_{c <= j} T[c][0][0];
+ *     level S keeps every voxel.
+ *   curves (R, S+1, 3) fp64, each ONE division of exact integers: dice_j = 2 tp_j / (2 tp_j + fp_j + fn_j), 1 when the denominator
+ *     is 0 (the convention of uz_vol_region_scores); ftp_j = (tp_S - tp_j) / tp_S, 0 when tp_S = 0; ftn_j = (tn_S - tn_j) / tn_S,
+ *     0 when tn_S = 0.
+ *   auc (R, 4) fp64 = {auc_dice, auc_ftp, auc_ftn, score}: trapezoid sums over the uniform grid j / S,
+ *     auc_x = (1/S) sum_{j<S} (x_j + x_{j+1}) / 2, summed in fp64 in the order of j (every term lies in [0, 1]: the error is below
+ *     (S + 4) 2^-52); score = (auc_dice + (1 - auc_ftp) + (1 - auc_ftn)) / 3.
+ *   calibration (R, 3) fp64 = {ece, mce, brier} with n_c = sum_{d,t} T[c][d][t] and pos_c = sum_d T[c][d][1], each ONE division of
+ *     an exact integer numerator: ece = (sum_c |S pos_c - c n_c|) / (S P); mce = max over c with n_c > 0 of |S pos_c - c n_c| / (S n_c);
+ *     brier = (sum_c pos_c (S-c)^2 + (n_c - pos_c) c^2) / (S^2 P).  Every numerator and denominator is below 2^53 for P < 2^31 and
+ *     S <= 255 (the largest, S^2 P, is below 2^47), so each is exact in fp64 and each quotient is correctly rounded.
+ *   votes (R, D, H, W) uint8, nullable = c, the per-region vote map (a BraTS uncertainty submission writes 100 a / S from it).
+ * Two launches (csrc/voluncert.hip).  The table pass streams the S + 2 volumes once: a wide form (16 or 4 voxels per thread with
+ * 16- or 4-byte loads, when EVERY row samples + s P, decision, ref and votes + r P is so aligned) and a scalar form (any address; it
+ * also takes the tail of the wide form); membership by a 256-entry table in LDS, the region tables in LDS as uint32 with LDS
+ * atomics, the bin (c, d, t) = (0, 0, 0) counted in registers and added once per wave, words of four background voxels skipped
+ * without touching LDS.  No global atomics: every workgroup of a capped, grid-striding grid stores its whole table to its own slice
+ * of the workspace, and the finish (one workgroup per region) sums the slices in int64 and forms everything else in integers up to
+ * the final divisions.  Exact, independent of order, bit-equal on repetition; nothing depends on the workspace's previous content.
+ * `workspace`: uz_vol_uncertainty_workspace bytes (at most 1024 slices of R (S+1) 4 uint32), 16-byte aligned.
+ * Refused before any launch (-1, uz_last_error names the reason, nothing written): a null pointer (votes excepted), S < 1 or
+ * S > UZ_VOL_UNC_MAX_SAMPLES, R < 1 or R > UZ_VOL_MAX_REGIONS, an empty axis, S*D*H*W >= 2^31, a workspace off 16 bytes, table,
+ * levels, curves, auc or calibration off 8.  uz_vol_uncertainty_workspace returns 0 for the sizes the call would refuse.
+ * uz_vol_uncertainty_route (host only, like uz_vol_components_route) answers from the predicates the launch uses, for a call WITH
+ * votes whose pointers all have byte alignment `align` (1, 2, 4, 8 or 16): out3[0] = 0 the scalar form, 1 the wide form,
+ * out3[1] = workgroups of the table pass, out3[2] = 1 when the pass grid-strides (P exceeds what the capped grid covers in one sweep). */
+#define UZ_VOL_UNC_MAX_SAMPLES 255
+size_t uz_vol_uncertainty_workspace(int S, int R, int D, int H, int W);
+int    uz_vol_uncertainty(const uint8_t* samples, int S, const uint8_t* decision, const uint32_t* pred_sets,
+                          const uint8_t* ref, const uint32_t* ref_sets, int R, int D, int H, int W,
+                          void* workspace, int64_t* table, int64_t* levels, double* curves, double* auc,
+                          double* calibration, uint8_t* votes, void* stream);
+int    uz_vol_uncertainty_route(int S, int R, int D, int H, int W, int align, int* out3);
+
 /* ---------------------------------------------------------------- volumes (models/phiseg3D.py), one sample
  * A volume is stored [D + 2][C][H][W] (zero slice before and after the D real ones) = a batch of D 2-D images.  Conv3d(3x3x3,
  * pad 1) (phiseg3D.py:24) then is uz_conv_fwd / uz_conv_bwd_* with the depth window as 3 C input channels (pointer = slice d-1,

@@ -319,3 +319,83 @@ def keep_largest_components(pred, regions=((1,), (2,), (3,)), min_voxels=None, u
     if not is_pred:
         return out
     return _filtered_prediction(pred, out)
+
+
+# --------------------------------------------------------------------------- S samples of one volume as an uncertainty estimate: filtered Dice, calibration
+UncertaintyScores = collections.namedtuple("UncertaintyScores", "table levels dice ftp ftn auc calibration votes")
+UncertaintyScores.__doc__ = """What score_uncertainty returns, all on the device, per region r: table (R, S+1, 2, 2) int64 = voxels with c of the S samples in
+the region, decision d and reference t; levels (R, S+1, 4) int64 = {tp, fp, fn, tn} over the voxels on which at most j samples contradict the
+decision; dice, ftp, ftn (R, S+1) fp64 - views of one (R, S+1, 3) buffer -: the filtered Dice and the filtered shares of true positives and
+true negatives at level j; auc (R, 4) fp64 = {auc_dice, auc_ftp, auc_ftn, score}, score the BraTS uncertainty-task score; calibration (R, 3)
+fp64 = {ece, mce, brier} of the vote frequencies c / S; votes (R, D, H, W) uint8 = c, or None when it was not asked for."""
+
+_uncertainty_ws = {}                                # workspace per (device, S, R, D, H, W), as _volume_ws
+
+
+def score_uncertainty(pred, reference, pred_regions, ref_regions=None, decision=None, return_votes=False):
+    """Judges S samples of ONE volume as an uncertainty estimate against `reference`, for R regions given as in score_volume - one
+    uz_vol_uncertainty call (csrc/voluncert.hip) on the caller's current stream: no host round trip, no synchronisation, no ATen
+    arithmetic on the volumes.  A voxel's uncertainty in a region is the share of the samples that contradict the decision there;
+    the levels j = 0 .. S keep the voxels with at most j such samples (include/uz_api.h "volume uncertainty" has every definition).
+    pred: a Prediction of PHISeg3D.predict / predict_volume - labels (S, 1, D, H, W), the decision is mean_label -, as it is or as
+    keep_largest_components returns it; or a uint8 tensor (S, D, H, W), and then `decision` is required.  decision: uint8 (D, H, W)
+    or (1, D, H, W), overrides the decision volume (for instance the filtered mean label while the samples stay unfiltered).
+    reference: uint8 (D, H, W) on the same device.  Returns an UncertaintyScores of device tensors."""
+    if hasattr(pred, "labels") and hasattr(pred, "mean_label"):
+        labels, mean_label = pred.labels, pred.mean_label
+        if not isinstance(labels, torch.Tensor) or not isinstance(mean_label, torch.Tensor) or labels.dtype != torch.uint8 or mean_label.dtype != torch.uint8:
+            raise TypeError("Prediction.labels and Prediction.mean_label must be uint8")
+        if labels.dim() != 5 or int(labels.shape[1]) != 1 or tuple(mean_label.shape) != tuple(labels.shape[1:]):
+            raise ValueError(f"Prediction of one volume expected: labels (S, 1, D, H, W) and mean_label (1, D, H, W), got {tuple(labels.shape)} and {tuple(mean_label.shape)}")
+        samples = labels[:, 0]
+        dec = mean_label[0] if decision is None else decision
+    else:
+        samples = pred
+        if not isinstance(samples, torch.Tensor) or samples.dtype != torch.uint8:
+            raise TypeError("pred must be a Prediction or a uint8 tensor (S, D, H, W)")
+        if samples.dim() != 4:
+            raise ValueError(f"pred {tuple(samples.shape)} is not (S, D, H, W)")
+        if decision is None:
+            raise ValueError("decision is required when pred is a tensor of samples: the volume the samples are judged against")
+        dec = decision
+    vol = tuple(samples.shape[1:])
+    for t, what in ((dec, "decision"), (reference, "reference")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise TypeError(f"{what} must be a uint8 tensor (D, H, W)")
+    if dec.dim() == 4 and int(dec.shape[0]) == 1:
+        dec = dec[0]
+    if tuple(dec.shape) != vol:
+        raise ValueError(f"decision {tuple(dec.shape)} does not match the volumes {vol} of pred")
+    if tuple(reference.shape) != vol:
+        raise ValueError(f"reference {tuple(reference.shape)} does not match the volumes {vol} of pred")
+    if reference.device != samples.device or dec.device != samples.device:
+        raise ValueError("reference and decision must be on the device of pred")
+    ref_regions = pred_regions if ref_regions is None else ref_regions
+    if len(ref_regions) != len(pred_regions):
+        raise ValueError(f"{len(pred_regions)} regions of pred against {len(ref_regions)} of the reference")
+    psets, rsets = _region_sets(pred_regions, "pred_regions"), _region_sets(ref_regions, "ref_regions")
+    _on_device(samples, "pred")
+    S, D, H, W = (int(d) for d in samples.shape)
+    R = len(psets)
+    L, dev = _ffi.lib(), samples.device
+    nbytes = L.uz_vol_uncertainty_workspace(S, R, D, H, W)
+    if nbytes == 0:
+        raise _ffi.UzError(f"score_uncertainty: sizes refused (S {S} R {R} volume {D} x {H} x {W}; 1 <= S <= 255, 1 <= R <= 8, no empty axis, S*D*H*W < 2^31)")
+    samples, dec, reference = samples.contiguous(), dec.contiguous(), reference.contiguous()
+    key = (dev, S, R, D, H, W)
+    ws = _uncertainty_ws.get(key)
+    if ws is None:
+        _uncertainty_ws.clear()                      # one shape at a time, as score_volume
+        ws = _uncertainty_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    table = torch.empty(R, S + 1, 2, 2, dtype=torch.int64, device=dev)
+    levels = torch.empty(R, S + 1, 4, dtype=torch.int64, device=dev)
+    curves = torch.empty(R, S + 1, 3, dtype=torch.float64, device=dev)
+    auc = torch.empty(R, 4, dtype=torch.float64, device=dev)
+    calibration = torch.empty(R, 3, dtype=torch.float64, device=dev)
+    votes = torch.empty(R, D, H, W, dtype=torch.uint8, device=dev) if return_votes else None
+    U32 = C.c_uint32 * R
+    _ffi.check(L.uz_vol_uncertainty(samples.data_ptr(), S, dec.data_ptr(), U32(*psets), reference.data_ptr(), U32(*rsets), R, D, H, W,
+                                    ws.data_ptr(), table.data_ptr(), levels.data_ptr(), curves.data_ptr(), auc.data_ptr(), calibration.data_ptr(),
+                                    votes.data_ptr() if return_votes else None, _stream(samples)), "vol_uncertainty")
+    return UncertaintyScores(table=table, levels=levels, dice=curves[..., 0], ftp=curves[..., 1], ftn=curves[..., 2], auc=auc,
+                             calibration=calibration, votes=votes)
