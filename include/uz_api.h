@@ -883,6 +883,77 @@ int    uz_vol_uncertainty(const uint8_t* samples, int S, const uint8_t* decision
                           double* calibration, uint8_t* votes, void* stream);
 int    uz_vol_uncertainty_route(int S, int R, int D, int H, int W, int align, int* out3);
 
+/* ---------------------------------------------------------------- volume preparation (data/BratsProcessing/brats18_data_loader.py:31-96,
+ * brats18_validation_data_loader.py:27-74) and the way back into native space
+ * uz_vol_prepare turns one raw case - the stacked modalities as they come from the challenge - into what the HDF5 file stores:
+ * crop_volume_allDim, crop_or_pad_slice_to_size and normalise_image in seven launches on the caller's stream.  The box never visits
+ * the host; no host round trip, no synchronisation.
+ *   raw (X, Y, Z, C) fp32, channels last; mask (X, Y, Z) uint8, nullable; target extent (Xt, Yt, Zt); placement 0 = centre (the
+ *   training loader), 1 = corner (the validation loader).  image (Xt, Yt, Zt, C) fp32; mask_out (Xt, Yt, Zt) uint8, null exactly
+ *   when mask is; info int32[16]; stats (C, 3) fp64 = {count, mean, std}.
+ *   BOX  per spatial axis the minimum and the maximum + 1 of the index over the voxels where ANY channel is > 0 (np.argwhere(image > 0),
+ *   not != 0: a negative value does not open the box, neither does a NaN).
+ *   PLACEMENT  per axis a descriptor {n, t, e}: target voxel t + i shows native voxel n + i for 0 <= i < e.  Box [b0, b1), s = b1 - b0,
+ *   target T, d = abs(T - s) / 2 (integer division):
+ *     centre, T <  s:  n = b0 + d, t = 0, e = T          centre, T >= s:  n = b0, t = d, e = s
+ *     corner:          n = b0,     t = 0, e = min(s, T)
+ *   The reference's corner placement truncates x only and raises when y or z does not fit; here every axis is truncated.
+ *   Everything of the target outside the placed block is 0, in image and in mask_out.
+ *   info[0..5] = {x0, y0, z0, x1, y1, z1} the box, [6..8] = n, [9..11] = t, [12..14] = e, [15] = flags: bit 0 = no voxel > 0, bit 1 =
+ *   some axis lost voxels (T < s).  With bit 0 every output is 0: image, mask_out, stats and all fifteen descriptor entries.
+ *   STATISTICS  per channel over the PLACED voxels with value != 0: a zero inside the box does not count, a negative value does, a
+ *   voxel that was cropped away does not.  count = their number; mean = sum / count in fp64; std = sqrt(sum((x - mean)^2) / count) in
+ *   fp64 with the unrounded fp64 mean - numpy's two-pass nanstd, ddof = 0, on fp64 input: the validation loader's route.  (The
+ *   training loader hands fp32 to nanmean / nanstd; what it gets depends on numpy's fp32 pairwise order and is not restated.)  A
+ *   channel without such a voxel has {0, 0, 0} (numpy: NaN and a warning) and its voxels are all 0.  A NaN counts and propagates.
+ *   Summation order, fixed: a thread adds its voxels in index order (grid stride), the 64 lanes of a wave by a shuffle tree, the four
+ *   waves of a workgroup in order, the workgroup stores to its own slice; the fold adds slices t, t + 256, ... per thread and then the
+ *   same tree.  No float atomics: a repeated call is bit-equal.  Error: every fp64 sum of n terms obeys |err| <= (n - 1) 2^-53 sum|term|
+ *   to first order whatever the order, so |mean - exact| <= (n - 1) 2^-53 sum|x| / n + 2^-53 |mean| (the division); a term (x - mean)^2
+ *   carries three roundings (the difference, the product, or one less with a fused multiply-add), so with V the exact variance and dm
+ *   the error of the mean |sum / n - V| <= (n + 3) 2^-53 (V + dm^2) + dm^2, and |std - exact| <= that / sqrt(V) + 2^-52 sqrt(V) (the
+ *   division, the square root).  With integer-valued intensities below 2^53 / n the sums of x are exact.
+ *   STORE  out = (x == 0) ? 0 : (x - f32(mean)) / f32(std) in fp32: one subtraction and one correctly rounded IEEE division, what
+ *   np.divide(image - m, s) does with m, s cast to float32.  std == 0 (one voxel, or a constant channel) gives what IEEE gives: NaN
+ *   on that channel's non-zero voxels.
+ * Kernels (csrc/volprep.hip): a wide form - C == 4 and raw and image 16-byte aligned: a voxel is one 16-byte load and one 16-byte
+ * store - and a scalar form for any C in 1 .. UZ_VOL_PREP_MAX_CHANNELS and any fp32 alignment.  Grids are capped (2048 workgroups of
+ * 256 threads) and grid-striding.  Launches: bounds (one read of raw) | fold bounds + descriptor | sums | fold -> count, mean |
+ * centred squares | fold -> std | store (with the mask).  The three passes behind the descriptor walk the target extent, whose
+ * size the host knows, and touch memory only inside the placed block.
+ * `workspace`: uz_vol_prepare_workspace bytes (a 32-byte box slice and a 128-byte sum slice per workgroup), 16-byte aligned; nothing
+ * depends on its previous content, nor on that of the outputs.
+ * Limits: X*Y*Z*C < 2^31, Xt*Yt*Zt*C < 2^31, 1 <= C <= 8.  Refused before any launch (-1, uz_last_error names the reason, nothing
+ * written): a null pointer (mask and mask_out excepted, but only both or neither), an empty axis, the limits, a placement other than
+ * 0 / 1, a workspace off 16 bytes, info off 4, stats off 8.  uz_vol_prepare_workspace returns 0 for sizes the call would refuse.
+ * uz_vol_prepare_route (host only) answers from the predicates the launches use, for raw and image of byte alignment `align` (4, 8
+ * or 16): out3[0] = 0 the scalar form, 1 the wide form; out3[1] = workgroups of the widest pass (bounds walks X*Y*Z voxels, the
+ * others Xt*Yt*Zt); out3[2] = 1 when that pass grid-strides.
+ *
+ * uz_vol_restore puts N rows of target extent back into native volumes: label maps, vote maps (uint8) or entropy maps (fp32).
+ *   rows (N, Xt, Yt, Zt) and out (N, X, Y, Z) of one element type, elem = 1 (uint8) or 4 (fp32); place int32[9] in DEVICE memory =
+ *   info[6..14] of uz_vol_prepare = {n, t, e}.  Native voxel v takes target voxel t + (v - n) where 0 <= v - n < e on all three axes,
+ *   and `fill` elsewhere; every output element is written exactly once.  fill: one element of that type in HOST memory.
+ *   lut: 256 bytes in HOST memory, nullable, uint8 rows only: out = lut[row value] (class index -> raw label {0, 1, 2, 4}).  It maps
+ *   the rows, never the fill.  It is copied into the launch arguments: the caller need not keep it alive.
+ *   `place` is data the host cannot see: the kernel clips per voxel (the ranges are intersected in 64-bit arithmetic, any nine int32)
+ *   and never reads outside rows.
+ * One thread per element, or per W consecutive elements with one 4- / 16-byte store where out is so aligned: W = 16 (uint8, out on 16
+ * bytes) or 4 (uint8, out on 4; fp32, out on 16).  The source is read element by element (Z is odd in real cases) and its row is
+ * looked up once per (n, x, y); the tail of N*X*Y*Z % W elements goes one per thread.
+ * Limits: N*X*Y*Z < 2^31, N*Xt*Yt*Zt < 2^31.  Refused before the launch: a null pointer (lut excepted), an empty axis, N < 1, the
+ * limits, elem other than 1 / 4, a non-null lut with elem = 4, fp32 rows or out off 4 bytes, place off 4, out overlapping rows.
+ * uz_vol_restore_route (host only), for an `out` of byte alignment `align`: out3[0] = W, the elements a thread writes (1, 4 or 16);
+ * out3[1] = workgroups; out3[2] = 0 (one sweep, always). */
+#define UZ_VOL_PREP_MAX_CHANNELS 8
+size_t uz_vol_prepare_workspace(int C, int X, int Y, int Z, int Xt, int Yt, int Zt);
+int    uz_vol_prepare(const float* raw, const uint8_t* mask, int C, int X, int Y, int Z, int Xt, int Yt, int Zt, int placement,
+                      void* workspace, float* image, uint8_t* mask_out, int32_t* info, double* stats, void* stream);
+int    uz_vol_prepare_route(int C, int X, int Y, int Z, int Xt, int Yt, int Zt, int align, int* out3);
+int    uz_vol_restore(const void* rows, int elem, int N, int Xt, int Yt, int Zt, const int32_t* place, const uint8_t* lut,
+                      const void* fill, void* out, int X, int Y, int Z, void* stream);
+int    uz_vol_restore_route(int elem, int N, int X, int Y, int Z, int align, int* out3);
+
 /* ---------------------------------------------------------------- volumes (models/phiseg3D.py), one sample
  * A volume is stored [D + 2][C][H][W] (zero slice before and after the D real ones) = a batch of D 2-D images.  Conv3d(3x3x3,
  * pad 1) (phiseg3D.py:24) then is uz_conv_fwd / uz_conv_bwd_* with the depth window as 3 C input channels (pointer = slice d-1,

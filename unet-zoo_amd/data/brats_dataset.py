@@ -11,11 +11,13 @@ re-designed like ``batch_provider.py`` for a 288 GB GPU:
     (C, Xc, Yc, Zc) image and (3, Xc, Yc, Zc) label tensors ``PHISeg3D.forward`` consumes: no per-slice Python loop, no cv2.
 
 ``filePath`` is the HDF5 file (opened lazily, needs ``h5py``) or a mapping with ``images_<mode>`` (N, X, Y, Z, C), ``masks_<mode>``
-(N, X, Y, Z) and ``pids_<mode>``.  Items are device tensors.  Without a GPU the dataset still draws (``draw_augmentation3d`` is host
+(N, X, Y, Z) and ``pids_<mode>`` - and ``xOffsets_<mode>`` / ``yOffsets_<mode>`` / ``zOffsets_<mode>`` for ``returnOffsets=True``, which appends
+the validation writer's crop offsets to the item as the reference does (bratsDataset.py:101-113).  A mapping's device tensors
+(``data.prepare_cases(...).as_mapping(mode)``) are taken as they are, without a trip through the host.  Items are device tensors.  Without a GPU the dataset still draws (``draw_augmentation3d`` is host
 code) but cannot assemble voxels - there is no CPU fallback for the product path.
 
 Not built: ``NN_AUGMENTATION = False`` - the soft and hard one-hot label schemes, which resample one-hot label volumes bilinearly -
-raises NotImplementedError; ``returnOffsets`` (the validation writer's crop offsets) is not taken.  Quirk kept: the intensity
+raises NotImplementedError.  Quirk kept: the intensity
 shift is hard-coded to four channels (augmentation.py:83), so with fewer the reference raises and so does this.
 """
 import ctypes as C
@@ -71,7 +73,7 @@ def draw_augmentation3d(shape, cfg, randomCrop=None, augment=True):
 
 class BratsDataset(torch.utils.data.Dataset):
     # mode must be train, test or val
-    def __init__(self, filePath, expConfig, mode="train", randomCrop=None, hasMasks=True, device=None):
+    def __init__(self, filePath, expConfig, mode="train", randomCrop=None, hasMasks=True, returnOffsets=False, device=None):
         super().__init__()
         self.filePath, self.mode, self.file = filePath, mode, None
         self.expConfig = expConfig
@@ -86,6 +88,7 @@ class BratsDataset(torch.utils.data.Dataset):
                                       "is not part of the native input pipeline")
         self.randomCrop = None if randomCrop is None else tuple(int(v) for v in randomCrop)
         self.hasMasks = hasMasks
+        self.returnOffsets = returnOffsets
         self.device = torch.device(device) if device is not None else \
             (torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu"))
         self._dev = None
@@ -112,13 +115,21 @@ class BratsDataset(torch.utils.data.Dataset):
             if self.device.type != "cuda":
                 raise _ffi.UzError("no GPU visible: the native input pipeline assembles batches on the device (no CPU fallback)")
             self.openFileIfNotOpen()
-            img = torch.as_tensor(np.ascontiguousarray(np.asarray(self.file["images_" + self.mode][...], dtype=np.float32))).to(self.device)
+            img = self.file["images_" + self.mode]
+            if isinstance(img, torch.Tensor) and img.is_cuda:               # already resident (data.prepare_cases)
+                img = img.to(self.device, torch.float32).contiguous()
+            else:
+                img = torch.as_tensor(np.ascontiguousarray(np.asarray(img[...], dtype=np.float32))).to(self.device)
             lbl = None
             if self.hasMasks:
-                m = np.asarray(self.file["masks_" + self.mode][...])
-                if m.ndim == 5:
-                    m = m[..., 0]
-                lbl = torch.as_tensor(np.ascontiguousarray(m.astype(np.uint8))).to(self.device)
+                m = self.file["masks_" + self.mode]
+                if isinstance(m, torch.Tensor) and m.is_cuda:
+                    lbl = (m[..., 0] if m.dim() == 5 else m).to(self.device, torch.uint8).contiguous()
+                else:
+                    m = np.asarray(m[...])
+                    if m.ndim == 5:
+                        m = m[..., 0]
+                    lbl = torch.as_tensor(np.ascontiguousarray(m.astype(np.uint8))).to(self.device)
             _, X, Y, Z, Cn = img.shape
             ws = torch.empty(_ffi.lib().uz_augment_volume_workspace(Cn, X, Y, Z), dtype=torch.uint8, device=self.device)
             self._dev = (img, lbl, ws)
@@ -137,5 +148,12 @@ class BratsDataset(torch.utils.data.Dataset):
         _ffi.check(_ffi.lib().uz_augment_volume(img[index].data_ptr(), lbl[index].data_ptr() if self.hasMasks else None, Cn, X, Y, Z,
                                                 prm.ctypes.data, Xc, Yc, Zc, ws.data_ptr(), x.data_ptr(),
                                                 y.data_ptr() if self.hasMasks else None, None, C.c_void_p(st)), "augment_volume")
+        return self._item(index, x, y)
+
+    def _item(self, index, x, y):
+        """the reference's tuples (bratsDataset.py:98-113): image, pid, labels with masks, then the three crop offsets on request"""
         pid = self.file["pids_" + self.mode][index]
-        return (x, str(pid), y) if self.hasMasks else (x, pid)
+        item = (x, str(pid), y) if self.hasMasks else (x, pid)
+        if self.returnOffsets:
+            item += tuple(self.file[ax + "Offsets_" + self.mode][index] for ax in "xyz")
+        return item

@@ -132,6 +132,7 @@ def score_prediction(pred, annotations, return_counts=False):
 # --------------------------------------------------------------------------- N label volumes against one reference: the BraTS region scores
 BRATS_REGIONS = ((1, 2, 4), (1, 4), (4,))          # raw BraTS labels: whole tumour, tumour core, enhancing tumour (bratsUtils.py:86-93)
 BRATS_REGION_NAMES = ("WT", "TC", "ET")
+BRATS_LABELS = (0, 1, 2, 4)                         # class index -> raw BraTS label: the lut of data.restore_volume
 
 VolumeScores = collections.namedtuple("VolumeScores", "dice sensitivity specificity hd95 counts")
 VolumeScores.__doc__ = """What score_volume returns, all on the device: dice, sensitivity, specificity, hd95 (N, R) fp64 - views of one (N, R, 4)
