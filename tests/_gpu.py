@@ -60,3 +60,33 @@ def maxabs(got, ref):
 def L():
     """The loaded C-ABI library (size queries: uz_*_workspace)."""
     return _ffi.lib()
+
+
+# ---------------------------------------------------------------------------------------------- guarded buffers
+CANARY = {torch.int32: -7777, torch.int64: -7777, torch.float32: -777.0, torch.float64: -777.0, torch.uint8: 0xA5}
+
+
+def guarded(n, dtype, guard=64, fill=None, off=0, room=0):
+    """n elements of `dtype` between two guards of `guard` elements, everything holding `fill` (CANARY[dtype] when None) -> (raw, body).
+    The body starts `off` elements behind the front guard - for uint8 and a guard that is a multiple of 16, `off` bytes behind a 16-byte
+    boundary; `room`: the elements set aside for that, so that buffers of several offsets have one size."""
+    raw = torch.full((n + 2 * guard + max(off, room),), CANARY[dtype] if fill is None else fill, dtype=dtype, device=dev())
+    assert raw.data_ptr() % 16 == 0
+    return raw, raw[guard + off:guard + off + n]
+
+
+def embed(arr, off, fill=0xEE):
+    """the bytes of a numpy array `off` bytes behind a 16-byte boundary of a larger uint8 buffer of `fill` -> (buffer, view)"""
+    b = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
+    buf = torch.full((b.size + 64,), fill, dtype=torch.uint8, device=dev())
+    assert buf.data_ptr() % 16 == 0
+    view = buf[off:off + b.size]
+    view.copy_(torch.from_numpy(b.copy()))
+    return buf, view
+
+
+def intact(raw, body, fill=None):
+    """every element of `raw` in front of and behind `body`, a view into it, still holds `fill` (CANARY[raw.dtype] when None)"""
+    fill = CANARY[raw.dtype] if fill is None else fill
+    lo = (body.data_ptr() - raw.data_ptr()) // raw.element_size()
+    return bool((raw[:lo] == fill).all()) and bool((raw[lo + body.numel():] == fill).all())

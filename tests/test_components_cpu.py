@@ -233,3 +233,20 @@ def test_prediction_rows_and_the_filtered_prediction_on_cpu_tensors():
     t = rnd(2, 4, 5, 6)
     rows, is_pred = metrics._prediction_rows(t)
     assert rows is t and not is_pred
+
+
+def test_workspace_slots_are_kept_per_owner_and_replaced_when_the_key_changes():
+    from unet_zoo_amd import _vol
+    cpu = torch.device("cpu")
+    a = _vol.workspace("test_owner_a", (cpu, 2, 3), 64, cpu)
+    assert a.dtype == torch.uint8 and a.numel() == 64
+    assert _vol.workspace("test_owner_a", (cpu, 2, 3), 64, cpu) is a                   # the same key: the same tensor object
+    b = _vol.workspace("test_owner_b", (cpu, 2, 3), 32, cpu)
+    assert b is not a and b.numel() == 32
+    assert _vol.workspace("test_owner_a", (cpu, 2, 3), 64, cpu) is a                   # two owners do not evict each other
+    a2 = _vol.workspace("test_owner_a", (cpu, 2, 4), 80, cpu)
+    assert a2 is not a and a2.numel() == 80                                            # a new key replaces the slot ...
+    assert _vol.workspace("test_owner_a", (cpu, 2, 4), 80, cpu) is a2
+    a3 = _vol.workspace("test_owner_a", (cpu, 2, 3), 64, cpu)
+    assert a3 is not a and a3 is not a2                                                 # ... for good: one shape at a time
+    assert _vol.workspace("test_owner_b", (cpu, 2, 3), 32, cpu) is b

@@ -13,7 +13,6 @@ from tests import _components as K
 
 pytestmark = pytest.mark.gpu
 
-CANARY = {torch.int32: -7777, torch.uint8: 0xA5}
 KEEP_IDS = [(c.name, k) for c in K.cases() for k in range(len(c.params))]
 
 
@@ -22,22 +21,12 @@ def _g():
     return _gpu
 
 
-def _guarded(n, dtype, dev, guard=64):
-    raw = torch.full((n + 2 * guard,), CANARY[dtype], dtype=dtype, device=dev)
-    return raw, raw[guard:guard + n]
-
-
-def _intact(raw, n, guard=64):
-    c = CANARY[raw.dtype]
-    return bool((raw[:guard] == c).all()) and bool((raw[guard + n:] == c).all())
-
-
 def _workspace(g, shape):
     nbytes = g.L().uz_vol_components_workspace(*shape)
     assert nbytes > 0
-    raw, ws = _guarded(nbytes, torch.uint8, g.dev(), 256)
+    raw, ws = g.guarded(nbytes, torch.uint8, 256)
     assert ws.data_ptr() % 16 == 0
-    return raw, ws, nbytes
+    return raw, ws
 
 
 def _label(g, vol, values, want_sizes=True):
@@ -46,16 +35,16 @@ def _label(g, vol, values, want_sizes=True):
     v = torch.from_numpy(np.array(vol)).to(dev)
     before = v.clone()
     T = vol.size
-    ws_raw, ws, nbytes = _workspace(g, vol.shape)
-    lab_raw, lab = _guarded(T, torch.int32, dev)
-    sz_raw, sz = _guarded(T, torch.int32, dev)
+    ws_raw, ws = _workspace(g, vol.shape)
+    lab_raw, lab = g.guarded(T, torch.int32)
+    sz_raw, sz = g.guarded(T, torch.int32)
     rc = L.uz_vol_label_components(v.data_ptr(), *vol.shape, K.region_bits(values), lab.data_ptr(), sz.data_ptr() if want_sizes else None,
                                    ws.data_ptr(), g.stream())
     torch.cuda.synchronize()
     assert rc == 0, L.uz_last_error()
-    assert _intact(ws_raw, nbytes, 256) and _intact(lab_raw, T) and _intact(sz_raw, T) and torch.equal(v, before)
+    assert g.intact(ws_raw, ws) and g.intact(lab_raw, lab) and g.intact(sz_raw, sz) and torch.equal(v, before)
     if not want_sizes:
-        assert bool((sz == CANARY[torch.int32]).all())
+        assert bool((sz == g.CANARY[torch.int32]).all())
     return lab.cpu().numpy().reshape(vol.shape), sz.cpu().numpy().reshape(vol.shape) if want_sizes else None
 
 
@@ -65,14 +54,14 @@ def _keep(g, vol, regions, mv, unlisted):
     v = torch.from_numpy(np.array(vol)).to(dev)
     before = v.clone()
     T, R = vol.size, len(regions)
-    ws_raw, ws, nbytes = _workspace(g, vol.shape)
-    out_raw, out = _guarded(T, torch.uint8, dev)
+    ws_raw, ws = _workspace(g, vol.shape)
+    out_raw, out = g.guarded(T, torch.uint8)
     sets = (C.c_uint32 * R)(*[K.region_bits(r) for r in regions])
     mins = (C.c_int32 * R)(*K.min_voxels_list(mv, R))
     rc = L.uz_vol_keep_components(v.data_ptr(), *vol.shape, sets, mins, R, int(unlisted == "keep"), out.data_ptr(), ws.data_ptr(), g.stream())
     torch.cuda.synchronize()
     assert rc == 0, L.uz_last_error()
-    assert _intact(ws_raw, nbytes, 256) and _intact(out_raw, T) and torch.equal(v, before)                # vol untouched
+    assert g.intact(ws_raw, ws) and g.intact(out_raw, out) and torch.equal(v, before)                # vol untouched
     return out.cpu().numpy().reshape(vol.shape)
 
 

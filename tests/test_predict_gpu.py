@@ -15,6 +15,7 @@ import torch
 import oracle
 from oracle import refgraph as R
 from tests import _golden as G
+from tests import _nets as N
 from tests import _predict as P
 
 pytestmark = pytest.mark.gpu
@@ -138,14 +139,7 @@ def test_sample_stats_ties_zero_probabilities_and_class_limits():
 # ------------------------------------------------------------------------------------------ model level
 def _state(seed=91):
     from unet_zoo_amd.models.phiseg import phiseg_spec
-    sd = oracle.deterministic_state_dict(phiseg_spec(1, 2, FILTERS), seed=seed)
-    for k, v in sd.items():                                                         # eval-mode BatchNorm far from the identity
-        n = torch.arange(v.numel(), dtype=torch.float32).reshape(v.shape)
-        if k.endswith("running_mean"):
-            v += 0.3 * torch.cos(1.7 * n + 0.3)
-        elif k.endswith("running_var"):
-            v *= 1.0 + 0.6 * torch.sin(2.3 * n + 1.1)
-    return sd
+    return N.off_identity_state(phiseg_spec(1, 2, FILTERS), seed)
 
 
 def _net(sd=None, graphs=False):

@@ -13,12 +13,11 @@ import torch
 
 import oracle
 from tests import _golden as G
+from tests import _nets as N
 from tests import _score as SC
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64                                                                           # canary elements in front of and behind every output
-CANARY = {torch.int32: -7777, torch.float32: -777.0, torch.float64: -777.0, torch.uint8: 0xA5}
 
 
 def _g():
@@ -26,27 +25,17 @@ def _g():
     return _gpu
 
 
-def _guarded(n, dtype, dev, guard=GUARD):
-    raw = torch.full((n + 2 * guard,), CANARY[dtype], dtype=dtype, device=dev)
-    return raw, raw[guard:guard + n]
-
-
-def _intact(raw, n, guard=GUARD):
-    c = CANARY[raw.dtype]
-    return bool((raw[:guard] == c).all()) and bool((raw[guard + n:] == c).all())
-
-
 def _call(g, labels, ann, mean_label, soft, K, with_counts=True, sizes=None, check=True):
     """One uz_score_samples call with every output and the workspace between canaries.  sizes overrides (B, S, A, K, P) as the call
     states them (refusals).  -> (rc, outputs as guarded (raw, view) pairs)."""
-    dev = g.dev()
     S, B, P = labels.shape
     A = ann.shape[1]
     L = g.L()
     nbytes = L.uz_score_workspace(B, S, A, K, P) if sizes is None else 4096
     np_ = SC.n_pairs(S, A)
-    out = dict(ws=_guarded(nbytes, torch.uint8, dev, 256), counts=_guarded(B * K * np_ * 3, torch.int32, dev), ged=_guarded(B, torch.float64, dev),
-               ncc_pairs=_guarded(B * A, torch.float32, dev), ncc=_guarded(B, torch.float64, dev), dice=_guarded(B * A * K, torch.float64, dev))
+    # 64 canary elements in front of and behind every output, 256 around the workspace
+    out = dict(ws=g.guarded(nbytes, torch.uint8, 256), counts=g.guarded(B * K * np_ * 3, torch.int32), ged=g.guarded(B, torch.float64),
+               ncc_pairs=g.guarded(B * A, torch.float32), ncc=g.guarded(B, torch.float64), dice=g.guarded(B * A * K, torch.float64))
     assert out["ws"][1].data_ptr() % 256 == 0
     b_, s_, a_, k_, p_ = sizes if sizes is not None else (B, S, A, K, P)
     rc = L.uz_score_samples(labels.data_ptr(), ann.data_ptr(), mean_label.data_ptr(), soft.data_ptr() if soft is not None else None,
@@ -56,7 +45,7 @@ def _call(g, labels, ann, mean_label, soft, K, with_counts=True, sizes=None, che
     if check:
         assert rc == 0, L.uz_last_error()
         for k, (raw, view) in out.items():
-            assert _intact(raw, view.numel(), 256 if k == "ws" else GUARD), k
+            assert g.intact(raw, view), k
     return rc, out
 
 
@@ -126,7 +115,7 @@ def _check_case(g, c):
     _, bare = _call(g, labels, ann, mean_label, None, K, with_counts=False)
     assert torch.equal(bare["ged"][1], out["ged"][1]) and torch.equal(bare["dice"][1], out["dice"][1]), c
     for k in ("counts", "ncc_pairs", "ncc"):                                            # null counts / null soft: untouched
-        assert bool((bare[k][0] == CANARY[bare[k][0].dtype]).all()), (c, k)
+        assert bool((bare[k][0] == g.CANARY[bare[k][0].dtype]).all()), (c, k)
     for t, a in ((labels, v.labels), (ann, v.ann), (mean_label, v.mean_label)):
         assert np.array_equal(t.cpu().numpy(), a), c                                   # the inputs are read only
 
@@ -166,7 +155,7 @@ def test_score_samples_refusals_write_nothing():
         rc, out = _call(g, labels, ann, mean_label, soft, K, sizes=sizes, check=False)
         assert rc != 0 and L.uz_last_error(), sizes
         for k, (raw, _) in out.items():
-            assert bool((raw == CANARY[raw.dtype]).all()), (sizes, k)
+            assert bool((raw == g.CANARY[raw.dtype]).all()), (sizes, k)
     assert L.uz_score_workspace(B, S, A, K, P) > 0
     assert L.uz_score_workspace(1 << 12, 1 << 12, 4, 2, 1 << 12) == 0                   # S B P past int32
 
@@ -230,17 +219,6 @@ def _annotators(B, H, W, A=4, seed=23):
     return np.stack([np.roll(m, shift=(a, -a), axis=(1, 2)) for a in range(A)], axis=1)          # (B, A, H, W), as SyntheticData's
 
 
-def _off_identity(sd):
-    """Running statistics moved off the identity, as tests/_predict's users do."""
-    for k, v in sd.items():
-        n = torch.arange(v.numel(), dtype=torch.float32).reshape(v.shape)
-        if k.endswith("running_mean"):
-            v += 0.3 * torch.cos(1.7 * n + 0.3)
-        elif k.endswith("running_var"):
-            v *= 1.0 + 0.6 * torch.sin(2.3 * n + 1.1)
-    return sd
-
-
 def _model_prediction(model):
     dev = torch.device("cuda", 0)
     B, S = MODEL_BS
@@ -248,14 +226,14 @@ def _model_prediction(model):
     if model == "phiseg":
         from unet_zoo_amd.models.phiseg import PHISeg, phiseg_spec
         net = PHISeg(1, 2, PHISEG_FILTERS, image_size=(1, H, W))
-        sd = _off_identity(oracle.deterministic_state_dict(phiseg_spec(1, 2, PHISEG_FILTERS), seed=91))
+        sd = N.off_identity_state(phiseg_spec(1, 2, PHISEG_FILTERS), seed=91)
         shapes = oracle.phiseg_eps_shapes(B * S, H, W)
         x, _, eps = oracle.synthetic_batch(B * S, H, W, seed=45, eps_shapes=shapes)
         eps = [torch.from_numpy(a).to(dev) for a in eps]
     else:
         from unet_zoo_amd.models.probabilistic_unet import ProbabilisticUnet, probunet_spec
         net = ProbabilisticUnet(1, 2, PROBUNET_FILTERS, latent_dim=6, no_convs_fcomb=3, image_size=(1, H, W))
-        sd = _off_identity(oracle.deterministic_state_dict(probunet_spec(1, 2, PROBUNET_FILTERS, 6, 3), seed=1239))
+        sd = N.off_identity_state(probunet_spec(1, 2, PROBUNET_FILTERS, 6, 3), seed=1239)
         x, _, eps = oracle.synthetic_batch(B * S, H, W, seed=85, eps_shapes=[(S * B, 6)])
         eps = torch.from_numpy(eps[0]).to(dev)
     res = net.load_state_dict(sd)

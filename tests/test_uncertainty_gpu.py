@@ -22,36 +22,20 @@ def _g():
     return _gpu
 
 
-def _filled(nbytes, dev):
-    """nbytes of 0xFF between two guards of 0xFF, 16-byte aligned -> (raw, body)"""
-    raw = torch.full((nbytes + 2 * GUARD,), 0xFF, dtype=torch.uint8, device=dev)
-    assert raw.data_ptr() % 16 == 0
-    return raw, raw[GUARD:GUARD + nbytes]
-
-
-def _embed(arr, off, dev):
-    """the array's bytes at `off` bytes behind a 16-byte boundary of a larger buffer of 0xEE"""
-    buf = torch.full((arr.size + 64,), 0xEE, dtype=torch.uint8, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    view = buf[off:off + arr.size]
-    view.copy_(torch.from_numpy(np.array(arr)).reshape(-1))
-    return buf, view
-
-
 def _run(g, smp, dec, ref, preg, rreg, want_votes, off=0, stream=None):
     """One uz_vol_uncertainty call -> dict of numpy results (votes None when not asked for)"""
-    dev, L = g.dev(), g.L()
+    L = g.L()
     S, (D, H, W) = smp.shape[0], dec.shape
     R, P = len(preg), dec.size
-    sb, sv = _embed(smp, off, dev)
-    db, dv = _embed(dec, off, dev)
-    rb, rv = _embed(ref, off, dev)
+    sb, sv = g.embed(smp, off)
+    db, dv = g.embed(dec, off)
+    rb, rv = g.embed(ref, off)
     nbytes = L.uz_vol_uncertainty_workspace(S, R, D, H, W)
     assert nbytes > 0
     sizes = dict(ws=nbytes, table=R * (S + 1) * 4 * 8, levels=R * (S + 1) * 4 * 8, curves=R * (S + 1) * 3 * 8, auc=R * 4 * 8, cal=R * 3 * 8, votes=R * P + 16)
     raw, body = {}, {}
     for k, n in sizes.items():
-        raw[k], body[k] = _filled(n, dev)
+        raw[k], body[k] = g.guarded(n, torch.uint8, GUARD, 0xFF)
     votes = body["votes"][off:off + R * P]
     psets = (C.c_uint32 * R)(*[U.region_bits(x) for x in preg])
     rsets = (C.c_uint32 * R)(*[U.region_bits(x) for x in rreg])
@@ -62,12 +46,12 @@ def _run(g, smp, dec, ref, preg, rreg, want_votes, off=0, stream=None):
     torch.cuda.synchronize()
     assert rc == 0, L.uz_last_error()
     for k in sizes:                                                      # nothing outside the buffers
-        assert bool((raw[k][:GUARD] == 0xFF).all()) and bool((raw[k][GUARD + sizes[k]:] == 0xFF).all()), k
-    assert bool((body["votes"][:off] == 0xFF).all()) and bool((body["votes"][off + R * P:] == 0xFF).all())
+        assert g.intact(raw[k], body[k], 0xFF), k
+    assert g.intact(body["votes"], votes, 0xFF)
     if not want_votes:
         assert bool((body["votes"] == 0xFF).all())
     for buf, view, arr in ((sb, sv, smp), (db, dv, dec), (rb, rv, ref)):  # the inputs untouched
-        assert view.cpu().numpy().tobytes() == arr.tobytes() and bool((buf[:off] == 0xEE).all()) and bool((buf[off + arr.size:] == 0xEE).all())
+        assert view.cpu().numpy().tobytes() == arr.tobytes() and g.intact(buf, view, 0xEE)
     as_np = lambda k, dt, shape: body[k].cpu().numpy().view(dt).reshape(shape).copy()
     return dict(table=as_np("table", np.int64, (R, S + 1, 2, 2)), levels=as_np("levels", np.int64, (R, S + 1, 4)), curves=as_np("curves", np.float64, (R, S + 1, 3)),
                 auc=as_np("auc", np.float64, (R, 4)), cal=as_np("cal", np.float64, (R, 3)),
@@ -207,14 +191,12 @@ def test_predict_then_score_uncertainty_end_to_end():
     """PHISeg3D.predict(n_samples=4) -> score_uncertainty, as it is, filtered by keep_largest_components, and with decision= given"""
     import oracle
     from tests import _golden as G
+    from tests import _nets as N
     from unet_zoo_amd import metrics
-    from unet_zoo_amd.models.phiseg3D import PHISeg3D
     g = _g()
     dev = g.dev()
     arrays, meta = G.load("phiseg3d_small")
-    net = PHISeg3D(meta["input_channels"], meta["num_classes"], meta["filters"], latent_levels=meta["latent_levels"], image_size=(meta["input_channels"], *meta["dhw"]))
-    net.load_state_dict(oracle.deterministic_state_dict(G.spec_of(meta), seed=91))
-    net.eval()
+    net = N.small_phiseg3d(meta, oracle.deterministic_state_dict(G.spec_of(meta), seed=91))
     torch.manual_seed(5)
     with torch.no_grad():
         pred = net.predict(torch.from_numpy(arrays["patch"]).to(dev), n_samples=4)

@@ -12,9 +12,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import oracle
 from oracle import refgraph3d as R3
 from tests import _golden as G
+from tests import _nets as N
 from tests import _predict as P
 from tests import _vol_stats as VS
 
@@ -34,35 +34,25 @@ class _Out:
     """The outputs of one accum ... accum, finish sequence, each inside a buffer with PAD canary elements in front and behind;
     shift: elements the running sum (and mean_soft) start off their 16-byte boundary."""
 
-    def __init__(self, dev, K, S, n, soft=True, shift=0):
-        def raw(count, dtype, fill):
-            return torch.full((count + 2 * PAD + shift,), fill, dtype=dtype, device=dev)
-        self.n, self.K, self.S, self.shift = n, K, S, shift
-        self.raw = dict(labels=raw(S * n, torch.uint8, CANARY_B), soft=raw(S * K * n, torch.float32, CANARY_F) if soft else None,
-                        acc=raw(K * n, torch.float64, CANARY_F), mean_soft=raw(K * n, torch.float32, CANARY_F),
-                        mean_label=raw(n, torch.uint8, CANARY_B), entropy=raw(n, torch.float32, CANARY_F))
-
-    def _lo(self, name):
-        return PAD + (self.shift if name in ("acc", "mean_soft") else 0)
+    def __init__(self, g, K, S, n, soft=True, shift=0):
+        def buf(count, dtype, off=0):
+            return g.guarded(count, dtype, PAD, CANARY_B if dtype == torch.uint8 else CANARY_F, off, room=shift)
+        self.g, self.n, self.K, self.S = g, n, K, S
+        bufs = dict(labels=buf(S * n, torch.uint8), soft=buf(S * K * n, torch.float32) if soft else (None, None),
+                    acc=buf(K * n, torch.float64, shift), mean_soft=buf(K * n, torch.float32, shift),
+                    mean_label=buf(n, torch.uint8), entropy=buf(n, torch.float32))
+        self.raw = {k: b[0] for k, b in bufs.items()}
+        self.bodies = {k: b[1] for k, b in bufs.items()}
 
     def body(self, name):
-        t = self.raw[name]
-        lo = self._lo(name)
-        return None if t is None else t[lo:t.numel() - (2 * PAD + self.shift - lo)]
+        return self.bodies[name]
 
     def ptr(self, name, offset=0):
         t = self.body(name)
         return None if t is None else t.data_ptr() + offset * t.element_size()
 
     def canaries_intact(self):
-        for name, t in self.raw.items():
-            if t is None:
-                continue
-            lo, m = self._lo(name), self.body(name).numel()
-            want = CANARY_B if t.dtype == torch.uint8 else CANARY_F
-            if not (bool((t[:lo] == want).all()) and bool((t[lo + m:] == want).all())):
-                return False
-        return True
+        return all(self.g.intact(t, self.bodies[k], CANARY_B if t.dtype == torch.uint8 else CANARY_F) for k, t in self.raw.items() if t is not None)
 
     def untouched(self):
         return all(bool((t == (CANARY_B if t.dtype == torch.uint8 else CANARY_F)).all()) for t in self.raw.values() if t is not None)
@@ -96,7 +86,7 @@ def _dev_levels(g, c, levels, s, K, fill):
 def _run_pair(g, c, levels, K, S, fill=float("nan"), soft=True, shift=0):
     D, H, W = c.dhw
     n = D * H * W
-    out = _Out(g.dev(), K, S, n, soft=soft, shift=shift)
+    out = _Out(g, K, S, n, soft=soft, shift=shift)
     for s in range(S):
         bufs, tabs = _dev_levels(g, c, levels, s, K, fill)
         g.call("uz_vol_sample_accum", *tabs, len(levels), K, D, H, W, out.ptr("labels", s * n), out.ptr("soft", s * K * n) if soft else None,
@@ -169,7 +159,7 @@ def test_vol_stats_refusals_write_nothing():
     n = D * H * W
     levels, _, _ = VS.vol_case(6, K, S)
     bufs, (ptrs, ctot, f, fz) = _dev_levels(g, c, levels, 0, K, float("nan"))
-    out = _Out(g.dev(), K, S, n)
+    out = _Out(g, K, S, n)
     ints = lambda *v: (ctypes.c_int * len(v))(*v)                                   # noqa: E731
     good = dict(ptrs=ptrs, ctot=ctot, f=f, fz=fz, L=2, K=K, dhw=(D, H, W), labels=out.ptr("labels"), soft=out.ptr("soft"), acc=out.ptr("acc"))
     bad = [dict(K=0), dict(K=9), dict(L=0), dict(L=9), dict(ptrs=None), dict(ctot=None), dict(f=None), dict(fz=None), dict(labels=None),
@@ -199,27 +189,7 @@ def test_vol_stats_refusals_write_nothing():
 SAMPLES = 3
 
 
-def _state(meta, seed=91):
-    sd = oracle.deterministic_state_dict(G.spec_of(meta), seed=seed)
-    for k, v in sd.items():                                                         # eval-mode BatchNorm far from the identity
-        nn = torch.arange(v.numel(), dtype=torch.float32).reshape(v.shape)
-        if k.endswith("running_mean"):
-            v += 0.3 * torch.cos(1.7 * nn + 0.3)
-        elif k.endswith("running_var"):
-            v *= 1.0 + 0.6 * torch.sin(2.3 * nn + 1.1)
-    return sd
-
-
-def _net(meta, sd, graphs=False, reversible=False):
-    from unet_zoo_amd.models.phiseg3D import PHISeg3D
-    net = PHISeg3D(meta["input_channels"], meta["num_classes"], meta["filters"], latent_levels=meta["latent_levels"], reversible=reversible,
-                   image_size=(meta["input_channels"], *meta["dhw"]))
-    if sd is not None:
-        res = net.load_state_dict(sd)
-        assert not res.missing_keys and not res.unexpected_keys
-    net.eval()
-    net.enable_graphs(graphs)
-    return net
+_state, _net = N.off_identity_state, N.small_phiseg3d
 
 
 def _predict(net, c, eps=None, **kw):

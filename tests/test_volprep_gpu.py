@@ -25,52 +25,31 @@ def _g():
     return _gpu
 
 
-def _filled(nbytes, dev, off=0):
-    """nbytes of 0xFF `off` bytes behind a 16-byte boundary, between guards of 0xFF -> (raw, body)"""
-    raw = torch.full((nbytes + 2 * GUARD + 16,), 0xFF, dtype=torch.uint8, device=dev)
-    assert raw.data_ptr() % 16 == 0
-    return raw, raw[GUARD + off:GUARD + off + nbytes]
-
-
-def _intact(raw, body_bytes, off=0):
-    return bool((raw[:GUARD + off] == 0xFF).all()) and bool((raw[GUARD + off + body_bytes:] == 0xFF).all())
-
-
-def _embed(arr, off, dev):
-    """the array's bytes `off` bytes behind a 16-byte boundary of a larger buffer of 0xEE"""
-    b = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
-    buf = torch.full((b.size + 64,), 0xEE, dtype=torch.uint8, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    view = buf[off:off + b.size]
-    view.copy_(torch.from_numpy(b.copy()))
-    return buf, view
-
-
 def _prepare(g, c, off=None, with_mask=True, stream=None):
     """One uz_vol_prepare call -> V.Prepared of numpy arrays"""
-    dev, L = g.dev(), g.L()
+    L = g.L()
     off = c.offset if off is None else off
     (X, Y, Z, Cn), (Xt, Yt, Zt) = c.raw.shape, c.size
     Pt = Xt * Yt * Zt
-    rb, rv = _embed(c.raw, off, dev)
-    mb, mv = _embed(c.mask, 1, dev)
+    rb, rv = g.embed(c.raw, off)
+    mb, mv = g.embed(c.mask, 1)
     nbytes = L.uz_vol_prepare_workspace(Cn, X, Y, Z, Xt, Yt, Zt)
     assert nbytes > 0
     sizes = dict(ws=(nbytes, 0), image=(Pt * Cn * 4, off), mask=(Pt, 3), info=(64, 4), stats=(Cn * 24, 8))
     raw, body = {}, {}
     for k, (n, o) in sizes.items():
-        raw[k], body[k] = _filled(n, dev, o)
+        raw[k], body[k] = g.guarded(n, torch.uint8, GUARD, 0xFF, o, room=16)      # 0xFF, o bytes behind a 16-byte boundary, between guards of 0xFF
     st = g.stream() if stream is None else stream.cuda_stream
     rc = L.uz_vol_prepare(rv.data_ptr(), mv.data_ptr() if with_mask else None, Cn, X, Y, Z, Xt, Yt, Zt, c.placement, body["ws"].data_ptr(),
                           body["image"].data_ptr(), body["mask"].data_ptr() if with_mask else None, body["info"].data_ptr(), body["stats"].data_ptr(), st)
     torch.cuda.synchronize()
     assert rc == 0, L.uz_last_error()
     for k, (n, o) in sizes.items():                                        # nothing outside the buffers
-        assert _intact(raw[k], n, o), k
+        assert g.intact(raw[k], body[k], 0xFF), k
     if not with_mask:
         assert bool((body["mask"] == 0xFF).all())
     for buf, view, arr, o in ((rb, rv, c.raw, off), (mb, mv, c.mask, 1)):   # the inputs untouched
-        assert view.cpu().numpy().tobytes() == arr.tobytes() and bool((buf[:o] == 0xEE).all()) and bool((buf[o + arr.nbytes:] == 0xEE).all())
+        assert view.cpu().numpy().tobytes() == arr.tobytes() and g.intact(buf, view, 0xEE)
     as_np = lambda k, dt, shape: body[k].cpu().numpy().view(dt).reshape(shape).copy()
     return V.Prepared(as_np("image", np.float32, (Xt, Yt, Zt, Cn)), as_np("mask", np.uint8, (Xt, Yt, Zt)) if with_mask else None,
                       as_np("info", np.int32, (16,)), as_np("stats", np.float64, (Cn, 3)))
@@ -176,10 +155,10 @@ def _restore(g, rows, place, native, lut, fill, off=0, stream=None):
     dev, L = g.dev(), g.L()
     N = rows.shape[0]
     elem = rows.dtype.itemsize
-    rb, rv = _embed(rows, off, dev)
+    rb, rv = g.embed(rows, off)
     pl = torch.tensor(list(place), dtype=torch.int32, device=dev)
     nbytes = N * int(np.prod(native)) * elem
-    raw, body = _filled(nbytes, dev, off)
+    raw, body = g.guarded(nbytes, torch.uint8, GUARD, 0xFF, off, room=16)
     table = None
     if lut is not None:
         table = (C.c_uint8 * 256)(*range(256))
@@ -192,8 +171,8 @@ def _restore(g, rows, place, native, lut, fill, off=0, stream=None):
     del table                                                              # the lut travelled in the launch arguments
     torch.cuda.synchronize()
     assert rc == 0, L.uz_last_error()
-    assert _intact(raw, nbytes, off)
-    assert rv.cpu().numpy().tobytes() == rows.tobytes() and bool((rb[:off] == 0xEE).all()) and bool((rb[off + rows.nbytes:] == 0xEE).all())
+    assert g.intact(raw, body, 0xFF)
+    assert rv.cpu().numpy().tobytes() == rows.tobytes() and g.intact(rb, rv, 0xEE)
     return body.cpu().numpy().view(rows.dtype).reshape((N,) + tuple(native)).copy()
 
 
@@ -288,15 +267,13 @@ def test_raw_case_to_native_space_scores_end_to_end():
     the BraTS labels -> score_volume against the native mask"""
     import oracle
     from tests import _golden as G
+    from tests import _nets as N
     from unet_zoo_amd import data, metrics
-    from unet_zoo_amd.models.phiseg3D import PHISeg3D
     g = _g()
     dev = g.dev()
     _, meta = G.load("phiseg3d_small")
     Cn, K = int(meta["input_channels"]), int(meta["num_classes"])
-    net = PHISeg3D(Cn, K, meta["filters"], latent_levels=meta["latent_levels"], image_size=(Cn, 32, 32, 32))
-    net.load_state_dict(oracle.deterministic_state_dict(G.spec_of(meta), seed=91))
-    net.eval()
+    net = N.small_phiseg3d(dict(meta, dhw=(32, 32, 32)), oracle.deterministic_state_dict(G.spec_of(meta), seed=91))
     native, box = (40, 36, 33), ([3, 1, 0], [39, 36, 31])                  # 36 x 35 x 31: crop, crop, pad
     raw = V._boxed(77, shape=native, Cn=Cn, box=box)
     mask = V._mask(78, native)

@@ -15,23 +15,12 @@ from tests import _volscore as V
 
 pytestmark = pytest.mark.gpu
 
-CANARY = {torch.int32: -7777, torch.int64: -7777, torch.float64: -777.0, torch.uint8: 0xA5}
 NAMES = [c.name for c in V.CASES]
 
 
 def _g():
     from tests import _gpu
     return _gpu
-
-
-def _guarded(n, dtype, dev, guard=64):
-    raw = torch.full((n + 2 * guard,), CANARY[dtype], dtype=dtype, device=dev)
-    return raw, raw[guard:guard + n]
-
-
-def _intact(raw, n, guard=64):
-    c = CANARY[raw.dtype]
-    return bool((raw[:guard] == c).all()) and bool((raw[guard + n:] == c).all())
 
 
 def _sets(regions):
@@ -48,15 +37,15 @@ def _scores(g, pred, ref, pred_regions, ref_regions=None, hd=1):
     r = torch.from_numpy(np.array(ref)).to(dev)
     nbytes = L.uz_vol_region_scores_workspace(N, R, D, H, W, hd)
     assert nbytes > 0
-    ws = _guarded(nbytes, torch.uint8, dev, 256)
-    counts = _guarded(N * R * 4, torch.int64, dev)
-    scores = _guarded(N * R * 4, torch.float64, dev)
+    ws = g.guarded(nbytes, torch.uint8, 256)
+    counts = g.guarded(N * R * 4, torch.int64)
+    scores = g.guarded(N * R * 4, torch.float64)
     assert ws[1].data_ptr() % 16 == 0
     rc = L.uz_vol_region_scores(p.data_ptr(), N, _sets(pred_regions), r.data_ptr(), _sets(ref_regions or pred_regions), R, D, H, W, hd,
                                 ws[1].data_ptr(), counts[1].data_ptr(), scores[1].data_ptr(), g.stream())
     torch.cuda.synchronize()
     assert rc == 0, L.uz_last_error()
-    assert _intact(ws[0], nbytes, 256) and _intact(counts[0], N * R * 4) and _intact(scores[0], N * R * 4)
+    assert g.intact(*ws) and g.intact(*counts) and g.intact(*scores)
     return counts[1].cpu().numpy().reshape(N, R, 4), scores[1].cpu().numpy().reshape(N, R, 4)
 
 
@@ -84,12 +73,12 @@ def _edt(g, seeds):
     L = g.L()
     s = torch.from_numpy(np.array(seeds)).to(dev)
     nbytes = L.uz_vol_edt_sq_workspace(D, H, W)
-    ws = _guarded(nbytes, torch.uint8, dev, 256)
-    d2 = _guarded(D * H * W, torch.int32, dev)
+    ws = g.guarded(nbytes, torch.uint8, 256)
+    d2 = g.guarded(D * H * W, torch.int32)
     rc = L.uz_vol_edt_sq(s.data_ptr(), D, H, W, d2[1].data_ptr(), ws[1].data_ptr(), g.stream())
     torch.cuda.synchronize()
     assert rc == 0, L.uz_last_error()
-    assert _intact(ws[0], nbytes, 256) and _intact(d2[0], D * H * W)
+    assert g.intact(*ws) and g.intact(*d2)
     return d2[1].cpu().numpy().reshape(D, H, W)
 
 

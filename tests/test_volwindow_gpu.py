@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-import oracle
 from tests import _golden as G
+from tests import _nets as N
 from tests import _volwindow as VW
 
 pytestmark = pytest.mark.gpu
@@ -40,25 +40,23 @@ class _Bufs:
     """Accumulators and outputs of one call sequence, each with PAD canary elements in front and behind."""
 
     def __init__(self, K, S, n, soft=True, mean_label=True, entropy=True):
-        dev = _dev()
+        from tests import _gpu
 
-        def raw(count, dtype):
-            return torch.full((count + 2 * PAD,), CANARY_B if dtype == torch.uint8 else CANARY_F, dtype=dtype, device=dev)
-        self.raw = dict(acc=raw(S * K * n, torch.float64), wsum=raw(n, torch.float64), labels=raw(S * n, torch.uint8),
-                        soft=raw(S * K * n, torch.float32) if soft else None, mean_soft=raw(K * n, torch.float32),
-                        mean_label=raw(n, torch.uint8) if mean_label else None, entropy=raw(n, torch.float32) if entropy else None)
+        def buf(count, dtype):
+            return _gpu.guarded(count, dtype, PAD, CANARY_B if dtype == torch.uint8 else CANARY_F)
+        none = (None, None)
+        bufs = dict(acc=buf(S * K * n, torch.float64), wsum=buf(n, torch.float64), labels=buf(S * n, torch.uint8),
+                    soft=buf(S * K * n, torch.float32) if soft else none, mean_soft=buf(K * n, torch.float32),
+                    mean_label=buf(n, torch.uint8) if mean_label else none, entropy=buf(n, torch.float32) if entropy else none)
+        self.intact = _gpu.intact
+        self.raw = {k: b[0] for k, b in bufs.items()}
+        self.bodies = {k: b[1] for k, b in bufs.items()}
 
     def body(self, name):
-        t = self.raw[name]
-        return None if t is None else t[PAD:t.numel() - PAD]
+        return self.bodies[name]
 
     def canaries_intact(self):
-        for t in self.raw.values():
-            if t is not None:
-                want = CANARY_B if t.dtype == torch.uint8 else CANARY_F
-                if not (bool((t[:PAD] == want).all()) and bool((t[-PAD:] == want).all())):
-                    return False
-        return True
+        return all(self.intact(t, self.bodies[k], CANARY_B if t.dtype == torch.uint8 else CANARY_F) for k, t in self.raw.items() if t is not None)
 
 
 def _run_case(d, K, S, soft=True, mean_label=True, entropy=True, fill=float("nan")):
@@ -176,27 +174,7 @@ SAMPLES = 3
 NETS = {"phiseg3d_small": dict(volume=(21, 18, 13), stride=(8, 8, 4)), "phiseg3d_l3": dict(volume=(13, 18, 21), stride=(4, 8, 8))}
 
 
-def _state(meta, seed=91):
-    sd = oracle.deterministic_state_dict(G.spec_of(meta), seed=seed)
-    for k, v in sd.items():                                                         # eval-mode BatchNorm far from the identity (test_vol_stats_gpu.py)
-        nn = torch.arange(v.numel(), dtype=torch.float32).reshape(v.shape)
-        if k.endswith("running_mean"):
-            v += 0.3 * torch.cos(1.7 * nn + 0.3)
-        elif k.endswith("running_var"):
-            v *= 1.0 + 0.6 * torch.sin(2.3 * nn + 1.1)
-    return sd
-
-
-def _net(meta, sd, graphs=False, reversible=False):
-    from unet_zoo_amd.models.phiseg3D import PHISeg3D
-    net = PHISeg3D(meta["input_channels"], meta["num_classes"], meta["filters"], latent_levels=meta["latent_levels"], reversible=reversible,
-                   image_size=(meta["input_channels"], *meta["dhw"]))
-    if sd is not None:
-        res = net.load_state_dict(sd)
-        assert not res.missing_keys and not res.unexpected_keys
-    net.eval()
-    net.enable_graphs(graphs)
-    return net
+_state, _net = N.off_identity_state, N.small_phiseg3d
 
 
 def _eps_shapes(c, padded, S):

@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void pair_counts_k(const uint8_t* __restrict__
         const int x = pa[q] == label, y = pb[q] == label;
         inter += x & y; ca += x; cb += y;
     }
-    for (int o = 32; o > 0; o >>= 1) { inter += __shfl_xor(inter, o, 64); ca += __shfl_xor(ca, o, 64); cb += __shfl_xor(cb, o, 64); }
+    inter = uz::wave_sum(inter); ca = uz::wave_sum(ca); cb = uz::wave_sum(cb);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { sm[0][w] = inter; sm[1][w] = ca; sm[2][w] = cb; }
     __syncthreads();

@@ -58,12 +58,6 @@ __global__ __launch_bounds__(256) void score_planes_k(const uint8_t* __restrict_
     }
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // One wave per item.  Items 0 .. B*K*NP-1 (NP = S*A + S*S + A*A): item = (b*K + k)*NP + t, t walks [S][A], [S][S], [A][A] row-major
 // -> counts[item*3 + 0..2].  Items behind them: d = (b*A + j)*K + k -> dice[d] of mean_label[b] against annotator j.
 __global__ __launch_bounds__(256) void score_pairs_k(const u64* __restrict__ planes, int B, int S, int A, int K, int W64, long long NP,
@@ -96,7 +90,7 @@ __global__ __launch_bounds__(256) void score_pairs_k(const u64* __restrict__ pla
         const u64 xv = x[w], yv = y[w];
         inter += __popcll(xv & yv); ca += __popcll(xv); cb += __popcll(yv);
     }
-    inter = wave_sum_i(inter); ca = wave_sum_i(ca); cb = wave_sum_i(cb);
+    inter = uz::wave_sum(inter); ca = uz::wave_sum(ca); cb = uz::wave_sum(cb);
     if (lane != 0) return;
     if (g < nG) {
         int* out = counts + g * 3;

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <limits.h>
+#include <algorithm>
 #include <type_traits>
 #include "uz_api.h"
 
@@ -30,16 +32,25 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+// Reductions over the 64 lanes of a wave, a butterfly in the order o = 32 .. 1: every lane ends with the result.
+template <class T> __device__ __forceinline__ T lane_xor(T v, int o) { return __shfl_xor(v, o, 64); }
+template <> __device__ __forceinline__ unsigned long long lane_xor(unsigned long long v, int o) { return (unsigned long long)__shfl_xor((long long)v, o, 64); }
+template <class T> __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int o = 32; o > 0; o >>= 1) v += lane_xor(v, o);
     return v;
 }
-__device__ __forceinline__ double wave_sum_d(double v) {
+template <class T> __device__ __forceinline__ T wave_min(T v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int o = 32; o > 0; o >>= 1) v = min(v, lane_xor(v, o));
     return v;
 }
+template <class T> __device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, lane_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ double wave_sum_d(double v) { return wave_sum<double>(v); }
 
 // Block-wide sum of NV doubles (blockDim.x == 256).  Result valid in thread 0.
 template <int NV>
@@ -144,6 +155,21 @@ struct VolLevels {
     const float* p[VOL_LEVELS_MAX];
     int ctot[VOL_LEVELS_MAX], f[VOL_LEVELS_MAX], fz[VOL_LEVELS_MAX];
 };
+
+// What the volume post-processing files share (volscore.hip, volcomp.hip, voluncert.hip, volprep.hip).
+// Regions as sets of label values, bit v = value v: of the prediction (p) and of the reference (r); it travels as a kernel argument.
+struct RegionSets { uint32_t p[UZ_VOL_MAX_REGIONS], r[UZ_VOL_MAX_REGIONS]; };
+static inline RegionSets region_sets(const uint32_t* p, const uint32_t* r, int R) {       // sets beyond R are empty
+    RegionSets s = {};
+    for (int i = 0; i < R; ++i) { s.p[i] = p[i]; s.r[i] = r[i]; }
+    return s;
+}
+__host__ __device__ __forceinline__ bool in_set(unsigned v, uint32_t set) { return v < 32u && ((set >> (v & 31u)) & 1u); }
+static inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+// workgroups of `threads` that would cover work_items in one sweep (at least one), capped
+static inline int sweep_grid(long long work_items, int threads, long long cap = INT_MAX) {
+    return (int)std::min<long long>((std::max<long long>(work_items, 1) + threads - 1) / threads, cap);
+}
 
 // conv_split.hip: 3x3 forward / data gradient on the fp16 matrix pipe with two-piece split operands (fp32-accurate)
 bool conv_split_ok(int Kc, int Mc, int N, int H, int W, int ks, int dgrad);

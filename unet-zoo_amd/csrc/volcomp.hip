@@ -25,10 +25,7 @@ constexpr int SEL_VOX = 4096;           // voxels of one volume a workgroup of t
 
 #define UZ_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-__device__ __forceinline__ bool member(const uint8_t* __restrict__ lab, long long idx, uint32_t set) {
-    const unsigned v = lab[idx];
-    return v < 32u && ((set >> (v & 31u)) & 1u);
-}
+__device__ __forceinline__ bool member(const uint8_t* __restrict__ lab, long long idx, uint32_t set) { return uz::in_set(lab[idx], set); }
 
 // ------------------------------------------------------------------------------------------------ runs
 __global__ __launch_bounds__(256) void comp_runs_k(const uint8_t* __restrict__ vol, uint32_t set, long long rows, int W, int N,
@@ -132,8 +129,7 @@ __global__ __launch_bounds__(256) void comp_select_k(const int* __restrict__ par
             const long long g = off + v;
             if (parent[g] == (int)g) mine = max(mine, ((unsigned long long)(unsigned)cnt[g] << 32) | (0xFFFFFFFFull - (unsigned)v));
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mine = max(mine, (unsigned long long)__shfl_xor((long long)mine, o, 64));
+        mine = uz::wave_max(mine);
         if ((threadIdx.x & 63) == 0 && mine) atomicMax(&best[n], mine);
     }
 }
@@ -183,9 +179,8 @@ const char* sizes_bad(int N, int D, int H, int W) {
     for (int f : {D, H, W}) { t *= f; if (t >= (1LL << 31)) return "N*D*H*W must stay below 2^31"; }
     return nullptr;
 }
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-inline int vox_grid(long long T) { return (int)std::min<long long>((T + 255) / 256, VOX_GRID_MAX); }
-inline int row_grid(long long rows) { return (int)std::min<long long>((rows + 3) / 4, ROW_GRID_MAX); }
+inline int vox_grid(long long T) { return uz::sweep_grid(T, 256, VOX_GRID_MAX); }
+inline int row_grid(long long rows) { return uz::sweep_grid(rows, 4, ROW_GRID_MAX); }
 inline int sel_per_vol(int P) { return (int)(((long long)P + SEL_VOX - 1) / SEL_VOX); }
 inline int sel_grid(int N, int P) { return (int)std::min<long long>((long long)N * sel_per_vol(P), VOX_GRID_MAX); }
 
@@ -194,8 +189,8 @@ inline Ws carve(void* workspace, int N, long long T) {
     char* b = static_cast<char*>(workspace);
     Ws w;
     w.best = reinterpret_cast<unsigned long long*>(b);
-    w.parent = reinterpret_cast<int*>(b + up16((size_t)N * 8));
-    w.cnt = reinterpret_cast<int*>(b + up16((size_t)N * 8) + up16((size_t)T * 4));
+    w.parent = reinterpret_cast<int*>(b + uz::up16((size_t)N * 8));
+    w.cnt = reinterpret_cast<int*>(b + uz::up16((size_t)N * 8) + uz::up16((size_t)T * 4));
     return w;
 }
 
@@ -214,7 +209,7 @@ int label_set(const uint8_t* vol, uint32_t set, int N, int D, int H, int W, cons
 
 extern "C" size_t uz_vol_components_workspace(int N, int D, int H, int W) {
     if (sizes_bad(N, D, H, W)) return 0;
-    return up16((size_t)N * 8) + 2 * up16((size_t)N * D * H * W * 4);
+    return uz::up16((size_t)N * 8) + 2 * uz::up16((size_t)N * D * H * W * 4);
 }
 
 extern "C" int uz_vol_components_route(int N, int D, int H, int W, int* out2) {

@@ -63,22 +63,11 @@ __device__ __forceinline__ bool any_positive(const float* __restrict__ raw, unsi
     }
 }
 
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // lo[3] (minimum) and hi[3] (maximum + 1, 0 = none) of a workgroup into thread 0
 __device__ __forceinline__ void block_box(int (&lo)[3], int (&hi)[3], int (*sm)[6]) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { lo[a] = wave_min_i(lo[a]); hi[a] = wave_max_i(hi[a]); }
+    for (int a = 0; a < 3; ++a) { lo[a] = uz::wave_min(lo[a]); hi[a] = uz::wave_max(hi[a]); }
     if (lane == 0) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { sm[wave][a] = lo[a]; sm[wave][3 + a] = hi[a]; }
@@ -204,9 +193,7 @@ __global__ __launch_bounds__(TB) void prep_sums_k(const float* __restrict__ raw,
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         acc[c] = uz::wave_sum_d(acc[c]);
-        int n = cnt[c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+        const int n = uz::wave_sum(cnt[c]);
         if (lane == 0) { smd[wave][c] = acc[c]; smn[wave][c] = n; }
     }
     __syncthreads();
@@ -231,8 +218,7 @@ __global__ __launch_bounds__(TB) void prep_fold_stats_k(const SumSlice* __restri
         if (phase == 0) n += slices[k].n[c];
     }
     s = uz::wave_sum_d(s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    n = uz::wave_sum(n);
     if ((threadIdx.x & 63) == 0) { smd[threadIdx.x >> 6] = s; smn[threadIdx.x >> 6] = n; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -375,9 +361,8 @@ const char* prep_sizes_bad(int C, int X, int Y, int Z, int Xt, int Yt, int Zt) {
     if (b >= lim || b * Zt >= lim || b * Zt * C >= lim) return "Xt*Yt*Zt*C must stay below 2^31";
     return nullptr;
 }
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-inline long long sweep_wg(long long P) { return (P + TB - 1) / TB; }                              // workgroups that would cover P in one sweep
-inline int pass_grid(long long P) { return (int)std::min<long long>(sweep_wg(P), CAP); }
+inline int sweep_wg(long long P) { return uz::sweep_grid(P, TB); }                                // workgroups that would cover P in one sweep
+inline int pass_grid(long long P) { return uz::sweep_grid(P, TB, CAP); }
 inline bool prep_wide(int C, uintptr_t raw, uintptr_t image) { return C == 4 && raw % 16 == 0 && image % 16 == 0; }
 inline Geo make_geo(int C, int X, int Y, int Z, int Xt, int Yt, int Zt) {
     Geo g;
@@ -392,7 +377,7 @@ int launch_prepare(const float* raw, const uint8_t* mask, const Geo& g, int plac
     const unsigned P = (unsigned)g.X * g.Y * g.Z, Pt = (unsigned)g.Xt * g.Yt * g.Zt;
     const int Gb = pass_grid(P), Gt = pass_grid(Pt);
     int* bsl = static_cast<int*>(workspace);
-    SumSlice* ssl = reinterpret_cast<SumSlice*>(static_cast<char*>(workspace) + up16((size_t)Gb * BSL * sizeof(int)));
+    SumSlice* ssl = reinterpret_cast<SumSlice*>(static_cast<char*>(workspace) + uz::up16((size_t)Gb * BSL * sizeof(int)));
     hipLaunchKernelGGL(prep_bounds_k<WIDE>, dim3(Gb), dim3(TB), 0, st, raw, g, P, bsl);
     if (int rc = uz::check_launch("prep_bounds_k")) return rc;
     hipLaunchKernelGGL(prep_fold_bounds_k, dim3(1), dim3(TB), 0, st, bsl, Gb, g.X, g.Y, g.Z, g.Xt, g.Yt, g.Zt, placement, info);
@@ -426,7 +411,7 @@ inline long long restore_threads(int w, long long total) { return total / w + to
 
 template <typename T, int W>
 int launch_restore(const void* rows, const int32_t* place, const Lut& lut, int has_lut, T fill, void* out, const RGeo& g, unsigned total, hipStream_t st) {
-    const int G = (int)sweep_wg(restore_threads(W, total));
+    const int G = sweep_wg(restore_threads(W, total));
     hipLaunchKernelGGL((restore_k<T, W>), dim3(G), dim3(TB), 0, st, static_cast<const T*>(rows), place, lut, has_lut, fill, static_cast<T*>(out), g, total);
     return uz::check_launch("restore_k");
 }
@@ -435,7 +420,7 @@ int launch_restore(const void* rows, const int32_t* place, const Lut& lut, int h
 
 extern "C" size_t uz_vol_prepare_workspace(int C, int X, int Y, int Z, int Xt, int Yt, int Zt) {
     if (prep_sizes_bad(C, X, Y, Z, Xt, Yt, Zt)) return 0;
-    return up16((size_t)pass_grid((long long)X * Y * Z) * BSL * sizeof(int)) + (size_t)pass_grid((long long)Xt * Yt * Zt) * sizeof(SumSlice);
+    return uz::up16((size_t)pass_grid((long long)X * Y * Z) * BSL * sizeof(int)) + (size_t)pass_grid((long long)Xt * Yt * Zt) * sizeof(SumSlice);
 }
 
 extern "C" int uz_vol_prepare_route(int C, int X, int Y, int Z, int Xt, int Yt, int Zt, int align, int* out3) {
@@ -476,7 +461,7 @@ extern "C" int uz_vol_restore_route(int elem, int N, int X, int Y, int Z, int al
     const long long total = (long long)N * X * Y * Z;
     const int w = restore_width(elem, (uintptr_t)align, total);
     out3[0] = w;
-    out3[1] = (int)sweep_wg(restore_threads(w, total));
+    out3[1] = sweep_wg(restore_threads(w, total));
     out3[2] = 0;                                                            // one sweep, always
     return 0;
 }

@@ -26,12 +26,7 @@ constexpr int WALK_BINS = WALK_T * 4;
 constexpr long long EDT_MAX_SQ = 1LL << 30;
 constexpr long long HD_MAX_SQ = UZ_VOL_HD95_MAX_SQ;
 
-struct Sets { uint32_t p[UZ_VOL_MAX_REGIONS], r[UZ_VOL_MAX_REGIONS]; };
-
-__device__ __forceinline__ bool member(const uint8_t* __restrict__ lab, size_t idx, uint32_t set) {
-    const unsigned v = lab[idx];
-    return v < 32u && ((set >> (v & 31u)) & 1u);
-}
+__device__ __forceinline__ bool member(const uint8_t* __restrict__ lab, size_t idx, uint32_t set) { return uz::in_set(lab[idx], set); }
 // border of the mask {label in set}: a voxel of the mask with a face neighbour outside the mask or outside the volume
 // (scipy.ndimage.binary_erosion, connectivity 1, border_value 0: mask ^ erosion)
 __device__ __forceinline__ bool border_at(const uint8_t* __restrict__ lab, uint32_t set, int d, int h, int w, int D, int H, int W) {
@@ -125,7 +120,7 @@ __global__ __launch_bounds__(256) void edt_axis_k(const int* __restrict__ src, i
 
 // ------------------------------------------------------------------------------------------------ counts
 // counts[n][r] = {tp, |pred|, |ref|, .}: per-thread integer counters, wave sums, one LDS sum per workgroup, then integer atomics.
-__device__ __forceinline__ void count_voxel(unsigned a, unsigned b, const Sets& s, unsigned (&tp)[UZ_VOL_MAX_REGIONS],
+__device__ __forceinline__ void count_voxel(unsigned a, unsigned b, const uz::RegionSets& s, unsigned (&tp)[UZ_VOL_MAX_REGIONS],
                                             unsigned (&cp)[UZ_VOL_MAX_REGIONS], unsigned (&cr)[UZ_VOL_MAX_REGIONS]) {
     const uint32_t ma = a < 32u ? 1u << a : 0u, mb = b < 32u ? 1u << b : 0u;
 #pragma unroll
@@ -134,12 +129,7 @@ __device__ __forceinline__ void count_voxel(unsigned a, unsigned b, const Sets& 
         tp[r] += ip & ir; cp[r] += ip; cr[r] += ir;
     }
 }
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__global__ __launch_bounds__(256) void count_k(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ ref, Sets s, int R, int P, int vec,
+__global__ __launch_bounds__(256) void count_k(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ ref, uz::RegionSets s, int R, int P, int vec,
                                                unsigned long long* __restrict__ counts) {
     __shared__ unsigned long long acc[3 * UZ_VOL_MAX_REGIONS];
     const int n = blockIdx.y;
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(256) void count_k(const uint8_t* __restrict__ pred,
     }
 #pragma unroll
     for (int r = 0; r < UZ_VOL_MAX_REGIONS; ++r) {
-        const unsigned a = wave_sum_u(tp[r]), b = wave_sum_u(cp[r]), c = wave_sum_u(cr[r]);
+        const unsigned a = uz::wave_sum(tp[r]), b = uz::wave_sum(cp[r]), c = uz::wave_sum(cr[r]);
         if ((threadIdx.x & 63) == 0) {
             atomicAdd(&acc[3 * r], (unsigned long long)a); atomicAdd(&acc[3 * r + 1], (unsigned long long)b); atomicAdd(&acc[3 * r + 2], (unsigned long long)c);
         }
@@ -239,8 +229,7 @@ __global__ __launch_bounds__(WALK_T) void walk_k(unsigned* __restrict__ hist, in
     uint4* h4 = reinterpret_cast<uint4*>(hist);
     unsigned long long mine = 0ull;
     for (int q = threadIdx.x; q < nbins_pad / 4; q += WALK_T) { const uint4 c = h4[q]; mine += (unsigned long long)c.x + c.y + c.z + c.w; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    mine = uz::wave_sum(mine);
     if ((threadIdx.x & 63) == 0) atomicAdd(&tot, mine);
     __syncthreads();
     const unsigned long long n = tot;
@@ -277,12 +266,11 @@ const char* sizes_bad(int D, int H, int W, long long max_sq) {
         return max_sq == EDT_MAX_SQ ? "D^2 + H^2 + W^2 beyond 2^30" : "D^2 + H^2 + W^2 beyond 2^22 (the HD95 histogram)";
     return nullptr;
 }
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-inline int w_grid(int D, int H) { return (int)std::min<long long>(((long long)D * H + 3) / 4, 65536); }
+inline int w_grid(int D, int H) { return uz::sweep_grid((long long)D * H, 4, 65536); }
 inline int axis_form(int L) { return L > CH ? 1 : 0; }                  // 0 the whole axis in one LDS tile, 1 chunks of CH
 inline int axis_grid(long long outer, long long inner) { return (int)(outer * ((inner + TW - 1) / TW)); }
-inline int count_grid(int P, bool vec) { return std::min(uz::ceil_div(vec ? P / 4 : P, 256), 256); }
-inline int gather_grid(int P) { return std::min(uz::ceil_div(P, 256), 2048); }
+inline int count_grid(int P, bool vec) { return uz::sweep_grid(vec ? P / 4 : P, 256, 256); }
+inline int gather_grid(int P) { return uz::sweep_grid(P, 256, 2048); }
 inline bool count_vec(int P, const void* a, const void* b) { return P % 4 == 0 && (reinterpret_cast<uintptr_t>(a) & 3) == 0 && (reinterpret_cast<uintptr_t>(b) & 3) == 0; }
 inline int hist_bins(int D, int H, int W) { return (D - 1) * (D - 1) + (H - 1) * (H - 1) + (W - 1) * (W - 1) + 1; }
 inline int hist_bins_pad(int D, int H, int W) { return uz::ceil_div(hist_bins(D, H, W), WALK_BINS) * WALK_BINS; }
@@ -305,7 +293,7 @@ int transform(const uint8_t* src, bool border, uint32_t set, int D, int H, int W
 
 extern "C" size_t uz_vol_edt_sq_workspace(int D, int H, int W) {
     if (sizes_bad(D, H, W, EDT_MAX_SQ)) return 0;
-    return up16((size_t)D * H * W * 4);
+    return uz::up16((size_t)D * H * W * 4);
 }
 
 extern "C" int uz_vol_edt_sq(const uint8_t* seeds, int D, int H, int W, int32_t* d2, void* workspace, void* stream) {
@@ -319,7 +307,7 @@ extern "C" int uz_vol_edt_sq(const uint8_t* seeds, int D, int H, int W, int32_t*
 extern "C" size_t uz_vol_region_scores_workspace(int N, int R, int D, int H, int W, int want_hd95) {
     if (N < 1 || N > UZ_VOL_MAX_ROWS || R < 1 || R > UZ_VOL_MAX_REGIONS || sizes_bad(D, H, W, want_hd95 ? HD_MAX_SQ : EDT_MAX_SQ)) return 0;
     if (!want_hd95) return 16;
-    return 3 * up16((size_t)D * H * W * 4) + (size_t)hist_bins_pad(D, H, W) * 4;
+    return 3 * uz::up16((size_t)D * H * W * 4) + (size_t)hist_bins_pad(D, H, W) * 4;
 }
 
 extern "C" int uz_vol_region_scores_route(int N, int R, int D, int H, int W, int want_hd95, int* out4) {
@@ -355,8 +343,7 @@ extern "C" int uz_vol_region_scores(const uint8_t* pred, int N, const uint32_t* 
     UZ_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 7) == 0 && (reinterpret_cast<uintptr_t>(scores) & 7) == 0, "vol_region_scores: counts and scores must be 8-byte aligned");
     hipStream_t st = uz::S(stream);
     const int P = D * H * W;
-    Sets s = {};
-    for (int r = 0; r < R; ++r) { s.p[r] = pred_sets[r]; s.r[r] = ref_sets[r]; }
+    const uz::RegionSets s = uz::region_sets(pred_sets, ref_sets, R);
 
     if (hipMemsetAsync(counts, 0, (size_t)N * R * 4 * sizeof(int64_t), st) != hipSuccess) return uz::fail("vol_region_scores: clearing counts failed");
     const bool vec = count_vec(P, pred, ref);
@@ -367,7 +354,7 @@ extern "C" int uz_vol_region_scores(const uint8_t* pred, int N, const uint32_t* 
     if (!want_hd95) return 0;
 
     char* base = static_cast<char*>(workspace);
-    const size_t vol = up16((size_t)P * 4);
+    const size_t vol = uz::up16((size_t)P * 4);
     int* t_ref = reinterpret_cast<int*>(base);
     int* t_pred = reinterpret_cast<int*>(base + vol);
     int* tmp = reinterpret_cast<int*>(base + 2 * vol);

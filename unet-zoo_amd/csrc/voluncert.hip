@@ -23,8 +23,6 @@ constexpr int CAP = 1024;           // workgroups of the table pass at the most:
 constexpr int FT = 1024;            // threads of the finish
 constexpr int MAXB = (UZ_VOL_UNC_MAX_SAMPLES + 1) * 4;       // bins of one region at the most
 
-struct Sets { uint32_t p[UZ_VOL_MAX_REGIONS], r[UZ_VOL_MAX_REGIONS]; };
-
 typedef unsigned long long u64;
 
 // the VB bytes at p as VB / 4 words (VB = 1: the byte in the low bits of one word)
@@ -106,7 +104,7 @@ __device__ __forceinline__ void step(const uint8_t* __restrict__ samples, int S,
 
 template <int VB>
 __global__ __launch_bounds__(TB) void table_k(const uint8_t* __restrict__ samples, int S, const uint8_t* __restrict__ decision,
-                                              const uint8_t* __restrict__ ref, Sets sets, int R, int P_, uint32_t* __restrict__ slices,
+                                              const uint8_t* __restrict__ ref, uz::RegionSets sets, int R, int P_, uint32_t* __restrict__ slices,
                                               uint8_t* __restrict__ votes) {
     extern __shared__ __align__(16) u64 lds[];                          // [256] lutP, [256] lutR, then R * nb uint32
     u64* lutP = lds;
@@ -141,9 +139,7 @@ __global__ __launch_bounds__(TB) void table_k(const uint8_t* __restrict__ sample
 #pragma unroll
     for (int r = 0; r < UZ_VOL_MAX_REGIONS; ++r) {
         if (r < R) {
-            unsigned v = z[r] + bg;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            const unsigned v = uz::wave_sum(z[r] + bg);
             if ((threadIdx.x & 63) == 0 && v) atomicAdd(&tab[r * nb], v);
         }
     }
@@ -240,7 +236,6 @@ const char* sizes_bad(int S, int R, int D, int H, int W) {
     if (dh >= (1LL << 31) || dh * W >= (1LL << 31) || dh * W * S >= (1LL << 31)) return "S*D*H*W must stay below 2^31";
     return nullptr;
 }
-inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 inline int bins(int S, int R) { return R * (S + 1) * 4; }
 // n rows of P bytes from address a on, every one aligned to vb bytes
 inline bool rows_aligned(uintptr_t a, int n, long long P, int vb) { return a % vb == 0 && (n == 1 || P % vb == 0); }
@@ -250,11 +245,11 @@ inline int vec_bytes(uintptr_t samples, int S, uintptr_t decision, uintptr_t ref
         if (P >= vb && rows_aligned(samples, S, P, vb) && rows_aligned(decision, 1, P, vb) && rows_aligned(ref, 1, P, vb) && (votes == 0 || rows_aligned(votes, R, P, vb))) return vb;
     return 1;
 }
-inline long long sweeps_wg(long long P, int vb) { return (std::max<long long>(P / vb, 1) + TB - 1) / TB; }       // workgroups that would cover P in one sweep
-inline int table_grid(long long P, int vb) { return (int)std::min<long long>(sweeps_wg(P, vb), CAP); }
+inline int sweeps_wg(long long P, int vb) { return uz::sweep_grid(P / vb, TB); }               // workgroups that would cover P in one sweep
+inline int table_grid(long long P, int vb) { return uz::sweep_grid(P / vb, TB, CAP); }
 
 template <int VB>
-int launch_table(const uint8_t* samples, int S, const uint8_t* decision, const uint8_t* ref, const Sets& s, int R, int P, int G, uint32_t* slices,
+int launch_table(const uint8_t* samples, int S, const uint8_t* decision, const uint8_t* ref, const uz::RegionSets& s, int R, int P, int G, uint32_t* slices,
                  uint8_t* votes, hipStream_t st) {
     const size_t lds = 512 * sizeof(u64) + (size_t)bins(S, R) * sizeof(uint32_t);
     hipLaunchKernelGGL(table_k<VB>, dim3(G), dim3(TB), lds, st, samples, S, decision, ref, s, R, P, slices, votes);
@@ -265,7 +260,7 @@ int launch_table(const uint8_t* samples, int S, const uint8_t* decision, const u
 
 extern "C" size_t uz_vol_uncertainty_workspace(int S, int R, int D, int H, int W) {
     if (sizes_bad(S, R, D, H, W)) return 0;
-    return up16((size_t)table_grid((long long)D * H * W, 1) * bins(S, R) * sizeof(uint32_t));       // the scalar form's grid is the largest
+    return uz::up16((size_t)table_grid((long long)D * H * W, 1) * bins(S, R) * sizeof(uint32_t));       // the scalar form's grid is the largest
 }
 
 extern "C" int uz_vol_uncertainty_route(int S, int R, int D, int H, int W, int align, int* out3) {
@@ -296,8 +291,7 @@ extern "C" int uz_vol_uncertainty(const uint8_t* samples, int S, const uint8_t* 
                "vol_uncertainty: table, levels, curves, auc and calibration must be 8-byte aligned");
     hipStream_t st = uz::S(stream);
     const int P = D * H * W;
-    Sets s = {};
-    for (int r = 0; r < R; ++r) { s.p[r] = pred_sets[r]; s.r[r] = ref_sets[r]; }
+    const uz::RegionSets s = uz::region_sets(pred_sets, ref_sets, R);
     const int vb = vec_bytes(reinterpret_cast<uintptr_t>(samples), S, reinterpret_cast<uintptr_t>(decision), reinterpret_cast<uintptr_t>(ref),
                              reinterpret_cast<uintptr_t>(votes), R, P);
     const int G = table_grid(P, vb);                                     // <= the scalar form's grid, which sized the workspace

@@ -17,12 +17,11 @@ Quirks kept: the reference reads the flip switches as ``do_fliplr`` / ``do_flipu
 is called but its result discarded (:117-118), i.e. a no-op.  Not built: ``do_elasticaug`` (no experiment file enables it) and
 ``resize_to`` (UZH only) raise NotImplementedError.
 """
-import ctypes as C
 
 import numpy as np
 import torch
 
-from .. import _ffi
+from .. import _ffi, _vol
 
 
 def draw_augmentation(n_images, shape, options):
@@ -130,9 +129,8 @@ class BatchProvider:
         x = torch.empty(B, 1, H, W, device=self.device)
         s = torch.empty(B, H, W, device=self.device)
         nl = int(self.augmentation_options.get("nlabels", 0) or max(2, int(yd.max()) + 1 if not self.do_augmentations else 2))
-        st = torch.cuda.current_stream(self.device).cuda_stream
         _ffi.check(_ffi.lib().uz_augment_batch(Xd.data_ptr(), yd.data_ptr(), H, W, A, tab.data_ptr(), tab.data_ptr() + 4 * B,
-                                               pd.data_ptr(), B, nl, x.data_ptr(), s.data_ptr(), C.c_void_p(st)), "augment_batch")
+                                               pd.data_ptr(), B, nl, x.data_ptr(), s.data_ptr(), _vol.stream(self.device)), "augment_batch")
         return (x if self.add_dummy_dimension else x[:, 0]), s
 
     # ------------------------------------------------------------------ reference API

@@ -20,13 +20,12 @@ Not built: ``NN_AUGMENTATION = False`` - the soft and hard one-hot label schemes
 raises NotImplementedError.  Quirk kept: the intensity
 shift is hard-coded to four channels (augmentation.py:83), so with fewer the reference raises and so does this.
 """
-import ctypes as C
 import random
 
 import numpy as np
 import torch
 
-from .. import _ffi
+from .. import _ffi, _vol
 
 NPRM = 34       # UZ_AUG3_NPRM (include/uz_api.h)
 
@@ -144,10 +143,9 @@ class BratsDataset(torch.utils.data.Dataset):
         Xc, Yc, Zc = self.randomCrop if self.randomCrop is not None else (X, Y, Z)
         x = torch.empty(Cn, Xc, Yc, Zc, device=self.device)
         y = torch.empty(3, Xc, Yc, Zc, device=self.device) if self.hasMasks else None
-        st = torch.cuda.current_stream(self.device).cuda_stream
         _ffi.check(_ffi.lib().uz_augment_volume(img[index].data_ptr(), lbl[index].data_ptr() if self.hasMasks else None, Cn, X, Y, Z,
                                                 prm.ctypes.data, Xc, Yc, Zc, ws.data_ptr(), x.data_ptr(),
-                                                y.data_ptr() if self.hasMasks else None, None, C.c_void_p(st)), "augment_volume")
+                                                y.data_ptr() if self.hasMasks else None, None, _vol.stream(self.device)), "augment_volume")
         return self._item(index, x, y)
 
     def _item(self, index, x, y):

@@ -19,15 +19,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .. import _ffi
+from .. import _ffi, _vol
 
 PLACEMENTS = {"centre": 0, "center": 0, "corner": 1}
-
-_prepare_ws = {}                                    # workspace per (device, C, X, Y, Z, Xt, Yt, Zt): every call runs on the caller's current stream
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 class PreparedCase(collections.namedtuple("PreparedCase", "image mask info stats")):
@@ -112,8 +106,7 @@ def prepare_case(raw, mask=None, size=(160, 192, 160), placement="centre", pixel
     L = _ffi.lib()
     nbytes = L.uz_vol_prepare_workspace(Cn, X, Y, Z, Xt, Yt, Zt)
     if nbytes == 0:
-        raise _ffi.UzError(f"prepare_case: sizes refused (raw {X} x {Y} x {Z} x {Cn} into {Xt} x {Yt} x {Zt}; no empty axis, 1 <= C <= 8, "
-                           "X*Y*Z*C < 2^31, Xt*Yt*Zt*C < 2^31)")
+        raise _vol.refused("prepare_case", f"raw {X} x {Y} x {Z} x {Cn} into {Xt} x {Yt} x {Zt}; no empty axis, 1 <= C <= 8, X*Y*Z*C < 2^31, Xt*Yt*Zt*C < 2^31")
     if out is None:
         image = torch.empty(Xt, Yt, Zt, Cn, device=dev)
         mask_out = torch.empty(Xt, Yt, Zt, dtype=torch.uint8, device=dev) if mask is not None else None
@@ -127,16 +120,12 @@ def prepare_case(raw, mask=None, size=(160, 192, 160), placement="centre", pixel
         if mask_out is not None and (mask_out.dtype != torch.uint8 or tuple(mask_out.shape) != (Xt, Yt, Zt) or not mask_out.is_contiguous()
                                      or mask_out.device != dev):
             raise ValueError(f"out[1] must be a dense uint8 ({Xt}, {Yt}, {Zt}) tensor on {dev}")
-    key = (dev, Cn, X, Y, Z, Xt, Yt, Zt)
-    ws = _prepare_ws.get(key)
-    if ws is None:
-        _prepare_ws.clear()                          # one shape at a time: a split's cases share one
-        ws = _prepare_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _vol.workspace("prepare_case", (dev, Cn, X, Y, Z, Xt, Yt, Zt), nbytes, dev)          # a split's cases share one
     info = torch.empty(16, dtype=torch.int32, device=dev)
     stats = torch.empty(Cn, 3, dtype=torch.float64, device=dev)
     _ffi.check(L.uz_vol_prepare(raw.data_ptr(), mask.data_ptr() if mask is not None else None, Cn, X, Y, Z, Xt, Yt, Zt, PLACEMENTS[placement],
                                 ws.data_ptr(), image.data_ptr(), mask_out.data_ptr() if mask_out is not None else None, info.data_ptr(),
-                                stats.data_ptr(), _stream(raw)), "vol_prepare")
+                                stats.data_ptr(), _vol.stream(raw.device)), "vol_prepare")
     return PreparedCase(image=image, mask=mask_out, info=info, stats=stats)
 
 
@@ -209,7 +198,7 @@ def _restore_rows(rows, place, native, lut, fill):
     else:
         f = C.c_float(float(fill))
     _ffi.check(_ffi.lib().uz_vol_restore(rows.data_ptr(), elem, N, Xt, Yt, Zt, place.data_ptr(), lut_arg, C.addressof(f), out.data_ptr(), X, Y, Z,
-                                         _stream(rows)), "vol_restore")
+                                         _vol.stream(rows.device)), "vol_restore")
     return out
 
 
@@ -224,15 +213,10 @@ def restore_volume(x, place, native_shape=(240, 240, 155), lut=None, fill=0):
     native = tuple(int(v) for v in native_shape)
     if len(native) != 3 or any(v < 1 for v in native):
         raise ValueError(f"native_shape {native} is not three positive extents")
-    if hasattr(x, "labels") and hasattr(x, "mean_label"):
-        labels, mean_label, entropy = x.labels, x.mean_label, x.entropy
-        if labels.dtype != torch.uint8 or mean_label.dtype != torch.uint8:
-            raise TypeError("Prediction.labels and Prediction.mean_label must be uint8")
-        if labels.dim() != 5 or int(labels.shape[1]) != 1 or tuple(mean_label.shape) != tuple(labels.shape[1:]):
-            raise ValueError(f"Prediction of one volume expected: labels (S, 1, D, H, W) and mean_label (1, D, H, W), got {tuple(labels.shape)} and {tuple(mean_label.shape)}")
-        if not labels.is_cuda:
-            raise ValueError(f"x must be on the device, not on {labels.device}")
-        rows = torch.cat([labels[:, 0], mean_label], 0)
+    if _vol.is_prediction(x):
+        (labels, mean_label), entropy = _vol.prediction_maps(x), x.entropy
+        _vol.on_device(labels, "x")
+        rows = _vol.prediction_rows(labels, mean_label)
         pl = _place_tensor(place, tuple(rows.shape[1:]), native, rows.device)
         out = _restore_rows(rows, pl, native, lut, fill)
         S = int(labels.shape[0])
@@ -244,8 +228,7 @@ def restore_volume(x, place, native_shape=(240, 240, 155), lut=None, fill=0):
         raise TypeError("x must be a Prediction or a uint8 / fp32 tensor (N, Xt, Yt, Zt) or (Xt, Yt, Zt)")
     if x.dim() not in (3, 4):
         raise ValueError(f"x {tuple(x.shape)} is not (N, Xt, Yt, Zt) or (Xt, Yt, Zt)")
-    if not x.is_cuda:
-        raise ValueError(f"x must be on the device, not on {x.device}")
+    _vol.on_device(x, "x")
     rows = x if x.dim() == 4 else x[None]
     out = _restore_rows(rows, _place_tensor(place, tuple(rows.shape[1:]), native, rows.device), native, lut, fill)
     return out if x.dim() == 4 else out[0]

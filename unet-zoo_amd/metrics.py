@@ -10,11 +10,7 @@ import ctypes as C
 
 import torch
 
-from . import _ffi
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
+from . import _ffi, _vol
 
 
 def pair_counts(a, b, label):
@@ -23,7 +19,7 @@ def pair_counts(a, b, label):
     b8 = b.reshape(b.shape[0], -1).to(torch.uint8).contiguous()
     out = torch.empty(a8.shape[0], b8.shape[0], 3, dtype=torch.int32, device=a.device)
     _ffi.check(_ffi.lib().uz_label_pair_counts(a8.data_ptr(), a8.shape[0], b8.data_ptr(), b8.shape[0], a8.shape[1], int(label),
-                                               out.data_ptr(), _stream(a)), "label_pair_counts")
+                                               out.data_ptr(), _vol.stream(a.device)), "label_pair_counts")
     return out
 
 
@@ -59,8 +55,8 @@ def variance_ncc_dist(sample_arr, gt_arr):
     esy = torch.empty(M, H * W, device=s.device)
     out = torch.empty(M, device=s.device)
     L = _ffi.lib()
-    _ffi.check(L.uz_ncc_maps(s.data_ptr(), g.data_ptr(), N, M, K, H * W, ess.data_ptr(), esy.data_ptr(), _stream(s)), "ncc_maps")
-    _ffi.check(L.uz_ncc(ess.data_ptr(), esy.data_ptr(), M, H * W, out.data_ptr(), _stream(s)), "ncc")
+    _ffi.check(L.uz_ncc_maps(s.data_ptr(), g.data_ptr(), N, M, K, H * W, ess.data_ptr(), esy.data_ptr(), _vol.stream(s.device)), "ncc_maps")
+    _ffi.check(L.uz_ncc(ess.data_ptr(), esy.data_ptr(), M, H * W, out.data_ptr(), _vol.stream(s.device)), "ncc")
     return float(out.double().mean())
 
 
@@ -116,7 +112,7 @@ def score_prediction(pred, annotations, return_counts=False):
     L, dev = _ffi.lib(), labels.device
     nbytes = L.uz_score_workspace(B, S, A, K, P)
     if nbytes == 0:
-        raise _ffi.UzError(f"score_prediction: sizes refused (B {B} S {S} A {A} K {K} P {P}; 2 <= K <= 8, every element count within int32)")
+        raise _vol.refused("score_prediction", f"B {B} S {S} A {A} K {K} P {P}; 2 <= K <= 8, every element count within int32")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)                # (the caching allocator hands out 512-byte aligned blocks)
     packed = torch.empty(2 * B + B * A * K, dtype=torch.float64, device=dev)
     ged, ncc, dice = packed[:B], packed[B:2 * B], packed[2 * B:].view(B, A, K)
@@ -125,7 +121,7 @@ def score_prediction(pred, annotations, return_counts=False):
     _ffi.check(L.uz_score_samples(labels.data_ptr(), ann.data_ptr(), mean_label.data_ptr(), soft.data_ptr() if soft is not None else None,
                                   B, S, A, K, P, ws.data_ptr(), counts.data_ptr() if return_counts else None, ged.data_ptr(),
                                   ncc_pairs.data_ptr() if soft is not None else None, ncc.data_ptr() if soft is not None else None,
-                                  dice.data_ptr(), _stream(labels)), "score_samples")
+                                  dice.data_ptr(), _vol.stream(labels.device)), "score_samples")
     return Scores(ged=ged, dice=dice, ncc=ncc if soft is not None else None, ncc_pairs=ncc_pairs, counts=counts, packed=packed)
 
 
@@ -138,21 +134,6 @@ VolumeScores = collections.namedtuple("VolumeScores", "dice sensitivity specific
 VolumeScores.__doc__ = """What score_volume returns, all on the device: dice, sensitivity, specificity, hd95 (N, R) fp64 - views of one (N, R, 4)
 buffer - and counts (N, R, 4) int64 = {tp, |pred|, |ref|, voxels}.  hd95 is -1 where a mask is empty and NaN when it was not asked for."""
 
-_volume_ws = {}                                     # workspace per (device, N, R, D, H, W, hd95): every call runs on the caller's current stream
-
-
-def _region_sets(regions, what):
-    sets = []
-    for reg in regions:
-        m = 0
-        for v in reg:
-            v = int(v)
-            if not 0 <= v < 32:
-                raise ValueError(f"{what}: label value {v} in region {tuple(reg)} - a region is a set of values 0 .. 31")
-            m |= 1 << v
-        sets.append(m)
-    return sets
-
 
 def score_volume(pred, reference, pred_regions, ref_regions=None, hd95=True):
     """Dice, sensitivity, specificity and HD95 (bratsUtils.py:6-24,57-84) of N label volumes against ONE reference volume, for R regions
@@ -161,96 +142,48 @@ def score_volume(pred, reference, pred_regions, ref_regions=None, hd95=True):
     round trip, no synchronisation.  pred: a Prediction of PHISeg3D.predict - the rows are its S samples, then mean_label, N = S + 1 - or
     a uint8 tensor (N, D, H, W); reference: uint8 (D, H, W) on the same device, for instance the y_raw of BratsDataset.  Returns a
     VolumeScores of device tensors."""
-    if hasattr(pred, "labels") and hasattr(pred, "mean_label"):
-        labels, mean_label = pred.labels, pred.mean_label
-        if labels.dtype != torch.uint8 or mean_label.dtype != torch.uint8:
-            raise TypeError("Prediction.labels and Prediction.mean_label must be uint8")
-        if labels.dim() != 5 or int(labels.shape[1]) != 1 or tuple(mean_label.shape) != tuple(labels.shape[1:]):
-            raise ValueError(f"Prediction of one volume expected: labels (S, 1, D, H, W) and mean_label (1, D, H, W), got {tuple(labels.shape)} and {tuple(mean_label.shape)}")
-        rows = torch.cat([labels[:, 0], mean_label], 0)
+    if _vol.is_prediction(pred):
+        rows = _vol.prediction_rows(*_vol.prediction_maps(pred))
     else:
-        rows = pred
-        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8:
-            raise TypeError("pred must be a Prediction or a uint8 tensor (N, D, H, W)")
-        if rows.dim() != 4:
-            raise ValueError(f"pred {tuple(rows.shape)} is not (N, D, H, W)")
-    if not isinstance(reference, torch.Tensor) or reference.dtype != torch.uint8:
-        raise TypeError("reference must be a uint8 tensor (D, H, W)")
+        rows = _vol.label_tensor(pred, "pred", "(N, D, H, W)", 4, also="a Prediction or ")
+    _vol.label_tensor(reference, "reference", "(D, H, W)")
     if tuple(reference.shape) != tuple(rows.shape[1:]):
         raise ValueError(f"reference {tuple(reference.shape)} does not match the volumes {tuple(rows.shape[1:])} of pred")
     if reference.device != rows.device:
         raise ValueError("reference must be on the device of pred")
-    ref_regions = pred_regions if ref_regions is None else ref_regions
-    if len(ref_regions) != len(pred_regions):
-        raise ValueError(f"{len(pred_regions)} regions of pred against {len(ref_regions)} of the reference")
-    psets, rsets = _region_sets(pred_regions, "pred_regions"), _region_sets(ref_regions, "ref_regions")
+    psets, rsets = _vol.region_set_pair(pred_regions, ref_regions)
     N, D, H, W = (int(d) for d in rows.shape)
     R = len(psets)
     L, dev = _ffi.lib(), rows.device
     nbytes = L.uz_vol_region_scores_workspace(N, R, D, H, W, int(bool(hd95)))
     if nbytes == 0:
-        raise _ffi.UzError(f"score_volume: sizes refused (N {N} R {R} volume {D} x {H} x {W}; 1 <= R <= 8, D*H*W < 2^31, "
-                           "D^2 + H^2 + W^2 <= 2^22 with hd95)")
+        raise _vol.refused("score_volume", f"N {N} R {R} volume {D} x {H} x {W}; 1 <= R <= 8, D*H*W < 2^31, D^2 + H^2 + W^2 <= 2^22 with hd95")
     rows, reference = rows.contiguous(), reference.contiguous()
-    key = (dev, N, R, D, H, W, bool(hd95))
-    ws = _volume_ws.get(key)
-    if ws is None:
-        _volume_ws.clear()                           # one shape at a time: a validation loop scores volumes of one size
-        ws = _volume_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _vol.workspace("score_volume", (dev, N, R, D, H, W, bool(hd95)), nbytes, dev)
     scores = torch.empty(N, R, 4, dtype=torch.float64, device=dev)
     counts = torch.empty(N, R, 4, dtype=torch.int64, device=dev)
     U32 = C.c_uint32 * R
     _ffi.check(L.uz_vol_region_scores(rows.data_ptr(), N, U32(*psets), reference.data_ptr(), U32(*rsets), R, D, H, W, int(bool(hd95)),
-                                      ws.data_ptr(), counts.data_ptr(), scores.data_ptr(), _stream(rows)), "vol_region_scores")
+                                      ws.data_ptr(), counts.data_ptr(), scores.data_ptr(), _vol.stream(rows.device)), "vol_region_scores")
     return VolumeScores(dice=scores[..., 0], sensitivity=scores[..., 1], specificity=scores[..., 2], hd95=scores[..., 3], counts=counts)
 
 
 # --------------------------------------------------------------------------- connected components of label volumes: the clean-up between drawing and scoring
-_components_ws = {}                                 # workspace per (device, N, D, H, W), as _volume_ws
-
-
 def _components_workspace(rows, what):
     N, D, H, W = (int(d) for d in rows.shape)
     L, dev = _ffi.lib(), rows.device
     nbytes = L.uz_vol_components_workspace(N, D, H, W)
     if nbytes == 0:
-        raise _ffi.UzError(f"{what}: sizes refused (N {N} volume {D} x {H} x {W}; no empty axis, 1 <= N <= 65536, N*D*H*W < 2^31)")
-    key = (dev, N, D, H, W)
-    ws = _components_ws.get(key)
-    if ws is None:
-        _components_ws.clear()                       # one shape at a time, as score_volume
-        ws = _components_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    return ws
-
-
-def _label_rows(rows, what):
-    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8:
-        raise TypeError(f"{what} must be a uint8 tensor (N, D, H, W)")
-    if rows.dim() != 4:
-        raise ValueError(f"{what} {tuple(rows.shape)} is not (N, D, H, W)")
-    return rows
-
-
-def _on_device(rows, what):
-    if not rows.is_cuda:
-        raise ValueError(f"{what} must be on the device, not on {rows.device}")
+        raise _vol.refused(what, f"N {N} volume {D} x {H} x {W}; no empty axis, 1 <= N <= 65536, N*D*H*W < 2^31")
+    return _vol.workspace("components", (dev, N, D, H, W), nbytes, dev)              # label_components and keep_largest_components share it
 
 
 def _prediction_rows(pred):
     """(rows (N, D, H, W) uint8, is_prediction): a Prediction's samples, then its mean label, as score_volume concatenates them; a 2-D
     Prediction's (S, B, H, W) and (B, H, W) become S*B + B volumes of depth 1"""
-    if not (hasattr(pred, "labels") and hasattr(pred, "mean_label")):
-        return _label_rows(pred, "pred"), False
-    labels, mean_label = pred.labels, pred.mean_label
-    if not isinstance(labels, torch.Tensor) or not isinstance(mean_label, torch.Tensor) or labels.dtype != torch.uint8 or mean_label.dtype != torch.uint8:
-        raise TypeError("Prediction.labels and Prediction.mean_label must be uint8")
-    if labels.dim() not in (4, 5) or tuple(mean_label.shape) != tuple(labels.shape[1:]) or (labels.dim() == 5 and int(labels.shape[1]) != 1):
-        raise ValueError("Prediction expected with labels (S, 1, D, H, W) and mean_label (1, D, H, W), or labels (S, B, H, W) and mean_label (B, H, W), "
-                         f"got {tuple(labels.shape)} and {tuple(mean_label.shape)}")
-    if labels.dim() == 5:
-        return torch.cat([labels[:, 0], mean_label], 0), True
-    H, W = int(labels.shape[2]), int(labels.shape[3])
-    return torch.cat([labels.reshape(-1, 1, H, W), mean_label.reshape(-1, 1, H, W)], 0), True
+    if not _vol.is_prediction(pred):
+        return _vol.label_tensor(pred, "pred", "(N, D, H, W)", 4), False
+    return _vol.prediction_rows(*_vol.prediction_maps(pred, planar=True)), True
 
 
 def _filtered_prediction(pred, out):
@@ -268,16 +201,16 @@ def label_components(volumes, values, return_sizes=False):
     one uz_vol_label_components call (csrc/volcomp.hip) on the caller's current stream, no synchronisation.  Returns int32 labels
     (N, D, H, W): 0 on background, 1 + the smallest local index (z*H + y)*W + x of the voxel's component elsewhere - canonical, so a
     repeated call is bit-equal -, or (labels, sizes) with the voxel count of each voxel's component."""
-    rows = _label_rows(volumes, "volumes")
-    (bits,) = _region_sets((tuple(values),), "values")
-    _on_device(rows, "volumes")
+    rows = _vol.label_tensor(volumes, "volumes", "(N, D, H, W)", 4)
+    (bits,) = _vol.region_sets((tuple(values),), "values")
+    _vol.on_device(rows, "volumes")
     ws = _components_workspace(rows, "label_components")
     rows = rows.contiguous()
     labels = torch.empty(rows.shape, dtype=torch.int32, device=rows.device)
     sizes = torch.empty(rows.shape, dtype=torch.int32, device=rows.device) if return_sizes else None
     N, D, H, W = (int(d) for d in rows.shape)
     _ffi.check(_ffi.lib().uz_vol_label_components(rows.data_ptr(), N, D, H, W, bits, labels.data_ptr(), sizes.data_ptr() if return_sizes else None,
-                                                  ws.data_ptr(), _stream(rows)), "vol_label_components")
+                                                  ws.data_ptr(), _vol.stream(rows.device)), "vol_label_components")
     return (labels, sizes) if return_sizes else labels
 
 
@@ -295,7 +228,7 @@ def keep_largest_components(pred, regions=((1,), (2,), (3,)), min_voxels=None, u
     entropy describe the UNFILTERED draw.  The result goes into score_volume as it is."""
     if unlisted not in ("zero", "keep"):
         raise ValueError(f"unlisted must be 'zero' or 'keep', not {unlisted!r}")
-    sets = _region_sets(regions, "regions")
+    sets = _vol.region_sets(regions, "regions")
     R = len(sets)
     if min_voxels is None:
         mv = [0] * R
@@ -309,14 +242,14 @@ def keep_largest_components(pred, regions=((1,), (2,), (3,)), min_voxels=None, u
         raise ValueError(f"min_voxels {tuple(mv)}: a threshold is a voxel count >= 0")
     rows, is_pred = _prediction_rows(pred)
     if R < 1 or R > 8:
-        raise _ffi.UzError(f"keep_largest_components: sizes refused ({R} regions; 1 <= R <= 8)")
-    _on_device(rows, "pred")
+        raise _vol.refused("keep_largest_components", f"{R} regions; 1 <= R <= 8")
+    _vol.on_device(rows, "pred")
     ws = _components_workspace(rows, "keep_largest_components")
     rows = rows.contiguous()
     out = torch.empty_like(rows)
     N, D, H, W = (int(d) for d in rows.shape)
     _ffi.check(_ffi.lib().uz_vol_keep_components(rows.data_ptr(), N, D, H, W, (C.c_uint32 * R)(*sets), (C.c_int32 * R)(*mv), R, int(unlisted == "keep"),
-                                                 out.data_ptr(), ws.data_ptr(), _stream(rows)), "vol_keep_components")
+                                                 out.data_ptr(), ws.data_ptr(), _vol.stream(rows.device)), "vol_keep_components")
     if not is_pred:
         return out
     return _filtered_prediction(pred, out)
@@ -330,8 +263,6 @@ decision; dice, ftp, ftn (R, S+1) fp64 - views of one (R, S+1, 3) buffer -: the 
 true negatives at level j; auc (R, 4) fp64 = {auc_dice, auc_ftp, auc_ftn, score}, score the BraTS uncertainty-task score; calibration (R, 3)
 fp64 = {ece, mce, brier} of the vote frequencies c / S; votes (R, D, H, W) uint8 = c, or None when it was not asked for."""
 
-_uncertainty_ws = {}                                # workspace per (device, S, R, D, H, W), as _volume_ws
-
 
 def score_uncertainty(pred, reference, pred_regions, ref_regions=None, decision=None, return_votes=False):
     """Judges S samples of ONE volume as an uncertainty estimate against `reference`, for R regions given as in score_volume - one
@@ -342,27 +273,18 @@ def score_uncertainty(pred, reference, pred_regions, ref_regions=None, decision=
     keep_largest_components returns it; or a uint8 tensor (S, D, H, W), and then `decision` is required.  decision: uint8 (D, H, W)
     or (1, D, H, W), overrides the decision volume (for instance the filtered mean label while the samples stay unfiltered).
     reference: uint8 (D, H, W) on the same device.  Returns an UncertaintyScores of device tensors."""
-    if hasattr(pred, "labels") and hasattr(pred, "mean_label"):
-        labels, mean_label = pred.labels, pred.mean_label
-        if not isinstance(labels, torch.Tensor) or not isinstance(mean_label, torch.Tensor) or labels.dtype != torch.uint8 or mean_label.dtype != torch.uint8:
-            raise TypeError("Prediction.labels and Prediction.mean_label must be uint8")
-        if labels.dim() != 5 or int(labels.shape[1]) != 1 or tuple(mean_label.shape) != tuple(labels.shape[1:]):
-            raise ValueError(f"Prediction of one volume expected: labels (S, 1, D, H, W) and mean_label (1, D, H, W), got {tuple(labels.shape)} and {tuple(mean_label.shape)}")
+    if _vol.is_prediction(pred):
+        labels, mean_label = _vol.prediction_maps(pred)
         samples = labels[:, 0]
         dec = mean_label[0] if decision is None else decision
     else:
-        samples = pred
-        if not isinstance(samples, torch.Tensor) or samples.dtype != torch.uint8:
-            raise TypeError("pred must be a Prediction or a uint8 tensor (S, D, H, W)")
-        if samples.dim() != 4:
-            raise ValueError(f"pred {tuple(samples.shape)} is not (S, D, H, W)")
+        samples = _vol.label_tensor(pred, "pred", "(S, D, H, W)", 4, also="a Prediction or ")
         if decision is None:
             raise ValueError("decision is required when pred is a tensor of samples: the volume the samples are judged against")
         dec = decision
     vol = tuple(samples.shape[1:])
-    for t, what in ((dec, "decision"), (reference, "reference")):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-            raise TypeError(f"{what} must be a uint8 tensor (D, H, W)")
+    _vol.label_tensor(dec, "decision", "(D, H, W)")
+    _vol.label_tensor(reference, "reference", "(D, H, W)")
     if dec.dim() == 4 and int(dec.shape[0]) == 1:
         dec = dec[0]
     if tuple(dec.shape) != vol:
@@ -371,23 +293,16 @@ def score_uncertainty(pred, reference, pred_regions, ref_regions=None, decision=
         raise ValueError(f"reference {tuple(reference.shape)} does not match the volumes {vol} of pred")
     if reference.device != samples.device or dec.device != samples.device:
         raise ValueError("reference and decision must be on the device of pred")
-    ref_regions = pred_regions if ref_regions is None else ref_regions
-    if len(ref_regions) != len(pred_regions):
-        raise ValueError(f"{len(pred_regions)} regions of pred against {len(ref_regions)} of the reference")
-    psets, rsets = _region_sets(pred_regions, "pred_regions"), _region_sets(ref_regions, "ref_regions")
-    _on_device(samples, "pred")
+    psets, rsets = _vol.region_set_pair(pred_regions, ref_regions)
+    _vol.on_device(samples, "pred")
     S, D, H, W = (int(d) for d in samples.shape)
     R = len(psets)
     L, dev = _ffi.lib(), samples.device
     nbytes = L.uz_vol_uncertainty_workspace(S, R, D, H, W)
     if nbytes == 0:
-        raise _ffi.UzError(f"score_uncertainty: sizes refused (S {S} R {R} volume {D} x {H} x {W}; 1 <= S <= 255, 1 <= R <= 8, no empty axis, S*D*H*W < 2^31)")
+        raise _vol.refused("score_uncertainty", f"S {S} R {R} volume {D} x {H} x {W}; 1 <= S <= 255, 1 <= R <= 8, no empty axis, S*D*H*W < 2^31")
     samples, dec, reference = samples.contiguous(), dec.contiguous(), reference.contiguous()
-    key = (dev, S, R, D, H, W)
-    ws = _uncertainty_ws.get(key)
-    if ws is None:
-        _uncertainty_ws.clear()                      # one shape at a time, as score_volume
-        ws = _uncertainty_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _vol.workspace("score_uncertainty", (dev, S, R, D, H, W), nbytes, dev)
     table = torch.empty(R, S + 1, 2, 2, dtype=torch.int64, device=dev)
     levels = torch.empty(R, S + 1, 4, dtype=torch.int64, device=dev)
     curves = torch.empty(R, S + 1, 3, dtype=torch.float64, device=dev)
@@ -397,6 +312,6 @@ def score_uncertainty(pred, reference, pred_regions, ref_regions=None, decision=
     U32 = C.c_uint32 * R
     _ffi.check(L.uz_vol_uncertainty(samples.data_ptr(), S, dec.data_ptr(), U32(*psets), reference.data_ptr(), U32(*rsets), R, D, H, W,
                                     ws.data_ptr(), table.data_ptr(), levels.data_ptr(), curves.data_ptr(), auc.data_ptr(), calibration.data_ptr(),
-                                    votes.data_ptr() if return_votes else None, _stream(samples)), "vol_uncertainty")
+                                    votes.data_ptr() if return_votes else None, _vol.stream(samples.device)), "vol_uncertainty")
     return UncertaintyScores(table=table, levels=levels, dice=curves[..., 0], ftp=curves[..., 1], ftn=curves[..., 2], auc=auc,
                              calibration=calibration, votes=votes)
