@@ -5,9 +5,14 @@ argument (tests/test_tape_dispatch_cpu.py); tape.hip's own functions are strong 
 import ctypes as C
 import importlib.util
 import os
+import sys
+import types
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_spec = importlib.util.spec_from_file_location("_ffi", os.path.join(os.path.dirname(_HERE), "unet-zoo_amd", "_ffi.py"))
+# the binding alone, without importing the package (torch): a bare parent module whose path lets _ffi find its one sibling, _knobs
+_PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "unet-zoo_amd")
+sys.modules["_uz"] = types.ModuleType("_uz")
+sys.modules["_uz"].__path__ = [_PKG]
+_spec = importlib.util.spec_from_file_location("_uz._ffi", os.path.join(_PKG, "_ffi.py"))
 _ffi = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(_ffi)
 

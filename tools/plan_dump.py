@@ -24,6 +24,11 @@ import time
 NF7 = [32, 64, 128, 192, 192, 192, 192]
 KNOBS = {"UZ_FOLD_BN_BWD": "1", "UZ_BN_FOLD_DGRAD": "0", "UZ_PACK_DY": "0", "UZ_PACK_ACT": "0", "UZ_BN_OFFCHAIN": "1",
          "UZ_FOLD_RELU_BWD": "0", "UZ_WGRAD_TABLE": "0", "UZ_DBIAS_TABLE": "0", "UZ_CHAIN": "0"}       # each flipped from its default
+# (UZ_CHAIN=0 is the default spelled out - phiseg7@chain8192 is the configuration that turns it on; UZ_FOLD_RELU_BWD bites on unet only)
+FLIPS = {"phiseg7": {"UZ_PREPACK": "0", "UZ_BN_FUSE_STATS": "0", "UZ_BN_FOLD_REDUCE": "0", "UZ_PACK_OWN_GROUP": "0", "UZ_WGRAD_TABLE_CHUNK": "8",
+                     "UZ_DECOUPLE_WGRAD": "0", "UZ_DECOUPLE_PREFIX": "", "UZ_SCHED_COST": "alone", "UZ_SCHED_HEAVY": "r4", "UZ_FUSE_HEADS": "0"},
+         "phiseg3d_mid": {"UZ_WGRAD_TABLE_VOL": "0", "UZ_BN_FUSE_STATS_VOL": "0"},
+         "phiseg7@chain8192": {"UZ_CHAIN_BWD": "0", "UZ_CHAIN_WGS": "128", "UZ_CHAIN_WGS_BWD": "40", "UZ_CHAIN_NETS": "fwd"}}
 
 
 def golden_meta(root, name):
@@ -93,6 +98,10 @@ def configurations(root):
             add(f"{m}@{k}={v}", m, env={k: v})
         add(f"phiseg3d_mid@math3+b16@{k}={v}", "phiseg3d_mid", env={"UZ_STORE_B16": "1", k: v}, mode=3)
     add("phiseg7@chain8192", "phiseg7", env={"UZ_CHAIN": "8192"})
+    # the remaining plan switches, each away from its default on a model where that changes the plan (name: <base configuration>@<switch>=<value>)
+    for base, flips in FLIPS.items():
+        for k, v in flips.items():
+            add(f"{base}@{k}={v}", base.split("@")[0], env={**dict(out)[base]["env"], k: v})
     add("phiseg_small@heads_unfused", "phiseg_small", env={"UZ_FUSE_HEADS": "0"})
     add("phiseg_small@lanes3+resched", "phiseg_small", env={"UZ_LANES": "3", "UZ_SCHED_HEAVY": "off", "UZ_SCHED_COST": "beside"}, resched=True)
     add("phiseg7@resched", "phiseg7", resched=True)

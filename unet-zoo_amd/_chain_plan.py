@@ -3,7 +3,6 @@ ops of a tape into persistent UZ_OP_CHAIN launches (_chain_pass, the last of the
 tables of such a launch (_chain_tables, built when Plan._resolve first meets a "chaintab" ref) and its status query.  Functions of the plan.
 """
 import ctypes as C
-import os
 
 import torch
 
@@ -16,7 +15,7 @@ def _chain_limit(plan):
     """Largest N*H*W whose ops run inside the persistent chain launch (0: off).  Only with two-piece operands (the chain's
     convolutions are split-fp16: UZ_CONV_MATH=f32 keeps every convolution on the fp32 matrix pipe, bf16 is the volume path) and
     training-mode BatchNorm."""
-    px = int(os.environ.get("UZ_CHAIN", str(plan.chain_px)))
+    px = plan.knobs.chain_px
     if px <= 0 or not plan.bn_training or plan.L.uz_get_conv_math() in (0, 3) or plan.extra_ops:
         return 0
     return px
@@ -105,10 +104,9 @@ def _chain_pass(plan):
     px = _chain_limit(plan)
     if px <= 0:
         return
-    only = os.environ.get("UZ_CHAIN_NETS")                # diagnostics: "fwd,prior" = the forward chain and the prior's backward chain only
-    only = None if only is None else set(only.split(","))
+    only = plan.knobs.chain_nets                          # diagnostics: "fwd,prior" = the forward chain and the prior's backward chain only
     jobs = [("fwd", plan.fwd_ops, _chain_eligible_fwd, None)] if (only is None or "fwd" in only) else []
-    if plan.bwd_ops and os.environ.get("UZ_CHAIN_BWD", "1") == "1":
+    if plan.bwd_ops and plan.knobs.chain_bwd:
         nets = []
         for o in plan.bwd_ops:
             if _chain_eligible_bwd(o, px):
@@ -224,7 +222,7 @@ def _chain_build(plan, which, ops, elig, net, px):
     for k in sorted(Es):
         level[k] = 1 + max((level[d] for d in deps[k] if d in Es), default=-1)
     imgs = plan._chain_imgs.setdefault(which, {})
-    G = int(os.environ.get("UZ_CHAIN_WGS" if fwd else "UZ_CHAIN_WGS_BWD", str(plan.chain_wgs if fwd else plan.chain_wgs_bwd)))
+    G = plan.knobs.chain_wgs if fwd else plan.knobs.chain_wgs_bwd
     sub, flops = [], 0.0
 
     def emit(k, code, p, i, f=(), lvl=None):

@@ -12,7 +12,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _ffi
+from . import _ffi, _knobs
 from ._modtree import attach
 from ._plan import ParamTable, Plan
 
@@ -159,9 +159,7 @@ class NativeModel(nn.Module):
     # step started 1.3 ms late); host-issued lanes start every op when ITS predecessors are done: PHiSeg 17.2 -> 16.3 ms with three
     # lanes, Probabilistic U-Net 3 107 -> 3 240 images/s, U-Net / PHiSeg3D unchanged.  (More than four concurrently active hardware
     # queues collapse the step to 27 ms: lanes <= 4, GPU_MAX_HW_QUEUES >= lanes.)
-    replay_mode = os.environ.get("UZ_REPLAY", "lanes")
-    if replay_mode not in ("lanes", "graph"):          # (any other value used to select the hipGraph path silently: ADVICE r5)
-        raise ValueError(f"UZ_REPLAY={replay_mode!r}: the replay mode is 'lanes' (host-issued lane replay) or 'graph' (hipGraph)")
+    replay_mode = _knobs.get("UZ_REPLAY")              # (ValueError for any other value: it used to select the hipGraph path silently)
     default_lanes_by_mode = {}  # per-model override of default_lanes for a replay mode, e.g. {"lanes": 3}
     # Planes (N*H*W pixels) up to which a layer's weight gradient becomes a scheduling group of its own (Plan._decouple_wgrad;
     # UZ_DECOUPLE_WGRAD overrides).  Measured A/B on one MI355X: PHiSeg 19.49 -> 19.26 ms with 8192 (the deep levels' backward
@@ -185,17 +183,16 @@ class NativeModel(nn.Module):
 
     def _new_plan(self, N, bn_training):
         self._set_library_mode()
-        plan = Plan(N, self._ptab, bn_training, self.device)
-        if "UZ_LANES" not in os.environ:
-            plan.n_lanes = self.default_lanes_by_mode.get(self.replay_mode, self.default_lanes)
-        # the scheduler's "one device-filling group at a time" rule pays in the graph replay only
-        plan.sched_heavy = os.environ.get("UZ_SCHED_HEAVY", "off" if self.replay_mode == "lanes" else "r4")
-        # the lane replay is scheduled with durations as it realises them beside other lanes' kernels (Plan._op_cost_beside), and
-        # tune_schedule() refines them by measurement; the graph replay keeps the isolated-launch model its rule was measured with
-        plan.sched_cost = os.environ.get("UZ_SCHED_COST", "beside" if self.replay_mode == "lanes" else "alone")
-        plan.decouple_wgrad_px = self.decouple_wgrad_px
-        plan.chain_px = self.chain_px
-        plan.decouple_wgrad_prefixes = tuple(self.decouple_wgrad_prefixes)
+        lanes = self.replay_mode == "lanes"
+        knobs = _knobs.read(defaults=dict(
+            lanes=self.default_lanes_by_mode.get(self.replay_mode, self.default_lanes),
+            # the scheduler's "one device-filling group at a time" rule pays in the graph replay only
+            sched_heavy="off" if lanes else "r4",
+            # the lane replay is scheduled with durations as it realises them beside other lanes' kernels (Plan._op_cost_beside), and
+            # tune_schedule() refines them by measurement; the graph replay keeps the isolated-launch model its rule was measured with
+            sched_cost="beside" if lanes else "alone",
+            decouple_wgrad_px=self.decouple_wgrad_px, decouple_wgrad_prefixes=tuple(self.decouple_wgrad_prefixes), chain_px=self.chain_px))
+        plan = Plan(N, self._ptab, bn_training, self.device, knobs)
         dp = self._dp
         if dp is not None and dp.overlap:
             plan.grad_buckets = list(dp.buckets)
@@ -204,7 +201,7 @@ class NativeModel(nn.Module):
         extra = 1 if (dp is not None and dp.overlap) else 0
         if plan.n_lanes + extra > 4:
             import warnings
-            if "UZ_LANES" in os.environ:
+            if "lanes" in knobs.from_env:
                 warnings.warn(f"UZ_LANES={plan.n_lanes} with {extra} communication stream(s): more than four concurrently active streams - "
                               "measured to collapse the step (16 -> 27 ms on MI355X)", RuntimeWarning)
             else:
@@ -213,7 +210,7 @@ class NativeModel(nn.Module):
             hwq = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
         except ValueError:
             hwq = 4
-        if self.replay_mode == "lanes" and plan.n_lanes > 1 and hwq < plan.n_lanes and not self._warned_hwq:
+        if lanes and plan.n_lanes > 1 and hwq < plan.n_lanes and not self._warned_hwq:
             import warnings
             self._warned_hwq = True
             warnings.warn(f"GPU_MAX_HW_QUEUES={hwq} < {plan.n_lanes} dependency lanes: lanes share hardware queues and serialise "
@@ -367,7 +364,7 @@ class NativeModel(nn.Module):
                     best[(pid, which)] = (wall, used, plan)
                 if r == rounds:
                     continue
-                cmodel = Plan._op_cost_beside if os.environ.get("UZ_SCHED_COST", plan.sched_cost) == "beside" else Plan._op_cost
+                cmodel = Plan._op_cost_beside if plan.sched_cost == "beside" else Plan._op_cost
                 last, dur = {}, [0.0] * len(ops)
                 for e in runs:
                     last.clear()

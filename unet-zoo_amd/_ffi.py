@@ -11,9 +11,11 @@ import ctypes as C
 import os
 import re
 
+from . import _knobs
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # UZ_LIB: an experiment build of the same library (csrc/Makefile VARIANT=...); never a different implementation
-LIB_PATH = os.environ.get("UZ_LIB") or os.path.join(_HERE, "libuz_hip.so")
+LIB_PATH = _knobs.get("UZ_LIB") or os.path.join(_HERE, "libuz_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "uz_api.h")
 TABLE_PATH = os.path.join(os.path.dirname(_HERE), "include", "uz_ops.def")      # the tape encoding (included by the header)
 

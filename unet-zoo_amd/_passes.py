@@ -3,8 +3,6 @@ apply pass off the forward chain (_bn_offchain_pass, off by default), bf16 stora
 deep-level chain, is _chain_plan.py.  Each is a function of the plan: it reads the ops the emitters left (Plan._units, Plan._vol_units,
 the tapes), rewrites them in place and leaves a summary dict on the plan (round4, bn_offchain, b16_info).
 """
-import os
-
 from . import _chain_plan, _ops
 from ._ops import conv_dims
 from ._plan import View, _ScratchView, _buf_of
@@ -41,7 +39,7 @@ def _split_storage_passes(plan):
     """Plan-time rewrites on the Conv2D units (torchlayers.py:18-21) of the large planes, all decided from the emitted ops:
       1. folded backward reduction - where the ONLY writer of a unit's dA is an unsplit split-path data gradient, that launch masks
          dA with the unit's ReLU and leaves the BatchNorm-backward sums in its epilogue; the unit's backward runs a per-channel
-         finalise instead of the reduction pass over dA and y (UZ_FOLD_BN_BWD=0 switches it off);
+         finalise instead of the reduction pass over dA and y (off unless UZ_FOLD_BN_BWD=1);
       2. dY in split storage - where both consumers of a unit's dy (its weight and data gradient) run on the split path, the
          BatchNorm-backward apply pass writes the operand pieces instead of fp32 values (UZ_PACK_DY=0);
       3. activations in split storage - a buffer written only by BatchNorm-apply / pooling / interpolation launches that know
@@ -53,14 +51,14 @@ def _split_storage_passes(plan):
     units = [u for u in plan._units if "bn_bwd" in u or "bn_fwd" in u]
     if plan.L.uz_get_conv_math() in (0, 3) or not plan.bn_training:
         return info                              # fp32-only / bf16 modes have no two-piece operands
-    env = lambda k: os.environ.get(k, "1") == "1"
+    knobs = plan.knobs
     large = lambda u: u["N"] * u["H"] * u["W"] > 4096 and (u["H"] * u["W"]) % 4 == 0
     tabbed = {id(q.buf) for t in plan.ptr_tables for q in t if isinstance(q, View)}
     # ---- 1. folded backward reduction
     # (off by default: measured on MI355X the epilogue's extra read of y is exposed - the 64-channel-tile kernel keeps ONE
     #  workgroup per CU, so its memory phase overlaps nothing: data gradient of 128 -> 128 @ 128 x 128 451 -> 573 us against
     #  269 -> 170 us for the unit's BatchNorm backward; step +-0)
-    if os.environ.get("UZ_FOLD_BN_BWD", "0") == "1" and plan.bwd_ops:
+    if knobs.fold_bn_bwd and plan.bwd_ops:
         for u in units:
             if not large(u) or u["npart"] <= 0:
                 continue
@@ -83,7 +81,7 @@ def _split_storage_passes(plan):
     # launch leaves its partial sums in a buffer of the layer's own and the unit's one-workgroup-per-channel backward adds them
     # itself - one reduction launch less on the backward chains of the 8 x 8 ... 2 x 2 levels (UZ_BN_FOLD_DGRAD=0 switches it off)
     info["dgrad_folded"] = 0
-    if env("UZ_BN_FOLD_DGRAD") and plan.bwd_ops:
+    if knobs.bn_fold_dgrad and plan.bwd_ops:
         for u in units:
             if u["N"] * u["H"] * u["W"] > 4096:
                 continue
@@ -99,7 +97,7 @@ def _split_storage_passes(plan):
             u["bn_bwd"].set(p={"da_partials": slabs}, i={"nslab": parts})
             info["dgrad_folded"] += 1
     # ---- 2. dY in split storage
-    if env("UZ_PACK_DY") and plan.bwd_ops:
+    if knobs.pack_dy and plan.bwd_ops:
         for u in units:
             B, wg, dg = u.get("bn_bwd"), u.get("wgrad"), u.get("dgrad")
             if B is None or wg is None or not large(u) or u["ks"] != 3 or u["W"] % 4:
@@ -115,7 +113,7 @@ def _split_storage_passes(plan):
                     o.set(i={"dy_packed": 1})
             info["dy_packed"] += 1
     # ---- 3. activations in split storage
-    if env("UZ_PACK_ACT") and not plan.extra_ops:
+    if knobs.pack_act and not plan.extra_ops:
         named = {id(v.buf) for v in plan.named.values() if isinstance(v, View)}
         for b in plan.bufs:
             if b.alias is not None or id(b) in tabbed or id(b) in named or (b.H * b.W) % 4 or b.N * b.H * b.W <= max(4096, _chain_plan._chain_limit(plan)):
@@ -187,7 +185,7 @@ def _bn_offchain_pass(plan):
     statistics launch only; the apply pass still writes the activation for the weight gradient, beside the chain instead of in it."""
     info = dict(units=0)
     plan.bn_offchain = info
-    if os.environ.get("UZ_BN_OFFCHAIN", "0") != "1" or plan.L.uz_get_conv_math() in (0, 3) or not plan.bn_training or plan.extra_ops:
+    if not plan.knobs.bn_offchain or plan.L.uz_get_conv_math() in (0, 3) or not plan.bn_training or plan.extra_ops:
         return info
     ops = plan.fwd_ops
     for u in [u for u in plan._units if "bn_fwd" in u]:
@@ -273,7 +271,7 @@ def _b16_pass(plan):
     latent and loss tensors, the image) stays fp32.  A unit's dy moves to a bf16 twin of the zero-bordered scratch class when
     its three backward ops all qualify.  Returns / keeps a summary in plan.b16_info."""
     info = plan.b16_info = dict(buffers=0, grads=0, dy=0, bytes_saved=0, ops=0)
-    on = os.environ.get("UZ_STORE_B16", "0") == "1"
+    on = plan.knobs.store_b16
     if not on or plan.L.uz_get_conv_math() != 3 or not plan.bn_training or plan.extra_ops:
         return info
     all_ops = [o for ops in (plan.fwd_ops, plan.loss_ops, plan.bwd_ops) for o in ops]

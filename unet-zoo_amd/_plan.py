@@ -20,13 +20,12 @@ tapes lives beside it: ``_passes.py`` (split storage, BatchNorm off-chain, bf16 
 chain, off by default) and ``_sched.py`` (hazard analysis, cost models, the lane scheduler).
 """
 import ctypes as C
-import os
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
-from . import _ffi, _ops, _sched
+from . import _ffi, _knobs, _ops, _sched
 from ._ops import conv_dims
 
 BN_EPS = 1e-3        # reference torchlayers.py:20
@@ -168,8 +167,10 @@ class Latent:
 
 # ----------------------------------------------------------------------------------------------
 class Plan:
-    def __init__(self, N, ptab, bn_training, device):
+    def __init__(self, N, ptab, bn_training, device, knobs=None):
         self.N, self.ptab, self.bn_training, self.device = int(N), ptab, bool(bn_training), device
+        # the UZ_* switches this plan is built AND rescheduled under: NativeModel._new_plan reads them over the model's defaults, a bare Plan over the table's
+        self.knobs = knobs if knobs is not None else _knobs.read()
         self.codes = _ffi.op_codes()
         self.L = _ffi.lib()
         self.bufs = []
@@ -198,14 +199,9 @@ class Plan:
         self.events = []                    # hipEvent_t handles (uz_event_create), one per gradient bucket
         self._gid = 0                       # scheduling group of the ops being emitted (see _sched.schedule)
         self._gyz = {}                       # zero-bordered dy scratch classes of volume units: (slices, floats per slice) -> floats
-        self.n_lanes = max(1, min(int(os.environ.get("UZ_LANES", "2")), 8))
-        self.decouple_wgrad_px = 0           # NativeModel.decouple_wgrad_px: planes (N*H*W) up to which weight gradients get a group of their own
-        self.decouple_wgrad_prefixes = ()    # NativeModel.decouple_wgrad_prefixes
+        self.n_lanes = max(1, min(self.knobs.lanes, 8))      # (NativeModel._new_plan lowers it to the stream budget)
         self._nclaims = {}                   # backward writers seen per buffer (conv_relu's folded ReLU backward checks it was the last one)
         self._dbias_jobs = []                # folded ReLU backward: bias gradients still to be summed from their partials (one launch at the tape's end)
-        self.chain_px = 0                    # NativeModel.chain_px: planes (N*H*W) up to which a tape's ops run as phases of ONE persistent launch (_chain_plan._chain_pass)
-        self.chain_wgs = 256                 # workgroups of that launch (forward tape: nothing else runs beside it)
-        self.chain_wgs_bwd = 80              # ... of a backward chain (it runs beside the other lanes' device-filling kernels; at most three chains at once)
         self._chains = []                    # per chain op: dict(sub=[...], phases=[...]) -> device tables built on first resolve
         self._chain_imgs = {}                # tape -> {wkey: dict(off, bytes, mc, kc, cin, dgrad)} packed weight images of the chain convolutions
         self._chain_imgbuf = {}
@@ -217,8 +213,7 @@ class Plan:
         self._rev_ctx = None                 # branch of the reversible block being emitted (_rev_block), else None
         self._vol_depth = None               # depth of the volume a reversible sequence works on (rev_sequence, _rev_block): shapes _pool's scratch
         self._rev_pool, self._rev_slots = {}, {}   # pooled scratch of the reversible blocks and the arena regions it shares (_pool; laid out by finalize)
-        self.sched_cost = "alone"            # cost model of the lane scheduler (NativeModel._new_plan; UZ_SCHED_COST overrides): "alone" | "beside"
-        self.sched_heavy = "r4"              # its device-filling rule (NativeModel._new_plan; UZ_SCHED_HEAVY overrides): "r4" | "off" | microseconds
+        self.sched_cost = self.knobs.sched_cost   # cost model of the lane scheduler, "alone" | "beside" (its device-filling rule: knobs.sched_heavy)
         self.dag = {}                        # id(tape) -> the scheduled DAG, for diagnostics (_schedule)
         self.round4, self.bn_offchain, self.b16_info = {}, {}, {}   # summaries of _passes._split_storage_passes / _bn_offchain_pass / _b16_pass
         self.chain_info = {}                 # tape -> summaries of its chains (_chain_plan._chain_pass)
@@ -355,7 +350,7 @@ class Plan:
         """Deferred table-driven reductions (weight-gradient slabs, bias-gradient rows).  Data parallel: a bucket's gradients must be
         final when its all-reduce starts, so there the tables are cut per BUCKET (finalize(): one launch per bucket, and the bucket's
         "final" marker depends on it through the gradient ranges it writes); UZ_DP_TABLES=0 restores one reduction launch per layer."""
-        return not self.grad_buckets or os.environ.get("UZ_DP_TABLES", "1") == "1"
+        return not self.grad_buckets or self.knobs.dp_tables
 
     def _by_bucket(self, jobs, key_of):
         """jobs split by the gradient bucket their parameter lies in (one group when there are no buckets), emission order kept."""
@@ -433,7 +428,7 @@ class Plan:
             # uz_conv_bwd_weight's slab reduction does the [co][kd][ci] -> [co][ci][kd] permutation on the way out)
             # (slab reductions deferred to the table launch like the 2-D layers': the table row carries the window's C)
             nslab = 0
-            if self._tables_ok() and os.environ.get("UZ_WGRAD_TABLE", "1") == "1" and os.environ.get("UZ_WGRAD_TABLE_VOL", "1") == "1" \
+            if self._tables_ok() and self.knobs.wgrad_table and self.knobs.wgrad_table_vol \
                     and self._rev_ctx is None:
                 nslab = self.L.uz_conv_bwd_weight_slabs(3 * cin, cout, x.N, x.H, x.W, 3)
             slabbuf = self.vec(wkey + ":wslabs", nslab * 9 * cout * 3 * cin) if nslab else None
@@ -467,7 +462,7 @@ class Plan:
             # 3 x 3 layer leaves its partial-sum slabs in a buffer of its own and ONE table-driven launch at the end of the tape adds
             # the slabs of every layer (UZ_OP_WGRAD_REDUCE_TABLE) - PHiSeg: 106 + 27 small reduction launches less per step
             nslab = 0
-            if ks == 3 and db_key is None and wrow0 == 0 and self._tables_ok() and os.environ.get("UZ_WGRAD_TABLE", "1") == "1" \
+            if ks == 3 and db_key is None and wrow0 == 0 and self._tables_ok() and self.knobs.wgrad_table \
                     and self._rev_ctx is None:
                 nslab = self.L.uz_conv_bwd_weight_slabs(cin, cout, x.N, x.H, x.W, ks)
             slabbuf = self.vec(wkey + ":wslabs", nslab * ks * ks * cout * cin) if nslab else None
@@ -494,7 +489,7 @@ class Plan:
             # uses grad(x) in place as its dy instead of running uz_relu_bwd over it (conv_relu.bwd checks "last writer")
             fold = None
             st = (x.buf.relu or {}).get((x.c0, x.C)) if x.nb is None else None
-            if st is not None and ks == 3 and wrow0 == 0 and os.environ.get("UZ_FOLD_RELU_BWD", "1") == "1":
+            if st is not None and ks == 3 and wrow0 == 0 and self.knobs.fold_relu_bwd:
                 npart = self.L.uz_conv_bwd_relu_partials(cin, cout, x.N, x.H, x.W, ks)
                 if npart > 0:
                     fold = st["fold"] = dict(part=self.vec(x.buf.name + f":dbpart{x.c0}", 4 * cin * npart), npart=npart,
@@ -514,7 +509,7 @@ class Plan:
         # a Conv3d runs as a 2-D convolution whose contraction side has 3 C channels (the depth window): the image is packed
         # straight from the [Cout][Cin][3][3][3] parameter (no permutation pass)
         gcin, gcout = (cin, 3 * cout) if (vol and dgrad) else ((3 * cin, cout) if vol else (cin, cout))
-        if os.environ.get("UZ_PREPACK", "1") != "1" or self.L.uz_conv_route(1 if dgrad else 0, gcin, gcout, x.N, x.H, x.W, 3) != 1:
+        if not self.knobs.prepack or self.L.uz_conv_route(1 if dgrad else 0, gcin, gcout, x.N, x.H, x.W, 3) != 1:
             return None
         if not dgrad and self.target is not self.fwd_ops and self.target is not self.bwd_ops:
             return None                                        # extra (decode) tapes: the call packs its own image
@@ -556,10 +551,7 @@ class Plan:
         data gradient of layer L - 1 (PHiSeg's likelihood: +1 %; its posterior / prior nets: -0.5 ... -1 %, they already pair up)."""
         if x.nb is not None or ks != 3 or self.n_lanes <= 1:
             return False
-        lim = int(os.environ.get("UZ_DECOUPLE_WGRAD", str(self.decouple_wgrad_px)))
-        pref = os.environ.get("UZ_DECOUPLE_PREFIX")
-        pref = tuple(q for q in pref.split(",") if q) if pref is not None else tuple(self.decouple_wgrad_prefixes)
-        return x.N * x.H * x.W <= lim or any(name.startswith(q) for q in pref)
+        return x.N * x.H * x.W <= self.knobs.decouple_wgrad_px or any(name.startswith(q) for q in self.knobs.decouple_wgrad_prefixes)
 
     def _gy_scratch(self, like):
         self.scratch["gy"] = max(self.scratch["gy"], like.N * like.C * like.H * like.W)
@@ -585,8 +577,8 @@ class Plan:
         npart = 0
         # (not where the BatchNorm forward is ONE launch that forms the statistics from the channel's batch in registers anyway:
         #  the small path, and the mid path up to uz_bn_fwd_fused_limit)
-        if self.bn_training and os.environ.get("UZ_BN_FUSE_STATS", "1") == "1" and x.N * x.H * x.W > self.L.uz_bn_fwd_fused_limit(x.H, x.W) and \
-                (x.nb is None or (ks == 3 and os.environ.get("UZ_BN_FUSE_STATS_VOL", "1") == "1")):
+        if self.bn_training and self.knobs.bn_fuse_stats and x.N * x.H * x.W > self.L.uz_bn_fwd_fused_limit(x.H, x.W) and \
+                (x.nb is None or (ks == 3 and self.knobs.bn_fuse_stats_vol)):
             # (a volume's Conv3d is the 2-D kernel over its slices with the depth window as 3 Cin input channels: same epilogue)
             npart = self.L.uz_conv_bn_partials(x.C if x.nb is None else 3 * x.C, cout, x.N, x.H, x.W, ks)
         bnpart = self.vec(name + ":bnpart", 4 * cout * npart) if npart else None
@@ -594,7 +586,7 @@ class Plan:
         # chains): the convolution stops after its main kernel and the one-workgroup-per-channel BatchNorm adds the slabs itself -
         # one launch and one pass over y less per unit, bit-identical values (include/uz_api.h: uz_conv_fwd_slabs)
         nslab = 0
-        if x.nb is None and x.N * x.H * x.W <= 4096 and os.environ.get("UZ_BN_FOLD_REDUCE", "1") == "1":
+        if x.nb is None and x.N * x.H * x.W <= 4096 and self.knobs.bn_fold_reduce:
             nslab = self.L.uz_conv_splitk_parts(x.C, cout, x.N, x.H, x.W, ks)
             nslab = nslab if nslab > 1 else 0
         self._conv_fwd(x, wkey, bkey, y, ks, 0, bn_partials=bnpart, slabs_only=nslab > 0)
@@ -638,7 +630,7 @@ class Plan:
             # conv-bias gradient (the sum of dy: analytically zero behind a training-mode BatchNorm, the reference returns its
             # rounding noise and so do we): outside data-parallel runs the large-plane units leave their per-workgroup sums in rows of
             # their own and ONE table-driven launch at the end of the tape adds them - a summation launch less in every unit's chain
-            dbrows = self.L.uz_bn_bwd_dbias_rows(x.N, x.H, x.W) if (plain and self._tables_ok() and os.environ.get("UZ_DBIAS_TABLE", "1") == "1") else 0
+            dbrows = self.L.uz_bn_bwd_dbias_rows(x.N, x.H, x.W) if (plain and self._tables_ok() and self.knobs.dbias_table) else 0
             dbpart = self.vec(name + ":dbrows", 2 * dbrows * cout) if dbrows else None
             op_bwd = self._emit(self.bwd_ops, "UZ_OP_BN_RELU_BWD",
                                 p=[ga, y, self.P(gam), self.P(bet), save, gy, self.G(gam), self.G(bet), dbpart if dbrows else self.G(bkey), ("scratch", "bn"),
@@ -817,7 +809,7 @@ class Plan:
                 if self._nclaims.get(a.buf, 0) != fold["claims"]:
                     raise RuntimeError(f"{prefix}: a later writer of grad({a.buf.name}) follows the data gradient that folded the ReLU "
                                        "backward - set UZ_FOLD_RELU_BWD=0 for this model")
-                if not self._tables_ok() or os.environ.get("UZ_DBIAS_TABLE", "1") != "1":
+                if not self._tables_ok() or not self.knobs.dbias_table:
                     self._emit(self.bwd_ops, "UZ_OP_CHAN_SUM_PARTIALS", p=[fold["part"], self.G(bkey)], i=[fold["npart"], cout, fold.get("dbl", 0)])
                 else:
                     self._dbias_jobs.append((fold["part"], bkey, fold["npart"], cout, fold.get("dbl", 0)))
@@ -869,7 +861,7 @@ class Plan:
             # (the third unit of every vanilla U-Net block): fold that unit's ReLU backward in, like _conv_bwd does
             fold = None
             st = (x.buf.relu or {}).get((x.c0, x.C)) if x.nb is None else None
-            if st is not None and bcode in ("UZ_OP_AVGPOOL_BWD", "UZ_OP_BILINEAR_BWD") and os.environ.get("UZ_FOLD_RELU_BWD", "1") == "1":
+            if st is not None and bcode in ("UZ_OP_AVGPOOL_BWD", "UZ_OP_BILINEAR_BWD") and self.knobs.fold_relu_bwd:
                 rows = self.L.uz_resample_bwd_relu_rows(0 if bcode == "UZ_OP_AVGPOOL_BWD" else 1, x.C, x.N, x.H, x.W)
                 fold = st["fold"] = dict(part=self.vec(x.buf.name + f":dbpart{x.c0}", 2 * rows * x.C), npart=rows, dbl=1,
                                          amax=self.amax_out(self.gview(x)), claims=self._nclaims[x.buf])
@@ -1013,7 +1005,7 @@ class Plan:
         separate ops (UZ_FUSE_HEADS=0 keeps those).  Returns the Latent like latent()."""
         wm, bm, wsg, bsg = mu_prefix + ".weight", mu_prefix + ".bias", sigma_prefix + ".weight", sigma_prefix + ".bias"
         L, cin = self.ptab.shape[wm][0], h.C
-        fuse = (os.environ.get("UZ_FUSE_HEADS", "1") == "1" and h.nb is None and self.ptab.shape[wm][2:] == (1, 1) and self.ptab.shape[wsg] == self.ptab.shape[wm]
+        fuse = (self.knobs.fuse_heads and h.nb is None and self.ptab.shape[wm][2:] == (1, 1) and self.ptab.shape[wsg] == self.ptab.shape[wm]
                 and len(self.ptab.shape[wm]) == 4 and bool(self.L.uz_latent_heads_ok(cin, L)))
         if not fuse:
             mu = self.conv_bare(h, mu_prefix)
@@ -1151,8 +1143,7 @@ class Plan:
                 # that is ready as soon as ITS layers' slabs are written - measured: 1 789 / 1 790 / 1 793 / 1 791 images/s for one table /
                 # chunks of 16 / 8 / 32 layers, three alternations; with the chunks PRIORITISED in the lane scheduler - started the moment their layers are done - 1 820 -> 1 795 / 1 782 for chunks
                 # of 16 / 8: they delay the critical chains.  The single launch behind the tape stays.)
-                chunk = int(os.environ.get("UZ_WGRAD_TABLE_CHUNK", "0"))
-                chunk = len(jobs) if chunk <= 0 else chunk
+                chunk = self.knobs.wgrad_table_chunk if self.knobs.wgrad_table_chunk > 0 else len(jobs)
                 parts = self._by_bucket(jobs, lambda j: j[1]) if self.grad_buckets else [jobs[j0:j0 + chunk] for j0 in range(0, len(jobs), chunk)]
                 for part in parts:
                     refs, blk = [], 0
@@ -1205,9 +1196,8 @@ class Plan:
             self._packbuf[which] = self.vec("packed_weights:" + which, off // 4)
             # a scheduling group of its own (gid head - 1) behind the bound measurement: only the layers that READ the packed images wait for
             # it - the first layers of both encoders (1 / 3 input channels: fp32 matrix path) start beside it (40 us off the forward's chain)
-            own = os.environ.get("UZ_PACK_OWN_GROUP", "1") == "1"
             pack_ops[which] = _ops.make("UZ_OP_PACK_WEIGHTS", p=[self.ptr_table(refs), ("amaxw", 0), self._packbuf[which]], i=[len(lst), rows],
-                                        gid=head - 1 if own else head)
+                                        gid=head - 1 if self.knobs.pack_own_group else head)
         if "bwd" in pack_ops and self.bwd_ops:
             self.bwd_ops[:0] = [pack_ops["bwd"]]
         if self.fwd_ops:
@@ -1456,10 +1446,8 @@ class Plan:
         return _sched.hazard_deps([self._access(o) for o in ops])
 
     def _schedule(self, ops):
-        """Lane schedule of tape `ops` (_sched.schedule: REORDERS `ops` in place); the environment overrides the plan's two settings."""
-        cost_model = os.environ.get("UZ_SCHED_COST", self.sched_cost)
-        heavy_mode = os.environ.get("UZ_SCHED_HEAVY", self.sched_heavy)
-        sched, self.dag[id(ops)] = _sched.schedule(ops, self._access, self.n_lanes, cost_model, heavy_mode)
+        """Lane schedule of tape `ops` (_sched.schedule: REORDERS `ops` in place), under the switches the plan was built with."""
+        sched, self.dag[id(ops)] = _sched.schedule(ops, self._access, self.n_lanes, self.sched_cost, self.knobs.sched_heavy)
         return sched
 
     # ------------------------------------------------------------------ execution helpers

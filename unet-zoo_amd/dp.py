@@ -17,6 +17,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import _knobs
+
 
 def init_from_env(backend=None):
     """Initialise the default process group from RANK / WORLD_SIZE / MASTER_* (torchrun contract).
@@ -124,7 +126,7 @@ def param_buckets(ptab, target_floats=None):
     finalises them, in the order of the scheduled tape (GradSync.order).  A ring all-reduce below a few MB is latency, not
     bandwidth: slices are not cut finer than that, and a short tail is merged into its neighbour."""
     if target_floats is None:
-        target_floats = int(float(os.environ.get("UZ_DP_BUCKET_MB", "12")) * (1 << 20) / 4)
+        target_floats = int(_knobs.get("UZ_DP_BUCKET_MB") * (1 << 20) / 4)
     out, lo, acc = [], 0, 0
     end = 0
     for key, off in ptab.poff.items():
@@ -164,7 +166,7 @@ class GradSync:
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
         if backend is None:
-            backend = os.environ.get("UZ_DP_BACKEND") or \
+            backend = _knobs.get("UZ_DP_BACKEND") or \
                 ("rccl" if (dist.is_initialized() and dist.get_backend(group) == "nccl") else "torch")
         if backend not in ("rccl", "torch"):
             raise ValueError(f"GradSync backend {backend!r}: expected 'rccl' or 'torch'")
@@ -191,7 +193,7 @@ class GradSync:
         check(L.uz_comm_init(self.rank, self.world, uid, C.byref(h)), "comm_init")
         self.comm = h.value
         s = C.c_void_p()
-        check(L.uz_stream_create(C.byref(s), int(os.environ.get("UZ_DP_STREAM_PRIORITY", "1"))), "stream_create")
+        check(L.uz_stream_create(C.byref(s), _knobs.get("UZ_DP_STREAM_PRIORITY")), "stream_create")
         self.stream = s.value
         ev = []
         for timing in (0, 1, 1) + (1,) * len(self.buckets):

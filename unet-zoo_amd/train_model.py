@@ -25,7 +25,7 @@ import types
 import numpy as np
 import torch
 
-from . import dp
+from . import _knobs, dp
 from .optim import FusedAdam
 from .synthetic import synthetic_batch
 
@@ -183,13 +183,13 @@ class UNetModel:
         self.optimizer = FusedAdam(self.net, lr=1e-3, weight_decay=1e-5)
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, "min", min_lr=1e-4, patience=50000)
         if self.world > 1:
-            self.net.set_data_parallel(True, backend="rccl" if torch.cuda.is_available() and os.environ.get("UZ_DP_BACKEND", "rccl") == "rccl" else "torch")
+            self.net.set_data_parallel(True, backend="rccl" if torch.cuda.is_available() and _knobs.get("UZ_DP_BACKEND") in (None, "rccl") else "torch")
             self.net._dp.broadcast_params()
         # static shapes: replay the tapes' dependency DAGs on the engine's lanes (NativeModel.enable_graphs; bit-identical to the
         # one-stream tape) and, once the plan exists, let the engine measure its own schedule (tune_schedule; UZ_TUNE_SCHEDULE rounds, 0 = off)
-        if torch.cuda.is_available() and hasattr(self.net, "enable_graphs") and os.environ.get("UZ_TRAIN_REPLAY", "1") != "0":
+        if torch.cuda.is_available() and hasattr(self.net, "enable_graphs") and _knobs.get("UZ_TRAIN_REPLAY") != "0":
             self.net.enable_graphs(True)
-        self._tune_rounds = int(os.environ.get("UZ_TUNE_SCHEDULE", "8"))
+        self._tune_rounds = _knobs.get("UZ_TUNE_SCHEDULE")
         self.log_root = log_root
         self.tot_loss = self.kl_loss = self.reconstruction_loss = 0
         self.iteration = 0
@@ -471,7 +471,7 @@ def resolve_sys_config(local, data_root=None, preproc_folder=None, log_root=None
                 setattr(cfg, k, v)
     for attr, val, env in (("data_root", data_root, "UZ_DATA_ROOT"), ("preproc_folder", preproc_folder, "UZ_PREPROC_FOLDER"),
                            ("log_root", log_root, "UZ_LOG_ROOT")):
-        val = val or os.environ.get(env)
+        val = val or _knobs.get(env)
         if val:
             setattr(cfg, attr, val)
     if cfg.data_root and not cfg.preproc_folder:
