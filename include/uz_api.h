@@ -803,7 +803,8 @@ int    uz_vol_region_scores_route(int N, int R, int D, int H, int W, int want_hd
  * reference runs skimage.measure.label(connectivity=1) per label 1, 2, 3 on the host, keeps the blob with the largest area
  * (np.argmax over regionprops, in label order) and zeroes everything else.  Here N volumes (N, D, H, W) uint8, dense, W fastest, go
  * through one call.  Everything is integer and exact; no float atomics, so a repeated call is bit-equal.
- *   Connectivity: face neighbours only, 6 in 3-D and 4 when D == 1 (skimage connectivity=1, scipy's default structure).  Volumes never
+ *   Connectivity: face neighbours, 6 in 3-D and 4 when D == 1 (skimage connectivity=1, scipy's default structure), in the two calls
+ *   below; the _ex calls further down take 18 and 26 neighbours as well.  Volumes never
  *   connect to each other, rows never across the row end, slices never across the slice end.
  *   A SET is a bit mask of label values 0 .. 31, as uz_vol_region_scores takes regions: a voxel is foreground of set m when bit `label`
  *   of m is 1; a value of 32 or more is in no set.
@@ -827,13 +828,47 @@ int    uz_vol_region_scores_route(int N, int R, int D, int H, int W, int want_hd
  * the reason, nothing written): a null pointer (sizes excepted), an empty axis, the limits, a negative min_voxels, a workspace off
  * 16 bytes, labels or sizes off 4, out overlapping vol.  uz_vol_components_workspace returns 0 for sizes it refuses.
  * uz_vol_components_route (host only, like uz_vol_region_scores_route) answers from the predicates the launches use: out2[0] = the
- * form (always 0: there is one), out2[1] = workgroups of the widest launch of a call.                                            */
+ * form (always 0: there is one), out2[1] = workgroups of the widest launch of a call.
+ *
+ * The _ex calls and uz_vol_fill_holes: wider neighbourhoods, relabelling, hole filling.  Same volumes, sets, workspace bytes and limits.
+ *   `connectivity` is 1, 2 or 3, as skimage's `connectivity` and scipy's generate_binary_structure(3, c) define it: two voxels of one
+ *   volume are neighbours when every coordinate differs by at most 1 and at most `connectivity` coordinates differ - 6, 18 or 26
+ *   neighbours, and with D == 1 there is no z neighbour, so 4, 8 and 8.  Volumes never join; a neighbour outside 0 <= z < D,
+ *   0 <= y < H, 0 <= x < W does not exist and is never read.  The labelling stays canonical (1 + the smallest local index) and the
+ *   union-find the same: at connectivity >= 2 the merge pass looks, from every foreground voxel, at the rows (z, y-1) and (z-1, y) at
+ *   x-1, x, x+1 and at the rows (z-1, y-1) and (z-1, y+1) at x (connectivity 2) or at x-1, x, x+1 (connectivity 3); the first voxel of a
+ *   run whose window touches a run of the other row unites the two, and a window that touches two runs unites both.
+ * uz_vol_label_components_ex: uz_vol_label_components at `connectivity`; with connectivity 1 the same output.
+ * uz_vol_keep_components_ex: uz_vol_keep_components at `connectivity`, with relabel[r] in HOST memory: -1, a voxel that set r removes
+ * becomes 0, or a value v in 0 .. 255, it becomes v.  The sets run in order and every set sees the unfiltered input; a set that keeps
+ * a voxel writes nothing, and the last set that removes a voxel decides its value; nothing is labelled a second time, so a value
+ * written by relabelling is never itself filtered.  With connectivity 1 and relabel all -1 the output of uz_vol_keep_components.
+ * uz_vol_fill_holes, R sets with fill_values[r] and max_voxels[r] >= 0 in HOST memory.  The COMPLEMENT of set r is every voxel whose
+ * label is not in the set (a value of 32 or more is in it); it is labelled like a set, at `connectivity` - here the BACKGROUND's, as
+ * the `structure` of scipy.ndimage.binary_fill_holes is, whose default is 1.  A component of the complement is a HOLE when none of its
+ * voxels lies on the volume's border: the six faces for D > 1; for D == 1, an image, the rows y = 0 and y = H-1 and the columns x = 0
+ * and x = W-1 only (else an image could have no hole).  out = vol everywhere except in the holes of set r with max_voxels[r] == 0 or
+ * with at most max_voxels[r] voxels, which become fill_values[r], a member of set r.  Every set sees vol, not the earlier sets'
+ * output, and a later set overwrites an earlier one: with the regions listed from outer to inner the inner region's value wins.
+ * out may not overlap vol.  A root is marked as reaching the border by an integer OR into bit 31 of its size word (sizes stay below
+ * 2^31): idempotent, so the result does not depend on the order of arrival.  No third volume: the workspace is the same.
+ * Refused before any launch, nothing written, uz_last_error beginning with the function's name: what the calls above refuse, a
+ * connectivity outside 1 .. 3, relabel[r] outside -1 .. 255, a fill value that is no member of its set, a negative max_voxels.
+ * uz_vol_components_route_ex (host only): out2[0] = the merge instance the launches of a call at `connectivity` take (1, 2 or 3),
+ * out2[1] = workgroups of the widest launch, as uz_vol_components_route.                                                        */
 size_t uz_vol_components_workspace(int N, int D, int H, int W);
 int    uz_vol_label_components(const uint8_t* vol, int N, int D, int H, int W, uint32_t set,
                                int32_t* labels, int32_t* sizes, void* workspace, void* stream);
 int    uz_vol_keep_components(const uint8_t* vol, int N, int D, int H, int W, const uint32_t* sets, const int32_t* min_voxels, int R,
                               int keep_unlisted, uint8_t* out, void* workspace, void* stream);
 int    uz_vol_components_route(int N, int D, int H, int W, int* out2);
+int    uz_vol_label_components_ex(const uint8_t* vol, int N, int D, int H, int W, uint32_t set, int connectivity,
+                                  int32_t* labels, int32_t* sizes, void* workspace, void* stream);
+int    uz_vol_keep_components_ex(const uint8_t* vol, int N, int D, int H, int W, const uint32_t* sets, const int32_t* min_voxels,
+                                 const int32_t* relabel, int R, int connectivity, int keep_unlisted, uint8_t* out, void* workspace, void* stream);
+int    uz_vol_fill_holes(const uint8_t* vol, int N, int D, int H, int W, const uint32_t* sets, const int32_t* fill_values,
+                         const int32_t* max_voxels, int R, int connectivity, uint8_t* out, void* workspace, void* stream);
+int    uz_vol_components_route_ex(int N, int D, int H, int W, int connectivity, int* out2);
 
 /* ---------------------------------------------------------------- volume uncertainty (the BraTS uncertainty task; calibration)
  * Judges S sampled label volumes of ONE case as an uncertainty estimate against one reference, per region, from the votes of the

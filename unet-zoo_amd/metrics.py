@@ -196,11 +196,33 @@ def _filtered_prediction(pred, out):
     return type(pred)(**fields)
 
 
-def label_components(volumes, values, return_sizes=False):
-    """Face-connected components (6 neighbours, 4 when D == 1) of {label in values} in N label volumes, uint8 (N, D, H, W) on the device -
-    one uz_vol_label_components call (csrc/volcomp.hip) on the caller's current stream, no synchronisation.  Returns int32 labels
-    (N, D, H, W): 0 on background, 1 + the smallest local index (z*H + y)*W + x of the voxel's component elsewhere - canonical, so a
-    repeated call is bit-equal -, or (labels, sizes) with the voxel count of each voxel's component."""
+def _connectivity(connectivity):
+    if isinstance(connectivity, bool) or not isinstance(connectivity, int):
+        raise TypeError(f"connectivity must be the int 1, 2 or 3, not {connectivity!r}")
+    if connectivity not in (1, 2, 3):
+        raise ValueError(f"connectivity {connectivity}: 1 (faces), 2 (faces and edges) or 3 (faces, edges and corners)")
+    return connectivity
+
+
+def _per_region(value, R, what):
+    """None -> None; one int -> R of it; a sequence -> its ints, R of them"""
+    if value is None:
+        return None
+    if isinstance(value, int):
+        return [value] * R
+    out = [int(v) for v in value]
+    if len(out) != R:
+        raise ValueError(f"{len(out)} {what} for {R} regions")
+    return out
+
+
+def label_components(volumes, values, return_sizes=False, connectivity=1):
+    """Connected components of {label in values} in N label volumes, uint8 (N, D, H, W) on the device - one uz_vol_label_components
+    call (connectivity 1, faces: 6 neighbours, 4 when D == 1) or uz_vol_label_components_ex call (connectivity 2: 18, or 3: 26
+    neighbours, skimage's full connectivity; 8 when D == 1) (csrc/volcomp.hip) on the caller's current stream, no synchronisation.
+    Returns int32 labels (N, D, H, W): 0 on background, 1 + the smallest local index (z*H + y)*W + x of the voxel's component
+    elsewhere - canonical, so a repeated call is bit-equal -, or (labels, sizes) with the voxel count of each voxel's component."""
+    _connectivity(connectivity)
     rows = _vol.label_tensor(volumes, "volumes", "(N, D, H, W)", 4)
     (bits,) = _vol.region_sets((tuple(values),), "values")
     _vol.on_device(rows, "volumes")
@@ -209,12 +231,15 @@ def label_components(volumes, values, return_sizes=False):
     labels = torch.empty(rows.shape, dtype=torch.int32, device=rows.device)
     sizes = torch.empty(rows.shape, dtype=torch.int32, device=rows.device) if return_sizes else None
     N, D, H, W = (int(d) for d in rows.shape)
-    _ffi.check(_ffi.lib().uz_vol_label_components(rows.data_ptr(), N, D, H, W, bits, labels.data_ptr(), sizes.data_ptr() if return_sizes else None,
-                                                  ws.data_ptr(), _vol.stream(rows.device)), "vol_label_components")
+    tail = (labels.data_ptr(), sizes.data_ptr() if return_sizes else None, ws.data_ptr(), _vol.stream(rows.device))
+    if connectivity == 1:
+        _ffi.check(_ffi.lib().uz_vol_label_components(rows.data_ptr(), N, D, H, W, bits, *tail), "vol_label_components")
+    else:
+        _ffi.check(_ffi.lib().uz_vol_label_components_ex(rows.data_ptr(), N, D, H, W, bits, connectivity, *tail), "vol_label_components_ex")
     return (labels, sizes) if return_sizes else labels
 
 
-def keep_largest_components(pred, regions=((1,), (2,), (3,)), min_voxels=None, unlisted="zero"):
+def keep_largest_components(pred, regions=((1,), (2,), (3,)), min_voxels=None, unlisted="zero", connectivity=1, relabel=None):
     """keep_largest_connected_components (data/BratsProcessing/utils.py:228-251) on the device - one uz_vol_keep_components call
     (csrc/volcomp.hip) on the caller's current stream, no host round trip, no synchronisation.  Each region, a tuple of label values,
     is labelled on its own (the regions may be nested: ((1, 2, 3),) keeps the largest whole tumour); of a region with min_voxels 0 the
@@ -225,7 +250,12 @@ def keep_largest_components(pred, regions=((1,), (2,), (3,)), min_voxels=None, u
     pred: a uint8 tensor (N, D, H, W) -> the filtered tensor; or a Prediction - PHISeg3D's, labels (S, 1, D, H, W) and mean_label
     (1, D, H, W), or a 2-D model's, labels (S, B, H, W) and mean_label (B, H, W), run as D = 1 - whose samples and mean label go through
     ONE call -> a new Prediction with the filtered labels and mean_label.  Every other field is the same object: soft, mean_soft and
-    entropy describe the UNFILTERED draw.  The result goes into score_volume as it is."""
+    entropy describe the UNFILTERED draw.  The result goes into score_volume as it is.
+    connectivity: 1, 2 or 3 - 6, 18 or 26 neighbours (skimage's `connectivity`).  relabel: None, or one entry per region, each None
+    (a removed voxel becomes 0) or an int 0 .. 255 that a voxel removed by that region becomes; the regions run in order, all on the
+    unfiltered input, and the last region that removes a voxel decides.  The BraTS rule "a small enhancing component is necrosis":
+    keep_largest_components(pred, regions=((3,),), min_voxels=500, relabel=(1,), unlisted="keep").  With connectivity 1 and relabel
+    None the call is uz_vol_keep_components, else uz_vol_keep_components_ex."""
     if unlisted not in ("zero", "keep"):
         raise ValueError(f"unlisted must be 'zero' or 'keep', not {unlisted!r}")
     sets = _vol.region_sets(regions, "regions")
@@ -240,6 +270,18 @@ def keep_largest_components(pred, regions=((1,), (2,), (3,)), min_voxels=None, u
             raise ValueError(f"{len(mv)} min_voxels for {R} regions")
     if any(m < 0 for m in mv):
         raise ValueError(f"min_voxels {tuple(mv)}: a threshold is a voxel count >= 0")
+    _connectivity(connectivity)
+    rl = None
+    if relabel is not None:
+        rl = list(relabel)
+        if len(rl) != R:
+            raise ValueError(f"{len(rl)} relabel entries for {R} regions")
+        for v in rl:
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int)):
+                raise TypeError(f"relabel {tuple(rl)}: an entry is None or an int")
+            if v is not None and not 0 <= v <= 255:
+                raise ValueError(f"relabel {tuple(rl)}: a label value is 0 .. 255")
+        rl = [-1 if v is None else v for v in rl]
     rows, is_pred = _prediction_rows(pred)
     if R < 1 or R > 8:
         raise _vol.refused("keep_largest_components", f"{R} regions; 1 <= R <= 8")
@@ -248,8 +290,55 @@ def keep_largest_components(pred, regions=((1,), (2,), (3,)), min_voxels=None, u
     rows = rows.contiguous()
     out = torch.empty_like(rows)
     N, D, H, W = (int(d) for d in rows.shape)
-    _ffi.check(_ffi.lib().uz_vol_keep_components(rows.data_ptr(), N, D, H, W, (C.c_uint32 * R)(*sets), (C.c_int32 * R)(*mv), R, int(unlisted == "keep"),
-                                                 out.data_ptr(), ws.data_ptr(), _vol.stream(rows.device)), "vol_keep_components")
+    tail = (int(unlisted == "keep"), out.data_ptr(), ws.data_ptr(), _vol.stream(rows.device))
+    if connectivity == 1 and rl is None:
+        _ffi.check(_ffi.lib().uz_vol_keep_components(rows.data_ptr(), N, D, H, W, (C.c_uint32 * R)(*sets), (C.c_int32 * R)(*mv), R, *tail), "vol_keep_components")
+    else:
+        _ffi.check(_ffi.lib().uz_vol_keep_components_ex(rows.data_ptr(), N, D, H, W, (C.c_uint32 * R)(*sets), (C.c_int32 * R)(*mv),
+                                                        (C.c_int32 * R)(*(rl or [-1] * R)), R, connectivity, *tail), "vol_keep_components_ex")
+    if not is_pred:
+        return out
+    return _filtered_prediction(pred, out)
+
+
+def fill_holes(pred, regions=((1, 2, 3),), fill=None, max_voxels=None, connectivity=1):
+    """scipy.ndimage.binary_fill_holes per region on the device - one uz_vol_fill_holes call (csrc/volcomp.hip) on the caller's current
+    stream, no host round trip, no synchronisation.  A hole of a region, a tuple of label values, is a connected component of the
+    voxels whose label is NOT in the region that touches no face of the volume (of a 2-D map: no edge of the image); its voxels
+    become `fill` - None: the region's first value, or one int per region, a member of its region.  max_voxels: None or 0 (holes of
+    any size), one int, or one int per region: only holes of at most that many voxels are filled.  connectivity: 1, 2 or 3, the
+    BACKGROUND's, as binary_fill_holes' `structure` is (default 1: a cavity that a diagonal gap opens stays a hole).  Every region
+    sees the input; a later region overwrites an earlier one, so list nested regions from outer to inner.
+    pred: what keep_largest_components takes, and the same kind of thing comes back: a uint8 tensor (N, D, H, W), or a Prediction,
+    whose samples and mean label go through ONE call -> a new Prediction with the filled labels and mean_label."""
+    sets = _vol.region_sets(regions, "regions")
+    R = len(sets)
+    if fill is None:
+        if any(len(tuple(reg)) == 0 for reg in regions):
+            raise ValueError("fill_holes: an empty region has no value to fill with")
+        fv = [int(tuple(reg)[0]) for reg in regions]
+    else:
+        fv = _per_region(fill, R, "fill values")
+        for v, reg in zip(fv, regions):
+            if v not in tuple(int(x) for x in reg):
+                raise ValueError(f"fill value {v} is no member of its region {tuple(reg)}")
+    mx = _per_region(max_voxels, R, "max_voxels") or [0] * R
+    if any(m < 0 for m in mx):
+        raise ValueError(f"max_voxels {tuple(mx)}: a limit is a voxel count >= 0")
+    _connectivity(connectivity)
+    rows, is_pred = _prediction_rows(pred)
+    if R < 1 or R > 8:
+        raise _vol.refused("fill_holes", f"{R} regions; 1 <= R <= 8")
+    _vol.on_device(rows, "pred")
+    N, D, H, W = (int(d) for d in rows.shape)
+    nbytes = _ffi.lib().uz_vol_components_workspace(N, D, H, W)
+    if nbytes == 0:
+        raise _vol.refused("fill_holes", f"N {N} volume {D} x {H} x {W}; no empty axis, 1 <= N <= 65536, N*D*H*W < 2^31")
+    ws = _vol.workspace("fill_holes", (rows.device, N, D, H, W), nbytes, rows.device)   # its own slot: a loop alternates it with the keep call
+    rows = rows.contiguous()
+    out = torch.empty_like(rows)
+    _ffi.check(_ffi.lib().uz_vol_fill_holes(rows.data_ptr(), N, D, H, W, (C.c_uint32 * R)(*sets), (C.c_int32 * R)(*fv), (C.c_int32 * R)(*mx), R, connectivity,
+                                            out.data_ptr(), ws.data_ptr(), _vol.stream(rows.device)), "vol_fill_holes")
     if not is_pred:
         return out
     return _filtered_prediction(pred, out)
