@@ -464,7 +464,19 @@ int uz_vol_sample_finish(const double* acc, int K, int S, int D, int H, int W,
  * written): a null pointer (wsum too, whatever add_weight says), a factor below 1, a window that is not level size x factor,
  * ctot < K (gather: Ctot < C), an origin below 0, an extent or size below 1.  A voxel that no window reached (wsum == 0) is data the
  * host part cannot see: uz_vol_window_finish gives it label 0, probabilities 0 and entropy 0 - never NaN; covering the volume is
- * the caller's duty (models/phiseg3D.py window_grid does).                                                                       */
+ * the caller's duty (models/phiseg3D.py window_grid does).
+ * Mirrored passes (predict_volume(flips=...)): flip is a mask 0 .. 7, bit 0, 1, 2 = D, H, W as prm[30] of uz_augment_volume.  A pass
+ * mirrors the WINDOW within itself: net-frame voxel (z, y, x) is window voxel (z', y', x'), z' = wd - 1 - z where bit 0 is set, else z
+ * (likewise y', x'); grid, origins and coverage are those of the unmirrored pass.
+ * uz_vol_window_gather_ex: dst voxel (z, y, x) = src voxel (oz + z', oy + y', ox + x'), 0 where that lies beyond the volume.
+ * uz_vol_window_accum_ex: net-frame voxel (z, y, x) - levels read at (z / fz, y / f, x / f) as ever - adds to volume voxel
+ *   (oz + z', oy + y', ox + x') with the weight (tz[z'] * ty[y']) * tx[x']: the tables are indexed in the window, not in the net frame,
+ *   so they need not be symmetric.  add_weight acts on wsum at the same voxel; nothing is touched where it lies beyond the volume.
+ * uz_vol_window_noise: field (C2, d, h, w) fp32, dense - one sample's row of one latent level's noise - -> dst, the C2-channel slice of
+ *   a plan volume [cd][Ctot][ch][cw]: dst (z, c, y, x) = field (c, oz + z', oy + y', ox + x') with the mirror taken in the crop
+ *   (cd, ch, cw), origin and extents at the LEVEL's resolution.  Every element of the slice is written once.
+ * With flip == 0 the _ex calls give the bytes of the plain ones (which forward to them) and uz_vol_window_noise those of a slice copy.
+ * Refused as above, and: a mask outside 0 .. 7, a crop that leaves its field, C2 d h w or cd C2 ch cw >= 2^31.                     */
 int uz_vol_window_gather(const float* src, int C, int D, int H, int W, int oz, int oy, int ox,
                          float* dst, int Ctot, int wd, int wh, int ww, void* stream);
 int uz_vol_window_accum(const float* const* s_ptrs, const int* ctot, const int* f, const int* fz, int L, int K,
@@ -472,6 +484,14 @@ int uz_vol_window_accum(const float* const* s_ptrs, const int* ctot, const int* 
                         const double* tz, const double* ty, const double* tx, double* acc, double* wsum, int add_weight, void* stream);
 int uz_vol_window_finish(const double* acc, const double* wsum, int K, int S, int D, int H, int W,
                          uint8_t* labels, float* soft, float* mean_soft, uint8_t* mean_label, float* entropy, void* stream);
+int uz_vol_window_gather_ex(const float* src, int C, int D, int H, int W, int oz, int oy, int ox,
+                            float* dst, int Ctot, int wd, int wh, int ww, int flip, void* stream);
+int uz_vol_window_accum_ex(const float* const* s_ptrs, const int* ctot, const int* f, const int* fz, int L, int K,
+                           int wd, int wh, int ww, int oz, int oy, int ox, int D, int H, int W,
+                           const double* tz, const double* ty, const double* tx, double* acc, double* wsum, int add_weight, int flip,
+                           void* stream);
+int uz_vol_window_noise(const float* field, int C2, int d, int h, int w, int oz, int oy, int ox, int cd, int ch, int cw, int flip,
+                        float* dst, int Ctot, void* stream);
 /* Fcomb (probabilistic_unet.py:185-199) in eval mode for S latent draws per image, features read once (ProbabilisticUnet.predict;
  * csrc/fcomb.hip).
  *   feat      (B, C of CtotF, H, W), C == 32

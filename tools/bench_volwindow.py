@@ -8,13 +8,17 @@
             blending or coherent noise (what a host loop would launch before it crops, pads and stitches)
   single  : net.predict_volume(volume, S, window=the padded volume) - the pad-to-divisible route: ONE window, a plan of the whole
             volume (skipped with --no-single, or when its plan cannot be built)
+  With --flips (all | masks 0 .. 7) the windows call runs predict_volume(..., flips=...): per window and mask the mirrored gather, the
+  trunk plan, S x (mirrored noise crop, draw plan, mirrored accum) - and the mirrored kernels are timed alone, per mask, beside the
+  unmirrored ones (gather_ex, accum_ex, and the uz_vol_window_noise launches of one sample: one per latent level).
   and the three kernels of csrc/volwindow.hip alone on the buffers the windows call left: one gather, one accum (an interior
   window), the finish; with the bytes each must move and the GB/s that makes against the HBM figures of BASELINE.md.
 
 Every time is the median of --repeats calls between two device events after --warmup calls (fastest and slowest beside it).  All
 draw their noise on the device.  Prints one JSON line; --notes writes profiles/NOTES_volwindow.md.  Without a GPU the tool exits.
 usage: python tools/bench_volwindow.py [--volume 240 240 155] [--window 128 128 128] [--stride 64 64 64] [--samples 16] [--repeats 3]
-       [--warmup 1] [--graphs 1] [--no-single] [--notes]"""
+       [--warmup 1] [--graphs 1] [--no-single] [--flips all | --flips 0 7 ...] [--notes]
+--notes writes the whole file without --flips and only its section on mirrored passes with it."""
 import argparse
 import ctypes as C
 import json
@@ -64,8 +68,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--graphs", type=int, default=1, help="enable_graphs(), as the harness runs the nets")
     ap.add_argument("--no-single", action="store_true", help="skip the single-window route")
+    ap.add_argument("--flips", nargs="+", default=None, help="mirrored passes: all, or masks in 0 .. 7")
     ap.add_argument("--notes", action="store_true", help="write profiles/NOTES_volwindow.md")
     args = ap.parse_args()
+    flips = None if args.flips is None else "all" if args.flips == ["all"] else tuple(int(m) for m in args.flips)
+    masks = None if flips is None else M.flip_masks(flips)
     if not torch.cuda.is_available():
         sys.exit("bench_volwindow needs a GPU: a time taken anywhere else says nothing")
     dev = torch.device("cuda", 0)
@@ -86,18 +93,18 @@ def main():
     sink = {}
 
     def windows():
-        sink["w"] = net.predict_volume(volume, n_samples=S, window=window, stride=stride)
+        sink["w"] = net.predict_volume(volume, n_samples=S, window=window, stride=stride, flips=flips)
 
     def plain():
         for _ in origins:
             sink["p"] = net.predict(patch, n_samples=S)
 
     def single():
-        sink["s"] = net.predict_volume(volume, n_samples=S, window=padded)
+        sink["s"] = net.predict_volume(volume, n_samples=S, window=padded, flips=flips)
 
     lib, st = _ffi.lib(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
     res = dict(bench="volwindow", filters=FILTERS3D, volume=[D, H, W], window=list(extent), stride=list(stride), windows=len(origins), samples=S,
-               graphs=args.graphs, repeats=args.repeats, conv_math=lib.uz_get_conv_math(), device=torch.cuda.get_device_name(0))
+               graphs=args.graphs, repeats=args.repeats, flips=None if masks is None else list(masks), conv_math=lib.uz_get_conv_math(), device=torch.cuda.get_device_name(0))
     with torch.no_grad():
         tw = measure(windows, args.warmup, args.repeats)
         tp = measure(plain, args.warmup, args.repeats)
@@ -134,12 +141,35 @@ def main():
                    kernels_share_of_call=round(in_call / statistics.median(tw), 4),
                    accumulators_GB=round(8 * n * (S * K + 1) / 1e9, 3),
                    window_plans_GB=round(4 * (trunk.arena_floats + draw.arena_floats) / 1e9, 3))
+        if masks is not None:                                                        # the mirrored kernels alone, per mask
+            eps = [torch.randn(1, 2, *(p >> (nl - 1 - k) for p in padded), device=dev) for k in range(nl)]
+
+            def kernels(m):
+                def gather_ex():
+                    _ffi.check(lib.uz_vol_window_gather_ex(src.data_ptr(), Cin, D, H, W, *o, trunk._resolve(pview), pview.Ctot, ed, eh, ew, m, st),
+                               "gather_ex")
+
+                def noise():
+                    for k, (e, v) in enumerate(zip(eps, draw.io["eps"])):
+                        sh = nl - 1 - k
+                        _ffi.check(lib.uz_vol_window_noise(e.data_ptr(), 2, *e.shape[2:], o[0] >> sh, o[1] >> sh, o[2] >> sh, ed >> sh, eh >> sh,
+                                                           ew >> sh, m, draw._resolve(v), v.Ctot, st), "noise")
+
+                def accum_ex():
+                    _ffi.check(lib.uz_vol_window_accum_ex(tb["ptrs"], tb["ctot"], tb["f"], tb["fz"], nl, K, ed, eh, ew, *o, D, H, W, wt[0].data_ptr(),
+                                                          wt[1].data_ptr(), wt[2].data_ptr(), acc[0].data_ptr(), wsum.data_ptr(), 0, m, st), "accum_ex")
+                return {fn.__name__: stats(measure(fn, max(args.warmup, 2), max(args.repeats, 10))) for fn in (gather_ex, noise, accum_ex)}
+            res["flip_kernels_ms"] = {str(m): kernels(m) for m in masks}
+            per_pass = {m: v["gather_ex"]["median"] + S * (v["noise"]["median"] + v["accum_ex"]["median"]) for m, v in res["flip_kernels_ms"].items()}
+            res.update(flip_kernels_per_window_ms={m: round(v, 3) for m, v in per_pass.items()},
+                       unmirrored_kernels_per_window_ms=round(med["gather"] + S * med["accum"], 3),
+                       flip_kernels_in_call_ms=round(len(origins) * sum(per_pass.values()) + med["finish"], 3))
         windows()                                                                    # the timing launches added to acc: a fresh call, then compare
         net.set_rng_state(11)
-        x = net.predict_volume(volume, n_samples=2, window=window, stride=stride)
+        x = net.predict_volume(volume, n_samples=2, window=window, stride=stride, flips=flips)
         keep = (x.labels.clone(), x.mean_soft.clone())
         net.set_rng_state(11)
-        y = net.predict_volume(volume, n_samples=2, window=window, stride=stride)
+        y = net.predict_volume(volume, n_samples=2, window=window, stride=stride, flips=flips)
         res["repeat_bit_equal"] = bool(torch.equal(keep[0], y.labels) and torch.equal(keep[1], y.mean_soft))
         if not args.no_single:
             try:
@@ -152,10 +182,51 @@ def main():
         res["bound_flags"] = net.check_bounds()
     print(json.dumps(res), flush=True)
     if args.notes:
-        write_notes(res, args)
+        (write_flip_notes if masks is not None else write_notes)(res, args)
+
+
+FLIP_HEAD = "## Mirrored passes"
+KEPT_HEAD = "## Against the parent commit"          # written by hand behind the section on mirrored passes: kept as it is
+
+
+def _flip_section():
+    """The section on mirrored passes of the notes as they stand (write_flip_notes wrote it), or nothing."""
+    path = os.path.join(ROOT, "profiles", "NOTES_volwindow.md")
+    text = open(path).read() if os.path.exists(path) else ""
+    return text[text.index(FLIP_HEAD):] if FLIP_HEAD in text else ""
+
+
+def write_flip_notes(r, args):
+    """Replace the section on mirrored passes; the rest of the notes - the run without --flips - stays."""
+    f3 = lambda d: f"{d['median']} ({d['min']} - {d['max']})"                       # noqa: E731
+    path = os.path.join(ROOT, "profiles", "NOTES_volwindow.md")
+    text = open(path).read() if os.path.exists(path) else ""
+    head = text[:text.index(FLIP_HEAD)] if FLIP_HEAD in text else text.rstrip("\n") + "\n\n"
+    kept = text[text.index(KEPT_HEAD):] if KEPT_HEAD in text else ""
+    n = len(r["flips"])
+    lines = [
+        FLIP_HEAD, "",
+        f"`tools/bench_volwindow.py --flips {' '.join(map(str, args.flips))} --notes` on {r['device']}: the same volume, window, stride and S = "
+        f"{r['samples']}, `predict_volume(..., flips={r['flips']})` = {n} passes per window, graphs {r['graphs']}, convolution mode {r['conv_math']}; "
+        "times as above.", "",
+        "| what | ms |", "|---|---|",
+        f"| `predict_volume`, {r['windows']} windows x {n} masks | {f3(r['windows_ms'])} |",
+        f"| {r['windows']} plain `predict()` calls (no mirror) | {f3(r['plain_ms'])} |", "",
+        f"The call over the plain calls: {r['windows_over_plain']} for {n} passes.", "",
+        "The mirrored kernels alone, on one interior window (`noise`: one sample's `uz_vol_window_noise` launches, one per latent level):", "",
+        "| mask | `gather_ex` ms | `noise` ms | `accum_ex` ms | per window: gather + S (noise + accum) ms |", "|---|---|---|---|---|"]
+    for m, v in r["flip_kernels_ms"].items():
+        lines.append(f"| {m} | {f3(v['gather_ex'])} | {f3(v['noise'])} | {f3(v['accum_ex'])} | {r['flip_kernels_per_window_ms'][m]} |")
+    lines += ["", f"Unmirrored in the same run: `uz_vol_window_gather` {f3(r['gather_ms'])}, `uz_vol_window_accum` {f3(r['accum_ms'])}, per window "
+              f"gather + S accum = {r['unmirrored_kernels_per_window_ms']} ms (the unmirrored call crops its noise with ATen copies, which are not in that sum).",
+              f"In one call: {r['flip_kernels_in_call_ms']} ms of window kernels, {100 * r['flip_kernels_in_call_ms'] / r['windows_ms']['median']:.2f} % of the call.  "
+              f"A repeated call from the same generator state was bit-equal: {r['repeat_bit_equal']}.  Bound flags after the run: {r['bound_flags']}.", ""]
+    with open(path, "w") as f:
+        f.write(head + "\n".join(lines) + "\n" + kept)
 
 
 def write_notes(r, args):
+    flip_section = _flip_section()
     f3 = lambda d: f"{d['median']} ({d['min']} - {d['max']})"                       # noqa: E731
     vol, win = " x ".join(map(str, r["volume"])), " x ".join(map(str, r["window"]))
     lines = [
@@ -199,7 +270,7 @@ def write_notes(r, args):
         lines += [f"The single window was not measured here; the window's two plans hold {r['window_plans_GB']} GB.  Prefer the windows - the "
                   "default; the single window is the route for volumes that are at most a window large.", ""]
     with open(os.path.join(ROOT, "profiles", "NOTES_volwindow.md"), "w") as f:
-        f.write("\n".join(lines) + "\n")
+        f.write("\n".join(lines) + "\n" + (flip_section and "\n" + flip_section))
 
 
 if __name__ == "__main__":

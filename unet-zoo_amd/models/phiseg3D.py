@@ -17,6 +17,7 @@ Beyond the reference: predict(patch, n_samples) - samples, mean probabilities an
 and predict_volume(volume, n_samples, window, stride, blend): the same for a volume of any size, from blended windows.
 """
 import ctypes as C
+import operator
 
 import torch
 
@@ -80,6 +81,22 @@ def blend_tables(extent, blend):
         i = np.arange(int(w), dtype=np.float64)
         out.append(np.exp(-0.5 * ((i - (w - 1) / 2.0) / (w / 8.0)) ** 2) if blend == "gaussian" else np.ones(int(w), np.float64))
     return out
+
+
+def flip_masks(flips):
+    """The flip masks of predict_volume(flips=...) in the order of the passes: "all" -> 0 .. 7; else a non-empty sequence of distinct
+    ints in 0 .. 7 (bit 0, 1, 2 mirror D, H, W).  Anything else is a ValueError."""
+    if isinstance(flips, str) and flips == "all":
+        return tuple(range(8))
+    try:
+        if isinstance(flips, str) or any(isinstance(m, bool) for m in flips):
+            raise TypeError
+        masks = tuple(operator.index(m) for m in flips)
+    except TypeError:
+        masks = ()
+    if not masks or any(not 0 <= m <= 7 for m in masks) or len(set(masks)) != len(masks):
+        raise ValueError(f'flips must be None, "all" or a non-empty sequence of distinct integer masks in 0 .. 7, got {flips!r}')
+    return masks
 
 
 class PHISeg3D(HierarchicalModel):
@@ -302,7 +319,7 @@ class PHISeg3D(HierarchicalModel):
                 raise ValueError(f"predict_volume() needs a window: image_size {tuple(self.image_size)} names no (D, H, W)")
         return window_grid(dhw, window, stride, g)
 
-    def predict_volume(self, volume, n_samples=1, window=None, stride=None, blend="gaussian", eps=None, return_soft=False):
+    def predict_volume(self, volume, n_samples=1, window=None, stride=None, blend="gaussian", eps=None, return_soft=False, flips=None):
         """predict() for a volume of ANY size (1, C, D, H, W): the net runs on overlapping windows of the size it was trained at and
         the windows' probabilities are blended.  window defaults to image_size[1:], stride to half of it; window_grid() says where the
         windows lie (a window no smaller than the volume rounded up to 2^(levels-1) is the plain pad-to-divisible route: one window),
@@ -315,7 +332,20 @@ class PHISeg3D(HierarchicalModel):
         between calls and zeroed at the start of each: S accumulators (K, D, H, W) and one weight sum (D, H, W), all fp64 =
         8 (S K + 1) D H W bytes - the accumulators 3.4 GB, the weight sum 71 MB at 240 x 240 x 155, K = 3, S = 16.  Returns predict()'s Prediction for (D, H, W) (levels = None);
         sample s: p_s = sum_windows weight * softmax / sum_windows weight, labels its first maximum, mean_soft the mean over the samples,
-        mean_label / entropy from the unrounded mean.  prior_mu / prior_sigma / prior_latent_space are left as they are."""
+        mean_label / entropy from the unrounded mean.  prior_mu / prior_sigma / prior_latent_space are left as they are.
+        flips: mirrored passes (flip test-time augmentation; the net is trained with random flips on all three axes).  None - the
+        default - is the call above.  "all" = the masks 0 .. 7, or a sequence of distinct masks in 0 .. 7, in the order of the passes
+        (it may leave out 0, the unmirrored pass); bit 0, 1, 2 of a mask mirror D, H, W.  A pass with mask m mirrors every window
+        WITHIN ITSELF - grid, order of the visits and coverage stay: net-frame voxel (z, y, x) of a window of extent (wd, wh, ww) at
+        (oz, oy, ox) is volume voxel (oz + z', oy + y', ox + x'), z' = wd - 1 - z where bit 0 is set, else z (likewise y', x').  The net
+        reads that voxel (0 beyond the volume); the window's crop of every level's noise field, cut as without a mirror, is mirrored
+        within the crop at the level's resolution, so a sample's noise stays attached to the anatomy under every mask; the net's
+        probabilities at (z, y, x) are added at that volume voxel with the weight (tz[z'] ty[y']) tx[x'].  Order of work: per window,
+        per mask: the mirrored gather (uz_vol_window_gather_ex) and the trunk plan once, then per sample the mirrored noise crop
+        (uz_vol_window_noise, straight into the draw plan), the draw plan and uz_vol_window_accum_ex into the SAME accumulators; the
+        weight sum takes every (window, mask) pair once, so p_s = sum_windows sum_masks weight * softmax / sum weight, averaged before
+        any rounding.  One stream, no atomics: a repeated call is bit-equal.  Cost: n masks = n times the trunk and draw plans; no
+        memory beyond the call without flips."""
         S, nl, K, R = int(n_samples), self.latent_levels, self.num_classes, len(self.num_filters)
         if S < 1:
             raise ValueError("predict_volume() needs n_samples >= 1")
@@ -324,6 +354,7 @@ class PHISeg3D(HierarchicalModel):
         D, H, W = self._dims(volume)
         padded, extent, origins = self.window_plan((D, H, W), window, stride)
         tables = blend_tables(extent, blend)
+        masks = None if flips is None else flip_masks(flips)
         shapes = [(S, 2, *(n >> (R - 1 - k) for n in padded)) for k in range(nl)]             # deepest level first
         if eps is not None and (len(eps) != nl or [tuple(e.shape) for e in eps] != shapes):
             raise ValueError(f"predict_volume() takes {nl} eps tensors of the shapes {shapes} (deepest level first), got "
@@ -354,19 +385,36 @@ class PHISeg3D(HierarchicalModel):
         if eps is None:
             eps = [self._fill_normal(torch.empty(shape, device=dev)) for shape in shapes]
         patch = trunk.io["patch"]
+        if masks is not None:
+            eps = [e.to(device=dev, dtype=torch.float32).contiguous() for e in eps]
         for oz, oy, ox in origins:
-            _ffi.check(L.uz_vol_window_gather(src.data_ptr(), self.input_channels, D, H, W, oz, oy, ox, trunk._resolve(patch), patch.Ctot,
-                                              ed, eh, ew, st), "vol_window_gather")
-            self._run_trunk(trunk, draw)
-            for s in range(S):
-                noise = []
-                for k, e in enumerate(eps):
-                    sh = R - 1 - k                                                              # origins are multiples of 2^(R-1)
-                    noise.append(e[s:s + 1, :, oz >> sh:(oz + ed) >> sh, oy >> sh:(oy + eh) >> sh, ox >> sh:(ox + ew) >> sh])
-                self._draw(draw, noise)
-                _ffi.check(L.uz_vol_window_accum(tb["ptrs"], tb["ctot"], tb["f"], tb["fz"], nl, K, ed, eh, ew, oz, oy, ox, D, H, W,
-                                                 wt[0].data_ptr(), wt[1].data_ptr(), wt[2].data_ptr(), acc[s].data_ptr(), wsum.data_ptr(),
-                                                 int(s == 0), st), "vol_window_accum")
+            for m in (None,) if masks is None else masks:
+                if m is None:
+                    _ffi.check(L.uz_vol_window_gather(src.data_ptr(), self.input_channels, D, H, W, oz, oy, ox, trunk._resolve(patch), patch.Ctot,
+                                                      ed, eh, ew, st), "vol_window_gather")
+                else:
+                    _ffi.check(L.uz_vol_window_gather_ex(src.data_ptr(), self.input_channels, D, H, W, oz, oy, ox, trunk._resolve(patch),
+                                                         patch.Ctot, ed, eh, ew, m, st), "vol_window_gather_ex")
+                self._run_trunk(trunk, draw)
+                for s in range(S):
+                    if m is None:
+                        noise = []
+                        for k, e in enumerate(eps):
+                            sh = R - 1 - k                                                      # origins are multiples of 2^(R-1)
+                            noise.append(e[s:s + 1, :, oz >> sh:(oz + ed) >> sh, oy >> sh:(oy + eh) >> sh, ox >> sh:(ox + ew) >> sh])
+                        self._draw(draw, noise)
+                        _ffi.check(L.uz_vol_window_accum(tb["ptrs"], tb["ctot"], tb["f"], tb["fz"], nl, K, ed, eh, ew, oz, oy, ox, D, H, W,
+                                                         wt[0].data_ptr(), wt[1].data_ptr(), wt[2].data_ptr(), acc[s].data_ptr(), wsum.data_ptr(),
+                                                         int(s == 0), st), "vol_window_accum")
+                        continue
+                    for k, (e, v) in enumerate(zip(eps, draw.io["eps"])):
+                        sh = R - 1 - k
+                        _ffi.check(L.uz_vol_window_noise(e[s].data_ptr(), 2, *e.shape[2:], oz >> sh, oy >> sh, ox >> sh, ed >> sh, eh >> sh, ew >> sh,
+                                                         m, draw._resolve(v), v.Ctot, st), "vol_window_noise")
+                    self._run(draw, "fwd")
+                    _ffi.check(L.uz_vol_window_accum_ex(tb["ptrs"], tb["ctot"], tb["f"], tb["fz"], nl, K, ed, eh, ew, oz, oy, ox, D, H, W,
+                                                        wt[0].data_ptr(), wt[1].data_ptr(), wt[2].data_ptr(), acc[s].data_ptr(), wsum.data_ptr(),
+                                                        int(s == 0), m, st), "vol_window_accum_ex")
         out = Prediction(labels=torch.empty(S, 1, D, H, W, dtype=torch.uint8, device=dev), mean_soft=torch.empty(1, K, D, H, W, device=dev),
                          mean_label=torch.empty(1, D, H, W, dtype=torch.uint8, device=dev), entropy=torch.empty(1, D, H, W, device=dev),
                          levels=None, soft=torch.empty(S, 1, K, D, H, W, device=dev) if return_soft else None)

@@ -337,13 +337,16 @@ class UNetModel:
         return dict(dice=self.avg_dice, foreground_dice=self.foreground_dice, elbo=self.val_elbo, ged=self.avg_ged, ncc=self.avg_ncc)
 
     @torch.no_grad()
-    def predict(self, images, n_samples=1, window=None, stride=None, blend="gaussian"):
+    def predict(self, images, n_samples=1, window=None, stride=None, blend="gaussian", flips=None):
         """Segment unlabelled images: a numpy or torch batch (B, H, W) or (B, C, H, W) - or, for PHISeg3D, one volume (1, C, D, H, W),
         handed through as it is - -> the net's Prediction (models/phiseg.py) of `n_samples` prior samples per image.  No mask, no
         loss: validate() and test() keep the reference's loop.  With `window` (PHISeg3D only) the volume may have any size and goes
-        to predict_volume(): windows of that extent, `stride` apart, blended with `blend` weights."""
+        to predict_volume(): windows of that extent, `stride` apart, blended with `blend` weights, and with `flips` ("all" or a
+        sequence of masks 0 .. 7; needs `window`) averaged over mirrored passes of every window."""
         if not hasattr(self.net, "predict"):
             raise NotImplementedError(f"{type(self.net).__name__} has no mask-free predict()")
+        if flips is not None and window is None:
+            raise ValueError("predict(): `flips` are the mirrored passes of predict_volume() and need `window`")
         self.net.eval()
         patch = torch.as_tensor(images, dtype=torch.float32).to(self.device)
         if patch.dim() == 3:
@@ -351,7 +354,7 @@ class UNetModel:
         if window is not None:
             if not hasattr(self.net, "predict_volume"):
                 raise NotImplementedError(f"{type(self.net).__name__} has no predict_volume(): `window` is for PHISeg3D")
-            return self.net.predict_volume(patch.contiguous(), n_samples=n_samples, window=window, stride=stride, blend=blend)
+            return self.net.predict_volume(patch.contiguous(), n_samples=n_samples, window=window, stride=stride, blend=blend, flips=flips)
         return self.net.predict(patch.contiguous(), n_samples=n_samples)
 
     @torch.no_grad()
