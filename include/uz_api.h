@@ -890,6 +890,74 @@ int    uz_vol_fill_holes(const uint8_t* vol, int N, int D, int H, int W, const u
                          const int32_t* max_voxels, int R, int connectivity, uint8_t* out, void* workspace, void* stream);
 int    uz_vol_components_route_ex(int N, int D, int H, int W, int connectivity, int* out2);
 
+/* ---------------------------------------------------------------- volume morphology and lesion-wise scores (the BraTS rankings since 2023)
+ * uz_vol_morph: binary dilation (erode = 0) or erosion (erode = 1) of the membership mask of N label volumes.  vol (N, D, H, W) uint8,
+ * dense, W fastest; foreground is {label in set}, a SET as the components calls take it (a value of 32 or more is in no set).
+ * out (N, D, H, W) uint8 = 0 / 1.  The call is scipy.ndimage.binary_dilation / binary_erosion with
+ * structure = generate_binary_structure(3, connectivity), iterations = `iterations`, border_value = 0: `iterations` passes of the 7-,
+ * 19- or 27-voxel stencil, a voxel outside the volume reading as 0 - an erosion eats inward from the faces, as scipy's does.  With
+ * D == 1 there is no z neighbour and the stencil is the 2-D one (5, 9 or 9 voxels), the rule of the labelling calls: scipy on the
+ * 2-D array.  Volumes never touch each other, rows never wrap into the next row; iterations == 0 copies the membership mask.
+ * Bit planes (csrc/volmorph.hip): the mask is packed once, one 64-bit word per ballot of a wave, rows padded to whole words; every
+ * pass works on words - an x step is w | w << 1 | w >> 1 with the carry bits of the neighbouring words of the same row, a y or z
+ * step an OR (erosion: AND) with the words of the neighbouring rows, x-widened where one more coordinate may differ - and clears the
+ * pad bits of every row's last word; the result is unpacked once.  One launch per pass.  Integer and exact, bit-equal on repetition.
+ * `workspace`: uz_vol_morph_workspace bytes (two packed planes), 16-byte aligned; 0 for sizes the call refuses.
+ * Refused before any launch (-1, uz_last_error names the reason, nothing written): a null pointer, an empty axis, N < 1 or
+ * N > UZ_VOL_MAX_ROWS, N*D*H*W >= 2^31, a connectivity outside 1 .. 3, iterations < 0, erode outside 0 / 1, a workspace off 16 bytes,
+ * out overlapping vol.
+ * uz_vol_morph_route (host only): out2[0] = the 64-bit words of a packed row, out2[1] = workgroups of the widest launch of a call.
+ *
+ * uz_vol_lesion_scores: N label volumes pred (N, D, H, W) against ONE label volume ref (D, H, W) for R regions, the operands of
+ * uz_vol_region_scores (pred_sets / ref_sets: R bit masks in HOST memory).  The definition below is this library's CONTRACT; it follows
+ * the published description of the BraTS 2023 lesion-wise ranking, but parity with the challenge's own tool is not pinned (the tool
+ * is not part of the test tier).  For region r and row n let G = the reference voxels in ref_sets[r], P = the row's voxels in
+ * pred_sets[r], Dk = G dilated `dilation` times with the 18-neighbour structure (uz_vol_morph, connectivity 2).
+ *   1. Reference lesions are the 26-connected components of Dk, numbered g = 0 .. n_ref-1 by ascending canonical label - the order of
+ *      their first voxels in C order, scipy.ndimage.label's numbering.  gt_vol[g] = |G and Dk_g|.  Two reference blobs that the
+ *      dilation joins are ONE lesion.  Computed once per region: it does not depend on the row.
+ *   2. Predicted components are the 26-connected components of P, with their sizes.
+ *   3. match(g) = the predicted components with at least one voxel in Dk_g; pred_vol[n][g] = the sum of their FULL sizes, each
+ *      component once; inter[n][g] = |G and Dk_g and P|.  A component may match several lesions and counts in the pred_vol of each.
+ *      (Dilating every lesion on its own gives the same Dk_g, and every predicted voxel inside Dk_g belongs to a matched component.)
+ *   4. A lesion is KEPT when gt_vol[g] >= min_ref_voxels; one that is not kept is dropped from every sum, and a component that
+ *      touches a dropped lesion's Dk_g is still no false positive.  A predicted component is a FALSE POSITIVE when it has no voxel
+ *      in Dk at all and its size is >= min_pred_voxels.
+ *   5. dice_g = 2 inter / (gt_vol + pred_vol), 0 for a missed lesion (pred_vol == 0).  n_tp / n_fn = kept lesions with / without a match.
+ *      scores (N, R, 4) fp64 = {lesion_dice = (sum over kept g of dice_g) / (n_kept + n_fp), summed serially in ascending g in fp64;
+ *      lesion sensitivity n_tp / n_kept; precision n_tp / (n_tp + n_fp); F1 = 2 n_tp / (2 n_tp + n_fn + n_fp)}; an empty denominator
+ *      gives 1.0.  counts (N, R, 8) int64 = {n_ref, n_kept, n_tp, n_fn, n_fp, n_pred, lesions beyond max_lesions, roots with links
+ *      beyond max_links}.  lesions (N, R, max_lesions, 3) int64, nullable = {gt_vol, inter, pred_vol} per lesion, 0 beyond n_ref.
+ *   Overflow: the tables hold max_lesions lesions and a component is linked to at most max_links lesions.  A lesion beyond the table
+ *   keeps its voxels in Dk (a component on it is no false positive) but enters no table and no sum; all such lesions together are one
+ *   link.  counts[6] = n_ref - max_lesions when positive, counts[7] = the predicted components that touch more than max_links
+ *   different lesions.  Either one non-zero makes the four scores of that (n, r) NaN; the call still returns 0: this is data the
+ *   host part cannot see.  The lesion-wise HD95 is not built (it needs a distance transform per lesion, restricted to its box).
+ * csrc/vollesion.hip: per region uz_vol_morph and two uz_vol_label_components_ex sweeps at connectivity 3 (the reference side on one
+ * volume, the prediction side on all N), a two-level count that ranks the root voxels of Dk, and the (component, lesion) pairs
+ * counted once each by max_links rounds of an integer fetch_min on one word per component root, the root's own thread adding the
+ * component's size behind every round.  Integer atomics only, no float atomics: exact, independent of order, bit-equal on repetition.
+ * `workspace`: uz_vol_lesion_scores_workspace bytes, 16-byte aligned: the labelling's workspace for N volumes, the morphology's for
+ * one, a uint8 and two int32 volumes for the reference side, two int32 volumes per row, and the tables.
+ * Refused before any launch (-1, nothing written): a null pointer (lesions excepted), an empty axis, N < 1 or N > UZ_VOL_MAX_ROWS,
+ * R < 1 or R > UZ_VOL_MAX_REGIONS, N*D*H*W >= 2^31, dilation outside 0 .. UZ_VOL_MAX_DILATION, a negative min_ref_voxels or
+ * min_pred_voxels, max_lesions outside 1 .. UZ_VOL_MAX_LESIONS, max_links outside 1 .. UZ_VOL_MAX_LINKS, a workspace off 16 bytes,
+ * counts, lesions or scores off 8.  uz_vol_lesion_scores_workspace returns 0 for the sizes the call would refuse.
+ * uz_vol_lesion_scores_route (host only): out2[0] = the merge instance both labelling sweeps take (3), out2[1] = workgroups of the
+ * widest launch of a call.                                                                                                      */
+#define UZ_VOL_MAX_DILATION 16
+#define UZ_VOL_MAX_LESIONS 4096
+#define UZ_VOL_MAX_LINKS 16
+size_t uz_vol_morph_workspace(int N, int D, int H, int W);
+int    uz_vol_morph(const uint8_t* vol, int N, int D, int H, int W, uint32_t set, int connectivity, int iterations, int erode,
+                    uint8_t* out, void* workspace, void* stream);
+int    uz_vol_morph_route(int N, int D, int H, int W, int* out2);
+size_t uz_vol_lesion_scores_workspace(int N, int R, int D, int H, int W, int max_lesions);
+int    uz_vol_lesion_scores(const uint8_t* pred, int N, const uint32_t* pred_sets, const uint8_t* ref, const uint32_t* ref_sets, int R,
+                            int D, int H, int W, int dilation, int min_ref_voxels, int min_pred_voxels, int max_lesions, int max_links,
+                            void* workspace, int64_t* counts, int64_t* lesions, double* scores, void* stream);
+int    uz_vol_lesion_scores_route(int N, int R, int D, int H, int W, int* out2);
+
 /* ---------------------------------------------------------------- volume uncertainty (the BraTS uncertainty task; calibration)
  * Judges S sampled label volumes of ONE case as an uncertainty estimate against one reference, per region, from the votes of the
  * samples: with S samples a voxel's region probability takes only the S + 1 values c / S, so one integer table per region holds

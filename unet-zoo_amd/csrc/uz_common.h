@@ -170,6 +170,19 @@ static inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline int sweep_grid(long long work_items, int threads, long long cap = INT_MAX) {
     return (int)std::min<long long>((std::max<long long>(work_items, 1) + threads - 1) / threads, cap);
 }
+// the reason a call on N volumes of D x H x W voxels is refused, or null (volcomp.hip, volmorph.hip, vollesion.hip)
+static inline const char* vol_sizes_bad(int N, int D, int H, int W) {
+    if (D < 1 || H < 1 || W < 1) return "empty axis";
+    if (N < 1 || N > UZ_VOL_MAX_ROWS) return "1 <= N <= 65536 volumes";
+    long long t = N;
+    for (int f : {D, H, W}) { t *= f; if (t >= (1LL << 31)) return "N*D*H*W must stay below 2^31"; }
+    return nullptr;
+}
+// two blocks of `bytes` bytes share a byte
+static inline bool bytes_overlap(const void* a_, const void* b_, long long bytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(a_), b = reinterpret_cast<uintptr_t>(b_);
+    return !(a + (uintptr_t)bytes <= b || b + (uintptr_t)bytes <= a);
+}
 
 // conv_split.hip: 3x3 forward / data gradient on the fp16 matrix pipe with two-piece split operands (fp32-accurate)
 bool conv_split_ok(int Kc, int Mc, int N, int H, int W, int ks, int dgrad);

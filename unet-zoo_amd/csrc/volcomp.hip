@@ -249,13 +249,7 @@ __global__ __launch_bounds__(256) void comp_fill_k(const uint8_t* __restrict__ v
 }
 
 // ------------------------------------------------------------------------------------------------ host
-const char* sizes_bad(int N, int D, int H, int W) {
-    if (D < 1 || H < 1 || W < 1) return "empty axis";
-    if (N < 1 || N > UZ_VOL_MAX_ROWS) return "1 <= N <= 65536 volumes";
-    long long t = N;
-    for (int f : {D, H, W}) { t *= f; if (t >= (1LL << 31)) return "N*D*H*W must stay below 2^31"; }
-    return nullptr;
-}
+inline const char* sizes_bad(int N, int D, int H, int W) { return uz::vol_sizes_bad(N, D, H, W); }
 inline int vox_grid(long long T) { return uz::sweep_grid(T, 256, VOX_GRID_MAX); }
 inline int row_grid(long long rows) { return uz::sweep_grid(rows, 4, ROW_GRID_MAX); }
 inline int sel_per_vol(int P) { return (int)(((long long)P + SEL_VOX - 1) / SEL_VOX); }
@@ -291,10 +285,7 @@ template <bool INV> int label_set(const uint8_t* vol, uint32_t set, int connecti
     }
     return uz::fail("vol components: connectivity %d", connectivity);
 }
-inline bool overlap(const void* vol, const void* out, long long T) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(vol), b = reinterpret_cast<uintptr_t>(out);
-    return !(a + (uintptr_t)T <= b || b + (uintptr_t)T <= a);
-}
+inline bool overlap(const void* vol, const void* out, long long T) { return uz::bytes_overlap(vol, out, T); }
 
 // uz_vol_label_components and uz_vol_label_components_ex: `who` names the caller in a refusal
 int label_call(const char* who, const uint8_t* vol, int N, int D, int H, int W, uint32_t set, int connectivity, int32_t* labels, int32_t* sizes,

@@ -344,6 +344,113 @@ def fill_holes(pred, regions=((1, 2, 3),), fill=None, max_voxels=None, connectiv
     return _filtered_prediction(pred, out)
 
 
+# --------------------------------------------------------------------------- binary morphology and lesion-wise scores (the BraTS rankings since 2023)
+def _morph(what, volumes, values, iterations, connectivity, erode):
+    _connectivity(connectivity)
+    if isinstance(iterations, bool) or not isinstance(iterations, int):
+        raise TypeError(f"iterations must be an int >= 0, not {iterations!r}")
+    if iterations < 0:
+        raise ValueError(f"iterations {iterations}: a number of passes >= 0")
+    rows = _vol.label_tensor(volumes, "volumes", "(N, D, H, W)", 4)
+    (bits,) = _vol.region_sets((tuple(values),), "values")
+    _vol.on_device(rows, "volumes")
+    N, D, H, W = (int(d) for d in rows.shape)
+    L, dev = _ffi.lib(), rows.device
+    nbytes = L.uz_vol_morph_workspace(N, D, H, W)
+    if nbytes == 0:
+        raise _vol.refused(what, f"N {N} volume {D} x {H} x {W}; no empty axis, 1 <= N <= 65536, N*D*H*W < 2^31")
+    ws = _vol.workspace("morph", (dev, N, D, H, W), nbytes, dev)
+    rows = rows.contiguous()
+    out = torch.empty_like(rows)
+    _ffi.check(L.uz_vol_morph(rows.data_ptr(), N, D, H, W, bits, connectivity, iterations, erode, out.data_ptr(), ws.data_ptr(), _vol.stream(dev)), "vol_morph")
+    return out
+
+
+def binary_dilation(volumes, values, iterations=1, connectivity=1):
+    """scipy.ndimage.binary_dilation of {label in values} in N label volumes, uint8 (N, D, H, W) on the device, with
+    structure = generate_binary_structure(3, connectivity) - 6, 18 or 26 neighbours; the 2-D structure when D == 1 -, `iterations`
+    passes and border_value = 0: one uz_vol_morph call (csrc/volmorph.hip) on the caller's current stream, no synchronisation.
+    `volumes`, `values` and `connectivity` are what label_components takes.  Returns a uint8 tensor (N, D, H, W) of 0 / 1;
+    iterations = 0 gives the membership mask itself.  Volumes never touch each other."""
+    return _morph("binary_dilation", volumes, values, iterations, connectivity, 0)
+
+
+def binary_erosion(volumes, values, iterations=1, connectivity=1):
+    """scipy.ndimage.binary_erosion, as binary_dilation: a voxel outside the volume reads as 0, so an erosion eats inward from the
+    faces (border_value = 0, scipy's default)."""
+    return _morph("binary_erosion", volumes, values, iterations, connectivity, 1)
+
+
+def binary_opening(volumes, values, iterations=1, connectivity=1):
+    """scipy.ndimage.binary_opening: `iterations` erosions, then as many dilations of the result - two uz_vol_morph calls"""
+    return _morph("binary_opening", _morph("binary_opening", volumes, values, iterations, connectivity, 1), (1,), iterations, connectivity, 0)
+
+
+def binary_closing(volumes, values, iterations=1, connectivity=1):
+    """scipy.ndimage.binary_closing: `iterations` dilations, then as many erosions of the result - two uz_vol_morph calls.  The border
+    reads as 0 in both, as scipy's does: a closing can eat foreground that lies within `iterations` voxels of a face."""
+    return _morph("binary_closing", _morph("binary_closing", volumes, values, iterations, connectivity, 0), (1,), iterations, connectivity, 1)
+
+
+LesionScores = collections.namedtuple("LesionScores", "lesion_dice sensitivity precision f1 counts lesions")
+LesionScores.__doc__ = """What score_lesions returns, all on the device: lesion_dice, sensitivity, precision, f1 (N, R) fp64 - views of one (N, R, 4) buffer;
+NaN where a table overflowed - counts (N, R, 8) int64 = {n_ref, n_kept, n_tp, n_fn, n_fp, n_pred, lesions beyond max_lesions, components with links
+beyond max_links}, and lesions (N, R, max_lesions, 3) int64 = {gt_vol, inter, pred_vol} per reference lesion, or None when it was not asked for."""
+
+
+def score_lesions(pred, reference, pred_regions, ref_regions=None, dilation=3, min_ref_voxels=50, min_pred_voxels=0, max_lesions=256, max_links=4,
+                  return_lesions=False):
+    """Lesion-wise scores of N label volumes against ONE reference volume for R regions, the operands of score_volume (a 3-D
+    Prediction, filtered or not - its S samples, then mean_label - or a uint8 tensor (N, D, H, W); reference uint8 (D, H, W)) - one
+    uz_vol_lesion_scores call (csrc/vollesion.hip) on the caller's current stream: no host round trip, no synchronisation.
+    Per region: the reference lesions are the 26-connected components of the reference region dilated `dilation` times with the
+    18-neighbour structure (two blobs the dilation joins are one lesion; a lesion's volume counts its undilated voxels); a lesion is
+    matched to every predicted 26-connected component that reaches its dilated extent, and its Dice is 2 |lesion and prediction| /
+    (|lesion| + the full sizes of those components).  Lesions of fewer than min_ref_voxels voxels are dropped from every sum; a
+    predicted component that reaches no dilated lesion at all and has at least min_pred_voxels voxels is a false positive.
+    lesion_dice = (sum of the kept lesions' Dice) / (kept lesions + false positives), 1 when both are none: every missed lesion and
+    every false positive enters as a 0.  sensitivity, precision and f1 count kept lesions with a match, without one, and the false
+    positives.  The definition is this project's contract (include/uz_api.h spells it out); it follows the description of the BraTS
+    2023 ranking, parity with the challenge's own tool is not pinned, and the defaults - dilation 3, min_ref_voxels 50 - are OUR
+    reading of its glioma settings.  The lesion-wise HD95 is not built.
+    max_lesions (1 .. 4096) bounds the per-lesion tables and max_links (1 .. 16) the lesions one predicted component may reach; where
+    either is exceeded the scores of that (row, region) are NaN and counts[..., 6] / counts[..., 7] say by how much - nothing is
+    looked at on the host, so nothing raises.  Returns a LesionScores of device tensors."""
+    if _vol.is_prediction(pred):
+        rows = _vol.prediction_rows(*_vol.prediction_maps(pred))
+    else:
+        rows = _vol.label_tensor(pred, "pred", "(N, D, H, W)", 4, also="a Prediction or ")
+    _vol.label_tensor(reference, "reference", "(D, H, W)")
+    if tuple(reference.shape) != tuple(rows.shape[1:]):
+        raise ValueError(f"reference {tuple(reference.shape)} does not match the volumes {tuple(rows.shape[1:])} of pred")
+    if reference.device != rows.device:
+        raise ValueError("reference must be on the device of pred")
+    psets, rsets = _vol.region_set_pair(pred_regions, ref_regions)
+    for name, v, lo, hi in (("dilation", dilation, 0, 16), ("min_ref_voxels", min_ref_voxels, 0, None), ("min_pred_voxels", min_pred_voxels, 0, None),
+                            ("max_lesions", max_lesions, 1, 4096), ("max_links", max_links, 1, 16)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"{name} must be an int, not {v!r}")
+        if v < lo or (hi is not None and v > hi):
+            raise ValueError(f"{name} {v}: {lo} <= {name}" + (f" <= {hi}" if hi is not None else ""))
+    _vol.on_device(rows, "pred")
+    N, D, H, W = (int(d) for d in rows.shape)
+    R = len(psets)
+    L, dev = _ffi.lib(), rows.device
+    nbytes = L.uz_vol_lesion_scores_workspace(N, R, D, H, W, max_lesions)
+    if nbytes == 0:
+        raise _vol.refused("score_lesions", f"N {N} R {R} volume {D} x {H} x {W}; no empty axis, 1 <= N <= 65536, 1 <= R <= 8, N*D*H*W < 2^31")
+    rows, reference = rows.contiguous(), reference.contiguous()
+    ws = _vol.workspace("score_lesions", (dev, N, R, D, H, W, max_lesions), nbytes, dev)
+    scores = torch.empty(N, R, 4, dtype=torch.float64, device=dev)
+    counts = torch.empty(N, R, 8, dtype=torch.int64, device=dev)
+    lesions = torch.empty(N, R, max_lesions, 3, dtype=torch.int64, device=dev) if return_lesions else None
+    U32 = C.c_uint32 * R
+    _ffi.check(L.uz_vol_lesion_scores(rows.data_ptr(), N, U32(*psets), reference.data_ptr(), U32(*rsets), R, D, H, W, dilation, min_ref_voxels, min_pred_voxels,
+                                      max_lesions, max_links, ws.data_ptr(), counts.data_ptr(), lesions.data_ptr() if return_lesions else None,
+                                      scores.data_ptr(), _vol.stream(dev)), "vol_lesion_scores")
+    return LesionScores(lesion_dice=scores[..., 0], sensitivity=scores[..., 1], precision=scores[..., 2], f1=scores[..., 3], counts=counts, lesions=lesions)
+
+
 # --------------------------------------------------------------------------- S samples of one volume as an uncertainty estimate: filtered Dice, calibration
 UncertaintyScores = collections.namedtuple("UncertaintyScores", "table levels dice ftp ftn auc calibration votes")
 UncertaintyScores.__doc__ = """What score_uncertainty returns, all on the device, per region r: table (R, S+1, 2, 2) int64 = voxels with c of the S samples in
