@@ -54,16 +54,16 @@ def queries(L, c):
 
 CASES = [
     # ---- forward / data gradient: conv_split_ok, small_geo, tile_cot, split_parts (conv_split.hip) and the thin forward (conv_mfma.hip)
-    # W = 32 / 33: small_geo (conv_split.hip:837) - 16 x 16 tiles at grid 40 (split) against 16 x 32 tiles at grid 40 < min_grid (fp32)
+    # W = 32 / 33: small_geo (conv_split.hip) - 16 x 16 tiles at grid 40 (split) against 16 x 32 tiles at grid 40 < min_grid (fp32)
     R("fwd", 1, 20, 32, 32, 16, 32, 3, route=1, parts=1, cot=32, bn=40),                    # W = 32: 16 x 16 geometry, grid 40 = gmin16
     R("fwd", 1, 20, 32, 32, 16, 33, 3, route=0, parts=1, cot=32, bn=0),                     # W = 33: 16 x 32 geometry, grid 40 < min_grid, one-column ragged tile
     R("dgrad", 1, 20, 32, 32, 16, 32, 3, route=1, parts=1, cot=32, relu=40),                # the same boundary in the data gradient
     R("dgrad", 1, 20, 32, 32, 16, 33, 3, route=0, parts=1, cot=32, relu=0),
-    # H = 15 / 16: H < 16 (conv_split.hip:897, 16 x 32 tiles) and H >= 16 (conv_split.hip:901, 16 x 16 tiles)
+    # H = 15 / 16: conv_split_ok - H < 16 (16 x 32 tiles) and H >= 16 (16 x 16 tiles)
     R("fwd", 1, 16, 32, 64, 16, 128, 3, route=1, parts=1, cot=32, bn=128),                  # grid 64 = min_grid; cot 32 (Kc <= 32)
     R("fwd", 1, 16, 32, 64, 15, 128, 3, route=0, parts=1, cot=32, bn=0),
     R("fwd", 1, 20, 32, 32, 15, 32, 3, route=0, parts=1, cot=32, bn=0),
-    # Kc = 4 / 5 / 15 / 16 beside N H W = 262 143 / 262 144 (conv_split.hip:896-897, kcmin and the big-tensor clause)
+    # Kc = 4 / 5 / 15 / 16 beside N H W = 262 143 / 262 144 (conv_split_ok: kcmin and the big-tensor clause)
     R("fwd", 1, 16, 16, 32, 128, 128, 3, route=1, parts=1, cot=32, bn=1024),                # Kc = 16, 262 144 px
     R("fwd", 1, 1, 16, 32, 511, 513, 3, route=1, parts=1, cot=32, bn=1088),                 # Kc = 16, 262 143 px: dense chunk, no big-tensor clause needed
     R("fwd", 1, 16, 15, 32, 128, 128, 3, route=1, parts=1, cot=32, bn=1024),                # Kc = 15 (one chunk, K tail 15) at 262 144 px
@@ -72,31 +72,31 @@ CASES = [
     R("fwd", 1, 1, 5, 32, 511, 513, 3, route=0, parts=1, cot=32, bn=0),                     # Kc = 5 at 262 143 px
     R("dgrad", 1, 16, 32, 5, 128, 128, 3, route=1, parts=1, cot=32, relu=1024),             # data gradient Kc = Cout = 5
     R("dgrad", 1, 16, 32, 4, 128, 128, 3, route=0, parts=1, cot=32, relu=0),                # Kc = 4 < kcmin
-    # Mc = 31 / 32 below 262 144 px (conv_split.hip:897), and Mc = 31 beside it
+    # Mc = 31 / 32 below 262 144 px (conv_split_ok), and Mc = 31 beside it
     R("fwd", 1, 16, 32, 32, 16, 128, 3, route=1, parts=1, cot=32, bn=128),                  # grid 64
     R("fwd", 1, 16, 32, 31, 16, 128, 3, route=0, parts=1, cot=32, bn=0),
     R("fwd", 1, 16, 16, 31, 128, 128, 3, route=1, parts=1, cot=32, bn=1024),                # Mc = 31 at 262 144 px: a 32-wide tile one channel short
-    # 64-tile grid 63 / 64 (conv_split.hip:891 min_grid, :898-899)
+    # 64-tile grid 63 / 64 (conv_split_ok: min_grid)
     R("fwd", 1, 21, 32, 64, 16, 96, 3, route=0, parts=1, cot=32, bn=0),                     # grid 21 x 3 = 63
     R("fwd", 1, 32, 32, 64, 16, 64, 3, route=1, parts=1, cot=32, bn=128),                   # grid 32 x 2 = 64
-    # 16 x 16 grid 39 / 40 (conv_split.hip:905-906 gmin16)
+    # 16 x 16 grid 39 / 40 (conv_split_ok: gmin16)
     R("fwd", 1, 39, 32, 32, 16, 16, 3, route=0, parts=1, cot=32, bn=0),
     R("fwd", 1, 40, 32, 32, 16, 16, 3, route=1, parts=1, cot=32, bn=40),
     R("dgrad", 1, 39, 32, 32, 16, 16, 3, route=0, parts=1, cot=32, relu=0),
     R("dgrad", 1, 40, 32, 32, 16, 16, 3, route=1, parts=1, cot=32, relu=40),
-    # tile_cot (conv_split.hip:847-849): Kc 32 / 33 and Mc 32 / 33 on the 16 x 32 geometry; K tail of 1; overhang of 1 on the 64 tile
+    # tile_cot (conv_split.hip): Kc 32 / 33 and Mc 32 / 33 on the 16 x 32 geometry; K tail of 1; overhang of 1 on the 64 tile
     R("fwd", 1, 16, 33, 64, 16, 128, 3, route=1, parts=1, cot=64, bn=128),                  # cot 64, K tail of 1 channel
     R("fwd", 1, 16, 64, 32, 16, 128, 3, route=1, parts=1, cot=32, bn=128),                  # cot 32 (Mc <= 32)
     R("fwd", 1, 16, 64, 33, 16, 128, 3, route=1, parts=1, cot=64, bn=128),                  # cot 64 with 31 empty channels
     R("fwd", 1, 16, 64, 65, 16, 128, 3, route=1, parts=1, cot=64, bn=128),                  # two 64 tiles, the second overhangs by 1 channel
     R("dgrad", 1, 16, 65, 64, 16, 128, 3, route=1, parts=1, cot=64, relu=128),              # the same in the data gradient: Mc = Cin = 65
     R("fwd", 1, 16, 95, 64, 16, 128, 3, route=1, parts=1, cot=64, bn=128),                  # K tail of 15 channels
-    # ... in mode 3 the 128-channel tile from Mc = 65 on (conv_split.hip:849)
+    # ... in mode 3 the 128-channel tile from Mc = 65 on (tile_cot)
     R("fwd", 3, 16, 64, 64, 16, 128, 3, route=1, parts=1, cot=64, bn=128),
     R("fwd", 3, 16, 64, 65, 16, 128, 3, route=1, parts=1, cot=128, bn=128),                 # 128 tile overhanging by 63
     R("fwd", 3, 16, 64, 129, 16, 128, 3, route=1, parts=1, cot=128, bn=128),                # 128 tile overhanging by 1
     R("dgrad", 3, 16, 129, 64, 16, 128, 3, route=1, parts=1, cot=128, relu=128),
-    # split_parts (conv_split.hip:917-927): grid 159 / 160 (gmin), nChunks 5 / 6 (the nChunks / 3 cap), the S = 4 cap (smax)
+    # split_parts (conv_split.hip): grid 159 / 160 (gmin), nChunks 5 / 6 (the nChunks / 3 cap), the S = 4 cap (smax)
     R("fwd", 1, 159, 96, 32, 16, 16, 3, route=1, parts=2, cot=32, bn=0),                    # g = 159: S = 2 (6 chunks)
     R("fwd", 1, 160, 96, 32, 16, 16, 3, route=1, parts=1, cot=32, bn=160),                  # g = 160: unsplit
     R("dgrad", 1, 159, 32, 96, 16, 16, 3, route=1, parts=2, cot=32, relu=0),
@@ -106,7 +106,7 @@ CASES = [
     R("fwd", 1, 20, 192, 32, 16, 32, 3, route=1, parts=4, cot=32, bn=0),                    # 12 chunks: S = 4 by the nChunks / 3 cap
     R("fwd", 1, 20, 240, 32, 16, 32, 3, route=1, parts=4, cot=32, bn=0),                    # 15 chunks: S = 4 by the smax cap (nChunks / 3 = 5)
     R("fwd", 1, 20, 33, 33, 16, 32, 3, route=1, parts=1, cot=32, bn=40),                    # 32-channel tile overhanging by 1, K tail of 1
-    # thin forward (conv_mfma.hip:405-406, conv_wgrad.hip:603-604): Cin 4 / 5, N H W 65 535 / 65 536, Cout 256 / 257
+    # thin forward (conv_thin_ok, conv_mfma.hip): Cin 4 / 5, N H W 65 535 / 65 536, Cout 256 / 257
     R("fwd", 1, 4, 4, 32, 128, 128, 3, route=2, parts=1, cot=32, bn=0),
     R("fwd", 1, 4, 5, 32, 128, 128, 3, route=0, parts=1, cot=32, bn=0),
     R("fwd", 1, 5, 4, 32, 51, 257, 3, route=0, parts=1, cot=32, bn=0),                      # 65 535 px
@@ -129,21 +129,21 @@ CASES = [
     R("fwd", 3, 20, 33, 33, 16, 32, 3, route=1, parts=1, cot=32, bn=40),
     R("dgrad", 3, 20, 32, 32, 16, 33, 3, route=0, parts=1, cot=32, relu=0),
     R("fwd", 3, 16, 16, 32, 128, 128, 3, route=1, parts=1, cot=32, bn=1024),
-    # ---- weight gradient: wgrad_split_ok, chan_tile (conv_wgrad_split.hip), wgrad_thin_ok, pick_wgeom, uz_conv_route (conv_wgrad.hip)
-    # W = 16 / 24 / 32 / 48 / 64 (conv_wgrad_split.hip:1085 W % 32, W == 16)
+    # ---- weight gradient: wgrad_split_ok, chan_tile (conv_wgrad_split.hip), wgrad_thin_ok, pick_wgeom, wgrad_route (conv_wgrad.hip)
+    # W = 16 / 24 / 32 / 48 / 64 (wgrad_split_ok: W % 32, W == 16)
     R("wgrad", 1, 8, 64, 64, 16, 16, 3, route=1, slabs=16),                                 # 2 048 px = pxmin
     R("wgrad", 1, 8, 64, 64, 16, 24, 3, route=0, slabs=64),
     R("wgrad", 1, 8, 64, 64, 16, 32, 3, route=1, slabs=32),
     R("wgrad", 1, 8, 64, 64, 16, 48, 3, route=0, slabs=128),
     R("wgrad", 1, 8, 64, 64, 16, 64, 3, route=1, slabs=64),
-    # H = 15 / 16 (conv_wgrad_split.hip:1087)
+    # H = 15 / 16 (wgrad_split_ok)
     R("wgrad", 1, 8, 64, 64, 15, 32, 3, route=0, slabs=64),
-    # Cin, Cout 63 / 64 at 2 032 / 2 048 px (conv_wgrad_split.hip:1095, 1097: pixel counts of 16-wide rows are multiples of 16, so 2 047 cannot be formed)
+    # Cin, Cout 63 / 64 at 2 032 / 2 048 px (wgrad_split_ok: pixel counts of 16-wide rows are multiples of 16, so 2 047 cannot be formed)
     R("wgrad", 1, 1, 64, 64, 128, 16, 3, route=1, slabs=16),
     R("wgrad", 1, 1, 64, 64, 127, 16, 3, route=0, slabs=32),
     R("wgrad", 1, 1, 63, 64, 128, 16, 3, route=0, slabs=32),
     R("wgrad", 1, 1, 64, 63, 128, 16, 3, route=0, slabs=32),
-    # narrow side 15 / 16 / 32 / 33 beside 131 072 px (conv_wgrad_split.hip:1097), 131 040 px below it
+    # narrow side 15 / 16 / 32 / 33 beside 131 072 px (wgrad_split_ok), 131 040 px below it
     R("wgrad", 1, 8, 16, 64, 128, 128, 3, route=1, slabs=128),
     R("wgrad", 1, 8, 15, 64, 128, 128, 3, route=0, slabs=512),
     R("wgrad", 1, 8, 32, 64, 128, 128, 3, route=1, slabs=128),
@@ -153,13 +153,13 @@ CASES = [
     R("wgrad", 1, 32, 32, 5, 128, 128, 3, route=1, slabs=256),
     R("wgrad", 1, 32, 32, 4, 128, 128, 3, route=0, slabs=512),
     R("wgrad", 1, 129, 32, 5, 127, 32, 3, route=0, slabs=459),                              # 524 256 px, ragged H (127 rows)
-    # chan_tile 32 / 33 (conv_wgrad_split.hip:1101; forced split: the default policy never pairs a 33-channel side with the 64 tile)
+    # chan_tile 32 / 33 (conv_wgrad_split.hip; forced split: the default policy never pairs a 33-channel side with the 64 tile)
     R("wgrad", 2, 32, 32, 64, 32, 32, 3, route=1, slabs=85),
     R("wgrad", 2, 32, 33, 64, 32, 32, 3, route=1, slabs=128),
     # ragged H (rows per 128-pixel tile: 4 at W = 32, 8 at W = 16)
     R("wgrad", 1, 8, 64, 64, 18, 32, 3, route=1, slabs=40),
     R("wgrad", 1, 8, 64, 96, 17, 16, 3, route=1, slabs=24),
-    # fp32 path (pick_wgeom, conv_wgrad.hip:524-553): pow2_ceil tile widths, the 128-pixel fast tile, batch tiles, ks = 1
+    # fp32 path (pick_wgeom, conv_wgrad.hip): pow2_ceil tile widths, the 128-pixel fast tile, batch tiles, ks = 1
     R("wgrad", 0, 3, 20, 24, 5, 1, 3, route=0, slabs=4),                                    # TW = 1: the pixel pair of an MFMA step is two rows of one image
     R("wgrad", 0, 2, 8, 8, 1, 1, 3, route=0, slabs=4),                                      # TW = TH = 1: ... two images
     R("wgrad", 0, 3, 20, 24, 5, 3, 3, route=0, slabs=8),
@@ -177,7 +177,7 @@ CASES = [
     R("wgrad", 0, 2, 38, 32, 16, 16, 1, route=0, slabs=32),                                 # 1 x 1 kernel
     R("wgrad", 1, 2, 38, 32, 16, 16, 1, route=0, slabs=32),
     R("wgrad", 0, 8, 64, 64, 16, 32, 3, route=0, slabs=64),                                 # a split-path shape on the fp32 kernel
-    # thin path (conv_wgrad.hip:516-517): Cin 4 / 5, H even / odd (THIN_ROWS), W = 128 / 160 (THIN_WMAX), 65 536 / 65 280 px
+    # thin path (wgrad_thin_ok, conv_wgrad.hip): Cin 4 / 5, H even / odd (THIN_ROWS), W = 128 / 160 (THIN_WMAX), 65 536 / 65 280 px
     R("wgrad", 1, 4, 4, 32, 128, 128, 3, route=2, slabs=256),
     R("wgrad", 1, 4, 5, 32, 128, 128, 3, route=0, slabs=512),
     R("wgrad", 1, 4, 4, 32, 127, 128, 3, route=0, slabs=512),
@@ -188,7 +188,7 @@ CASES = [
     R("wgrad", 3, 8, 64, 64, 16, 32, 3, route=1, slabs=32),
     R("wgrad", 3, 8, 16, 64, 128, 128, 3, route=1, slabs=128),
     R("wgrad", 3, 8, 64, 96, 17, 16, 3, route=1, slabs=24),
-    # pick_wgeom's huge branch (conv_wgrad.hip:551): 2^30 elements in one operand take the generic 64-bit kernel (query only: too big for an fp64 reference)
+    # pick_wgeom's huge branch (wgrad_huge): 2^30 elements in one operand take the generic 64-bit kernel (query only: too big for an fp64 reference)
     R("wgrad", 0, 256, 256, 32, 128, 128, 3, gpu=False, route=0, slabs=256),
     R("wgrad", 0, 256, 255, 32, 128, 128, 3, gpu=False, route=0, slabs=128),
     # CONV_CASES of tests/test_ops_gpu.py whose comments name a route

@@ -321,7 +321,7 @@ inline bool conv_thin_ok(int Cin, int Cout, int N, int H, int W, int ks) {
     return ks == 3 && Cin <= 4 && Cout <= 256 && (long long)N * H * W >= 64 * 1024 && N <= 65535;
 }
 
-struct Geom { int TW, TH, TB, PW, PSI, PS, tilesX, tilesY, tilesB; };
+using uz::Geom;
 
 // Split the input-channel loop over several workgroups when the output grid alone cannot fill the
 // 256 CUs (deep, small-resolution levels: 2x2 ... 16x16 pixels).  Small cost model: MFMA time of the
@@ -405,150 +405,159 @@ int splitk_reduce(const float* slab, int ksplit, const float* bias, float* y, in
     return check_launch("conv_splitk_reduce");
 }
 
-// x: input view (Kc channels), y: output view (Mc channels); w = PyTorch [Cout][Cin][ks][ks] parameter.
-size_t conv_workspace(int Kc, int Mc, int N, int H, int W, int ks, int dgrad) {
-    if (conv_split_ok(Kc, Mc, N, H, W, ks, dgrad)) return conv_split_workspace(Kc, Mc, N, H, W);
-    const Geom g = pick_geom(N, H, W, ks / 2);
-    const int cot = 32 * pick_msub(Mc, (long long)g.tilesX * g.tilesY * g.tilesB, ceil_div(Kc, CK));
-    int ksplit, cps;
-    pick_split((long long)g.tilesX * g.tilesY * g.tilesB * ceil_div(Mc, cot), ceil_div(Kc, CK), cot / 32, ks * ks,
-               (double)N * Mc * H * W * sizeof(float), ksplit, cps);
-    return ksplit > 1 ? (size_t)ksplit * N * Mc * H * W * sizeof(float) : 0;
-}
-
-// slabs_only: stop after the split-K main kernel and leave the partial sums [ksplit][N][Mc][HW] at the start of the workspace
-// (the caller's BatchNorm adds them, uz_bn_relu_fwd_slabs); only legal where conv_splitk_parts() > 1.
-static int conv_mfma_impl(const float* x, int Kc, int KcTot, const float* w, int wCi, const float* bias,
-              float* y, int Mc, int McTot, int N, int H, int W, int ks, int dgrad, int relu, int accumulate,
-              const float* x_amax, const float* w_amax, float* y_amax,
-              void* workspace, size_t workspace_bytes, const void* packed_w, float* bn_partials, hipStream_t st, bool slabs_only,
-              float* slabs_out = nullptr);
-int conv_mfma(const float* x, int Kc, int KcTot, const float* w, int wCi, const float* bias,
-              float* y, int Mc, int McTot, int N, int H, int W, int ks, int dgrad, int relu, int accumulate,
-              const float* x_amax, const float* w_amax, float* y_amax,
-              void* workspace, size_t workspace_bytes, const void* packed_w, float* bn_partials, hipStream_t st) {
-    return conv_mfma_impl(x, Kc, KcTot, w, wCi, bias, y, Mc, McTot, N, H, W, ks, dgrad, relu, accumulate, x_amax, w_amax, y_amax,
-                          workspace, workspace_bytes, packed_w, bn_partials, st, false);
-}
-// split count of the fp32 forward kernel for this shape when it is given its workspace (1: unsplit, or another kernel family)
-int conv_splitk_parts(int Kc, int Mc, int N, int H, int W, int ks) {
-    if (conv_split_ok(Kc, Mc, N, H, W, ks, 0)) return 1;
-    const Geom g = pick_geom(N, H, W, ks / 2);
+// the fp32 MFMA kernel's part of a route
+static ConvRoute f32_route(int Kc, int Mc, int N, int H, int W, int ks) {
+    ConvRoute r;
+    const Geom& g = r.g = pick_geom(N, H, W, ks / 2);
     const long long tiles = (long long)g.tilesX * g.tilesY * g.tilesB;
-    const int msub = pick_msub(Mc, tiles, ceil_div(Kc, CK));
-    int ksplit, cps;
-    pick_split(tiles * ceil_div(Mc, 32 * msub), ceil_div(Kc, CK), msub, ks * ks, (double)N * Mc * H * W * sizeof(float), ksplit, cps);
-    return ksplit;
+    const int nChunks = ceil_div(Kc, CK), kk = ks * ks;
+    r.msub = pick_msub(Mc, tiles, nChunks);
+    const int cot = 32 * r.msub;
+    r.jmax = g.PS <= 512 ? 2 : 4;
+    r.smem = 2 * (size_t)(kk * CK * (cot + 1) + CK * r.jmax * 256) * sizeof(float);
+    pick_split(tiles * ceil_div(Mc, cot), nChunks, r.msub, kk, (double)N * Mc * H * W * sizeof(float), r.ksplit, r.cps);
+    r.ws_bytes = r.ksplit > 1 ? (size_t)r.ksplit * N * Mc * H * W * sizeof(float) : 0;
+    return r;
 }
-static int conv_mfma_impl(const float* x, int Kc, int KcTot, const float* w, int wCi, const float* bias,
-              float* y, int Mc, int McTot, int N, int H, int W, int ks, int dgrad, int relu, int accumulate,
-              const float* x_amax, const float* w_amax, float* y_amax,
-              void* workspace, size_t workspace_bytes, const void* packed_w, float* bn_partials, hipStream_t st, bool slabs_only,
-              float* slabs_out) {
-    UZ_REQUIRE(ks == 1 || ks == 3, "conv: kernel size %d unsupported (1 or 3)", ks);
-    UZ_REQUIRE(N > 0 && H > 0 && W > 0 && Kc > 0 && Mc > 0, "conv: empty tensor");
-    UZ_REQUIRE(H <= 4096 && W <= 4096, "conv: spatial size too large");
+// The families in the order every call and every query asks: 1x1 head, thin input (forward only), matrix pipe, fp32.
+ConvRoute conv_route(int dgrad, int Kc, int Mc, int N, int H, int W, int ks, bool streaming) {
+    ConvRoute r;
+    r.family = CONV_STREAM;
+    // heads with 1, 2, 3, 4, 6 or 8 outputs, Cin <= 512 (conv1x1_small_ok): streaming VALU kernel
+    if (streaming && ks == 1 && (dgrad ? conv1x1_small_ok(Mc, Kc) : conv1x1_small_ok(Kc, Mc))) { r.stream = STREAM_HEAD; return r; }
+    // 1..4 input channels at full resolution: streaming kernel
+    if (streaming && !dgrad && conv_thin_ok(Kc, Mc, N, H, W, ks)) { r.stream = STREAM_THIN; return r; }
     // large 3x3 layers: split-bf16 matrix pipe (conv_split.hip); its packed weight image lives in the workspace
-    UZ_REQUIRE(!slabs_only || !conv_split_ok(Kc, Mc, N, H, W, ks, dgrad), "conv_*_slabs: this shape does not run the split-K fp32 kernel");
-    if (conv_split_ok(Kc, Mc, N, H, W, ks, dgrad) && workspace && workspace_bytes >= conv_split_workspace(Kc, Mc, N, H, W))
-        return conv_split(x, Kc, KcTot, w, wCi, bias, y, Mc, McTot, N, H, W, dgrad, relu, accumulate, x_amax, w_amax, y_amax, workspace, packed_w, bn_partials, st);
-    UZ_REQUIRE(!packed_w, "conv: a pre-packed weight image was supplied for a layer that does not take the split path");
-    UZ_REQUIRE(!bn_partials, "conv: fused BatchNorm statistics were requested for a layer that does not take the split path (uz_conv_bn_partials() == 0)");
-    const Geom g = pick_geom(N, H, W, ks / 2);
+    if (!conv_split_ok(Kc, Mc, N, H, W, ks, dgrad)) return f32_route(Kc, Mc, N, H, W, ks);
+    r.family = CONV_SPLIT;
+    r.s = split_geom(Kc, Mc, N, H, W);
+    r.ws_bytes = r.s.ws_bytes;
+    return r;
+}
+namespace {
+// x: input view (Kc channels), y: output view (Mc channels); w = PyTorch [Cout][Cin][ks][ks] parameter.
+int conv_f32(const ConvCall& c, const ConvRoute& r) {
+    const Geom& g = r.g;
+    const int N = c.N, H = c.H, W = c.W, Kc = c.Kc, Mc = c.Mc;
+    UZ_REQUIRE(!c.packed_w, "conv: a pre-packed weight image was supplied for a layer that does not take the split path");
+    UZ_REQUIRE(!c.bn_partials, "conv: fused BatchNorm statistics were requested for a layer that does not take the split path (uz_conv_bn_partials() == 0)");
     ConvP p;
-    p.x = x; p.w = w; p.bias = bias; p.y = y;
+    p.x = c.x; p.w = c.w; p.bias = c.bias; p.y = c.y;
     p.N = N; p.H = H; p.W = W; p.HW = H * W;
-    p.Cin = Kc; p.CinTot = KcTot; p.Cout = Mc; p.CoutTot = McTot; p.wCi = wCi; p.wCo = dgrad ? Kc : Mc;
+    p.Cin = Kc; p.CinTot = c.KcTot; p.Cout = Mc; p.CoutTot = c.McTot; p.wCi = c.wCi; p.wCo = c.dgrad ? Kc : Mc;
     p.TW = g.TW; p.TH = g.TH; p.TB = g.TB; p.lgTW = ilog2(g.TW); p.lgTH = ilog2(g.TH);
     p.tilesX = g.tilesX; p.tilesY = g.tilesY;
     p.PW = g.PW; p.PSI = g.PSI; p.PS = g.PS;
-    p.relu = relu; p.accumulate = accumulate; p.y_amax = y_amax;
-    const int msub = pick_msub(Mc, (long long)g.tilesX * g.tilesY * g.tilesB, ceil_div(Kc, CK));
-    const int cot = 32 * msub;
-    p.nCoTiles = ceil_div(Mc, cot);
-    const int jmax = g.PS <= 512 ? 2 : 4;
-    const int kk = ks * ks;
-    const size_t smem = 2 * (size_t)(kk * CK * (cot + 1) + CK * jmax * 256) * sizeof(float);
-    const long long base_grid = (long long)g.tilesX * g.tilesY * g.tilesB * p.nCoTiles;
-    pick_split(base_grid, ceil_div(Kc, CK), msub, kk, (double)N * Mc * H * W * sizeof(float), p.ksplit, p.cps);
-    const size_t need = p.ksplit > 1 ? (size_t)p.ksplit * N * Mc * H * W * sizeof(float) : 0;
-    if (p.ksplit > 1 && !slabs_out && (!workspace || workspace_bytes < need)) { p.ksplit = 1; p.cps = ceil_div(Kc, CK); }   // no workspace: stay unsplit
-    UZ_REQUIRE(!slabs_only || p.ksplit > 1, "conv_fwd_slabs: the chunk loop of this shape is not split (uz_conv_splitk_parts() == 1) or the workspace is too small");
-    p.slab = slabs_out ? slabs_out : static_cast<float*>(workspace);
+    p.relu = c.relu; p.accumulate = c.accumulate; p.y_amax = c.y_amax;
+    p.nCoTiles = ceil_div(Mc, 32 * r.msub);
+    p.ksplit = r.ksplit; p.cps = r.cps;
+    if (p.ksplit > 1 && !c.slabs_out && (!c.workspace || c.workspace_bytes < r.ws_bytes)) { p.ksplit = 1; p.cps = ceil_div(Kc, CK); }   // no workspace: stay unsplit
+    UZ_REQUIRE(!c.slabs_only || p.ksplit > 1, "conv_fwd_slabs: the chunk loop of this shape is not split (uz_conv_splitk_parts() == 1) or the workspace is too small");
+    p.slab = c.slabs_out ? c.slabs_out : static_cast<float*>(c.workspace);
     if (p.ksplit > 1) p.y_amax = nullptr;               // split-K: the reduce kernel sees the final values
-    const long long grid = base_grid * p.ksplit;
+    const long long grid = (long long)g.tilesX * g.tilesY * g.tilesB * p.nCoTiles * p.ksplit;
     UZ_REQUIRE(grid < (1ll << 31), "conv: grid too large");
     int rc;
-    if (ks == 3) rc = dgrad ? launch_ks<3, true>(p, msub, jmax, (int)grid, smem, st) : launch_ks<3, false>(p, msub, jmax, (int)grid, smem, st);
-    else rc = dgrad ? launch_ks<1, true>(p, msub, jmax, (int)grid, smem, st) : launch_ks<1, false>(p, msub, jmax, (int)grid, smem, st);
-    if (rc || p.ksplit == 1 || slabs_only) return rc;
-    return splitk_reduce(p.slab, p.ksplit, bias, y, Mc, McTot, N, H * W, relu, accumulate, y_amax, st);
+    if (c.ks == 3) rc = c.dgrad ? launch_ks<3, true>(p, r.msub, r.jmax, (int)grid, r.smem, c.st) : launch_ks<3, false>(p, r.msub, r.jmax, (int)grid, r.smem, c.st);
+    else rc = c.dgrad ? launch_ks<1, true>(p, r.msub, r.jmax, (int)grid, r.smem, c.st) : launch_ks<1, false>(p, r.msub, r.jmax, (int)grid, r.smem, c.st);
+    if (rc || p.ksplit == 1 || c.slabs_only) return rc;
+    return splitk_reduce(p.slab, p.ksplit, c.bias, c.y, Mc, c.McTot, N, H * W, c.relu, c.accumulate, c.y_amax, c.st);
 }
+int conv_thin(const ConvCall& c) {
+    const dim3 grid(ceil_div(c.H * c.W, 256), c.N);
+    const size_t smem = (size_t)(c.Mc * c.Kc * 9 + c.Mc) * sizeof(float);
+    static const decltype(&conv_thin_fwd_kernel<1>) kern[] = {conv_thin_fwd_kernel<1>, conv_thin_fwd_kernel<2>, conv_thin_fwd_kernel<3>, conv_thin_fwd_kernel<4>};
+    hipLaunchKernelGGL(kern[c.Kc >= 1 && c.Kc <= 3 ? c.Kc - 1 : 3], grid, dim3(256), smem, c.st, c.x, c.KcTot, c.w, c.bias, c.y, c.Mc, c.McTot, c.H, c.W, c.relu, c.y_amax);
+    return check_launch("conv_thin_fwd_kernel");
+}
+int conv_launch(const ConvCall& c, ConvRoute r) {
+    if (r.stream == STREAM_HEAD)
+        return c.dgrad ? conv1x1_small_bwd_data(c.x, c.Kc, c.KcTot, c.w, c.y, c.Mc, c.McTot, c.N, c.H, c.W, c.accumulate, c.st)
+                       : conv1x1_small_fwd(c.x, c.Kc, c.KcTot, c.w, c.bias, c.y, c.Mc, c.McTot, c.N, c.H, c.W, c.st);
+    if (r.stream == STREAM_THIN) return conv_thin(c);
+    UZ_REQUIRE(c.ks == 1 || c.ks == 3, "conv: kernel size %d unsupported (1 or 3)", c.ks);
+    UZ_REQUIRE(c.N > 0 && c.H > 0 && c.W > 0 && c.Kc > 0 && c.Mc > 0, "conv: empty tensor");
+    UZ_REQUIRE(c.H <= 4096 && c.W <= 4096, "conv: spatial size too large");
+    UZ_REQUIRE(!c.slabs_only || r.family != CONV_SPLIT, "conv_*_slabs: this shape does not run the split-K fp32 kernel");
+    if (r.family == CONV_SPLIT) {
+        if (c.workspace && c.workspace_bytes >= r.ws_bytes) return conv_split(c, r);
+        r = f32_route(c.Kc, c.Mc, c.N, c.H, c.W, c.ks);          // without its workspace a split-eligible call runs the fp32 kernel
+    }
+    return conv_f32(c, r);
+}
+}  // namespace
 
 }  // namespace uz
 
-extern "C" int uz_conv_splitk_parts(int Cin, int Cout, int N, int H, int W, int ks) {
-    if ((ks != 1 && ks != 3) || Cin <= 0 || Cout <= 0 || N <= 0 || H <= 0 || W <= 0) return 1;
-    if (ks == 1 && uz::conv1x1_small_ok(Cin, Cout)) return 1;
-    if (conv_thin_ok(Cin, Cout, N, H, W, ks)) return 1;
-    return uz::conv_splitk_parts(Cin, Cout, N, H, W, ks);
+using uz::ConvCall; using uz::ConvRoute; using uz::conv_route;
+// the route of a forward call (kind 0) or of a data gradient (1) in the layer's terms
+static ConvRoute layer_route(int kind, int Cin, int Cout, int N, int H, int W, int ks, bool streaming = true) {
+    return kind == 1 ? conv_route(1, Cout, Cin, N, H, W, ks, streaming) : conv_route(0, Cin, Cout, N, H, W, ks, streaming);
 }
+// the forward / data-gradient call of a layer: operand views, dims, bounds, workspace; the entry points add their options by name
+static ConvCall fwd_call(const float* x, int Cin, int CinTot, const float* w, const float* bias, float* y, int Cout, int CoutTot, int N, int H, int W, int ks,
+                         const float* x_amax, const float* w_amax, float* y_amax, void* workspace, size_t workspace_bytes, const void* packed_w, float* bn_partials, void* stream) {
+    ConvCall c;
+    c.x = x; c.Kc = Cin; c.KcTot = CinTot; c.w = w; c.wCi = Cin; c.bias = bias; c.y = y; c.Mc = Cout; c.McTot = CoutTot;
+    c.N = N; c.H = H; c.W = W; c.ks = ks; c.x_amax = x_amax; c.w_amax = w_amax; c.y_amax = y_amax;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.packed_w = packed_w; c.bn_partials = bn_partials; c.st = uz::S(stream);
+    return c;
+}
+static ConvCall dgrad_call(const float* dy, int Cout, int CoutTot, const float* w, float* dx, int Cin, int CinTot, int N, int H, int W, int ks, int accumulate,
+                           const float* dy_amax, const float* w_amax, void* workspace, size_t workspace_bytes, const void* packed_w, void* stream) {
+    ConvCall c = fwd_call(dy, Cout, CoutTot, w, nullptr, dx, Cin, CinTot, N, H, W, ks, dy_amax, w_amax, nullptr, workspace, workspace_bytes, packed_w, nullptr, stream);
+    c.wCi = Cin; c.dgrad = 1; c.accumulate = accumulate;
+    return c;
+}
+// Which kernel family a convolution call takes under the current math mode (diagnostics / roofline bookkeeping):
+// kind 0 = forward, 1 = data gradient, 2 = weight gradient; returns 0 fp32 MFMA, 1 split-fp16 MFMA, 2 streaming VALU (1x1 heads, thin inputs).
+extern "C" int uz_conv_route(int kind, int Cin, int Cout, int N, int H, int W, int ks) {
+    if (kind == 0 || kind == 1) return layer_route(kind, Cin, Cout, N, H, W, ks).family;
+    const uz::WgradRoute r = uz::wgrad_route(Cin, Cout, Cin, Cout, N, H, W, ks);
+    return r.family < uz::WG_SPLIT ? uz::CONV_STREAM : r.split_eligible ? uz::CONV_SPLIT : uz::CONV_F32;
+}
+// split count of the fp32 kernel for this shape when it is given its workspace (1: unsplit, or another kernel family)
+static int splitk_parts(const ConvRoute& r, int Cin, int Cout, int N, int H, int W, int ks) {
+    return (ks == 1 || ks == 3) && Cin > 0 && Cout > 0 && N > 0 && H > 0 && W > 0 && r.family == uz::CONV_F32 ? r.ksplit : 1;
+}
+extern "C" int uz_conv_splitk_parts(int Cin, int Cout, int N, int H, int W, int ks) { return splitk_parts(layer_route(0, Cin, Cout, N, H, W, ks), Cin, Cout, N, H, W, ks); }
 extern "C" int uz_conv_fwd_slabs(const float* x, int Cin, int CinTot, const float* w, int Cout, int N, int H, int W, int ks,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    UZ_REQUIRE(uz_conv_splitk_parts(Cin, Cout, N, H, W, ks) > 1, "conv_fwd_slabs: uz_conv_splitk_parts() == 1 for this shape");
-    return uz::conv_mfma_impl(x, Cin, CinTot, w, Cin, nullptr, nullptr, Cout, Cout, N, H, W, ks, 0, 0, 0, nullptr, nullptr, nullptr,
-                              workspace, workspace_bytes, nullptr, nullptr, uz::S(stream), true);
+    const ConvRoute r = layer_route(0, Cin, Cout, N, H, W, ks);
+    UZ_REQUIRE(splitk_parts(r, Cin, Cout, N, H, W, ks) > 1, "conv_fwd_slabs: uz_conv_splitk_parts() == 1 for this shape");
+    ConvCall c = fwd_call(x, Cin, CinTot, w, nullptr, nullptr, Cout, Cout, N, H, W, ks, nullptr, nullptr, nullptr, workspace, workspace_bytes, nullptr, nullptr, stream);
+    c.slabs_only = true;
+    return uz::conv_launch(c, r);
 }
 
 // The same for the data gradient of the small planes (round 4): where uz_conv_bwd_splitk_parts() > 1 the call may stop behind its
 // main kernel and leave the partial sums [parts][N][Cin][H*W] in slabs_out; the BatchNorm backward of the unit that produced the
 // convolution's input adds them itself (uz_bn_relu_bwd_ex, da_slabs) instead of reading dA - one reduction launch less on the
 // backward chains of the 8 x 8 ... 2 x 2 levels, same values (slab order).
-extern "C" int uz_conv_bwd_splitk_parts(int Cin, int Cout, int N, int H, int W, int ks) {
-    if ((ks != 1 && ks != 3) || Cin <= 0 || Cout <= 0 || N <= 0 || H <= 0 || W <= 0) return 1;
-    if (ks == 1 && uz::conv1x1_small_ok(Cin, Cout)) return 1;
-    if (uz::conv_split_ok(Cout, Cin, N, H, W, ks, 1)) return 1;
-    const Geom g = pick_geom(N, H, W, ks / 2);
-    const long long tiles = (long long)g.tilesX * g.tilesY * g.tilesB;
-    const int msub = pick_msub(Cin, tiles, uz::ceil_div(Cout, CK));
-    int ksplit, cps;
-    pick_split(tiles * uz::ceil_div(Cin, 32 * msub), uz::ceil_div(Cout, CK), msub, ks * ks, (double)N * Cin * H * W * sizeof(float), ksplit, cps);
-    return ksplit;
-}
+extern "C" int uz_conv_bwd_splitk_parts(int Cin, int Cout, int N, int H, int W, int ks) { return splitk_parts(layer_route(1, Cin, Cout, N, H, W, ks), Cin, Cout, N, H, W, ks); }
 extern "C" int uz_conv_bwd_data_slabs(const float* dy, int Cout, int CoutTot, const float* w, int Cin, int N, int H, int W, int ks,
                                       float* slabs_out, void* stream) {
-    UZ_REQUIRE(slabs_out && uz_conv_bwd_splitk_parts(Cin, Cout, N, H, W, ks) > 1, "conv_bwd_data_slabs: uz_conv_bwd_splitk_parts() == 1 for this shape");
-    return uz::conv_mfma_impl(dy, Cout, CoutTot, w, Cin, nullptr, nullptr, Cin, Cin, N, H, W, ks, 1, 0, 0, nullptr, nullptr, nullptr,
-                              nullptr, 0, nullptr, nullptr, uz::S(stream), true, slabs_out);
+    const ConvRoute r = layer_route(1, Cin, Cout, N, H, W, ks);
+    UZ_REQUIRE(slabs_out && splitk_parts(r, Cin, Cout, N, H, W, ks) > 1, "conv_bwd_data_slabs: uz_conv_bwd_splitk_parts() == 1 for this shape");
+    ConvCall c = dgrad_call(dy, Cout, CoutTot, w, nullptr, Cin, Cin, N, H, W, ks, 0, nullptr, nullptr, nullptr, 0, nullptr, stream);
+    c.slabs_out = slabs_out; c.slabs_only = true;
+    return uz::conv_launch(c, r);
 }
 
+// sized for the matrix kernels of both directions: a call with a packed weight image or a ReLU epilogue stays on them
 extern "C" size_t uz_conv_workspace(int Cin, int Cout, int N, int H, int W, int ks) {
-    const size_t a = uz::conv_workspace(Cin, Cout, N, H, W, ks, 0), b = uz::conv_workspace(Cout, Cin, N, H, W, ks, 1);
-    return a > b ? a : b;
+    return std::max(layer_route(0, Cin, Cout, N, H, W, ks, false).ws_bytes, layer_route(1, Cin, Cout, N, H, W, ks, false).ws_bytes);
 }
 
-extern "C" int uz_conv_bn_partials(int Cin, int Cout, int N, int H, int W, int ks) {
-    if (ks != 3 || conv_thin_ok(Cin, Cout, N, H, W, ks)) return 0;
-    return uz::conv_split_bn_partials(Cin, Cout, N, H, W);
-}
+// rows of statistics partials a forward call with fused BatchNorm statistics writes / of bias-gradient partials a data gradient with
+// the folded ReLU backward writes (0: the call is off the matrix pipe, or its chunk loop is split over workgroups)
+static int split_partials(const ConvRoute& r) { return r.family == uz::CONV_SPLIT ? r.s.partials : 0; }
+extern "C" int uz_conv_bn_partials(int Cin, int Cout, int N, int H, int W, int ks) { return split_partials(layer_route(0, Cin, Cout, N, H, W, ks)); }
 extern "C" int uz_conv_fwd_bnstats(const float* x, int Cin, int CinTot, const float* w, const float* bias,
                                    float* y, int Cout, int CoutTot, int N, int H, int W, int ks, int relu,
                                    const float* x_amax, const float* w_amax, float* y_amax,
                                    void* workspace, size_t workspace_bytes, const void* packed_w, float* bn_partials, void* stream) {
-    UZ_REQUIRE(!bn_partials || uz_conv_bn_partials(Cin, Cout, N, H, W, ks) > 0, "conv_fwd_bnstats: this shape writes no fused statistics (uz_conv_bn_partials() == 0)");
-    if (ks == 1 && !relu && uz::conv1x1_small_ok(Cin, Cout)) {        // heads with 1, 2, 3, 4, 6 or 8 outputs, Cin <= 512 (conv1x1_small_ok): streaming VALU kernel; -2 cannot come back behind that check
-        const int rc = uz::conv1x1_small_fwd(x, Cin, CinTot, w, bias, y, Cout, CoutTot, N, H, W, uz::S(stream));
-        if (rc != -2) return rc;
-    }
-    if (conv_thin_ok(Cin, Cout, N, H, W, ks) && !packed_w) {           // 1..4 input channels at full resolution: streaming kernel
-        const dim3 grid(uz::ceil_div(H * W, 256), N);
-        const size_t smem = (size_t)(Cout * Cin * 9 + Cout) * sizeof(float);
-#define UZ_THINF(C_) hipLaunchKernelGGL(conv_thin_fwd_kernel<C_>, grid, dim3(256), smem, uz::S(stream), x, CinTot, w, bias, y, Cout, CoutTot, H, W, relu, y_amax)
-        if (Cin == 1) UZ_THINF(1); else if (Cin == 2) UZ_THINF(2); else if (Cin == 3) UZ_THINF(3); else UZ_THINF(4);
-#undef UZ_THINF
-        return uz::check_launch("conv_thin_fwd_kernel");
-    }
-    return uz::conv_mfma(x, Cin, CinTot, w, Cin, bias, y, Cout, CoutTot, N, H, W, ks, 0, relu, 0, x_amax, w_amax, y_amax, workspace, workspace_bytes, packed_w, bn_partials, uz::S(stream));
+    return uz_conv_fwd_ex(x, Cin, CinTot, w, bias, y, Cout, CoutTot, N, H, W, ks, relu, x_amax, w_amax, y_amax, workspace, workspace_bytes, packed_w, bn_partials, 0, nullptr, 0, stream);
 }
 extern "C" int uz_conv_fwd_packed(const float* x, int Cin, int CinTot, const float* w, const float* bias,
                                   float* y, int Cout, int CoutTot, int N, int H, int W, int ks, int relu,
@@ -570,14 +579,19 @@ extern "C" int uz_conv_fwd_ex(const float* x, int Cin, int CinTot, const float* 
                               const float* x_amax, const float* w_amax, float* y_amax,
                               void* workspace, size_t workspace_bytes, const void* packed_w, float* bn_partials,
                               int x_packed, const float* x_amax2, int seg_channels, void* stream) {
-    if (!x_packed)
-        return uz_conv_fwd_bnstats(x, Cin, CinTot, w, bias, y, Cout, CoutTot, N, H, W, ks, relu, x_amax, w_amax, y_amax, workspace, workspace_bytes, packed_w, bn_partials, stream);
-    UZ_REQUIRE(ks == 3 && uz_conv_route(0, Cin, Cout, N, H, W, ks) == 1 && uz::conv_np() == 2, "conv_fwd_ex: input in split storage, but this shape / math mode does not take the split-fp16 path");
-    UZ_REQUIRE(workspace && workspace_bytes >= uz::conv_split_workspace(Cin, Cout, N, H, W), "conv_fwd_ex: workspace too small");
-    UZ_REQUIRE(!bn_partials || uz_conv_bn_partials(Cin, Cout, N, H, W, ks) > 0, "conv_fwd_ex: this shape writes no fused statistics (uz_conv_bn_partials() == 0)");
-    uz::SplitOpts o;
-    o.x_packed = 1; o.x_amax2 = x_amax2; o.seg_channels = seg_channels;
-    return uz::conv_split_ex(x, Cin, CinTot, w, Cin, bias, y, Cout, CoutTot, N, H, W, 0, relu, 0, x_amax, w_amax, y_amax, workspace, packed_w, bn_partials, uz::S(stream), o);
+    ConvRoute r = layer_route(0, Cin, Cout, N, H, W, ks);
+    ConvCall c = fwd_call(x, Cin, CinTot, w, bias, y, Cout, CoutTot, N, H, W, ks, x_amax, w_amax, y_amax, workspace, workspace_bytes, packed_w, bn_partials, stream);
+    c.relu = relu; c.x_packed = x_packed != 0; c.x_amax2 = x_amax2; c.seg_channels = seg_channels;
+    if (!x_packed) {
+        UZ_REQUIRE(!bn_partials || split_partials(r) > 0, "conv_fwd_bnstats: this shape writes no fused statistics (uz_conv_bn_partials() == 0)");
+        // the head kernels have no ReLU epilogue; a pre-packed weight image keeps a thin-input layer on the matrix kernels
+        if ((r.stream == uz::STREAM_HEAD && relu) || (r.stream == uz::STREAM_THIN && packed_w)) r = layer_route(0, Cin, Cout, N, H, W, ks, false);
+        return uz::conv_launch(c, r);
+    }
+    UZ_REQUIRE(ks == 3 && r.family == uz::CONV_SPLIT && uz::conv_np() == 2, "conv_fwd_ex: input in split storage, but this shape / math mode does not take the split-fp16 path");
+    UZ_REQUIRE(workspace && workspace_bytes >= r.ws_bytes, "conv_fwd_ex: workspace too small");
+    UZ_REQUIRE(!bn_partials || r.s.partials > 0, "conv_fwd_ex: this shape writes no fused statistics (uz_conv_bn_partials() == 0)");
+    return uz::conv_split(c, r);
 }
 // uz_conv_fwd_ex for a layer that follows a Conv -> BatchNorm -> ReLU unit (torchlayers.py:18-21), reading that unit's PRE-normalisation
 // output y_prev and its statistics table bn_save ([4][Cin]: mean, rstd, alpha = gamma rstd, beta' = beta - mean alpha, as uz_bn_relu_fwd_ex
@@ -589,30 +603,30 @@ extern "C" int uz_conv_fwd_bn_ex(const float* y_prev, int Cin, int CinTot, const
                                  const float* a_amax, const float* w_amax, float* y_amax,
                                  void* workspace, size_t workspace_bytes, const void* packed_w, float* bn_partials, void* stream) {
     UZ_REQUIRE(y_prev && bn_save && a_amax, "conv_fwd_bn_ex: needs the producer's output, its statistics table and the activation's bound");
-    UZ_REQUIRE(ks == 3 && uz_conv_route(0, Cin, Cout, N, H, W, ks) == 1 && uz::conv_np() == 2, "conv_fwd_bn_ex: this shape / math mode does not take the split-fp16 path");
-    UZ_REQUIRE(workspace && workspace_bytes >= uz::conv_split_workspace(Cin, Cout, N, H, W), "conv_fwd_bn_ex: workspace too small");
-    UZ_REQUIRE(!bn_partials || uz_conv_bn_partials(Cin, Cout, N, H, W, ks) > 0, "conv_fwd_bn_ex: this shape writes no fused statistics (uz_conv_bn_partials() == 0)");
-    uz::SplitOpts o;
-    o.aff = bn_save; o.aff_relu = bn_relu;
-    return uz::conv_split_ex(y_prev, Cin, CinTot, w, Cin, bias, y, Cout, CoutTot, N, H, W, 0, 0, 0, a_amax, w_amax, y_amax, workspace, packed_w, bn_partials, uz::S(stream), o);
+    const ConvRoute r = layer_route(0, Cin, Cout, N, H, W, ks);
+    UZ_REQUIRE(ks == 3 && r.family == uz::CONV_SPLIT && uz::conv_np() == 2, "conv_fwd_bn_ex: this shape / math mode does not take the split-fp16 path");
+    UZ_REQUIRE(workspace && workspace_bytes >= r.ws_bytes, "conv_fwd_bn_ex: workspace too small");
+    UZ_REQUIRE(!bn_partials || r.s.partials > 0, "conv_fwd_bn_ex: this shape writes no fused statistics (uz_conv_bn_partials() == 0)");
+    ConvCall c = fwd_call(y_prev, Cin, CinTot, w, bias, y, Cout, CoutTot, N, H, W, ks, a_amax, w_amax, y_amax, workspace, workspace_bytes, packed_w, bn_partials, stream);
+    c.aff = bn_save; c.aff_relu = bn_relu;
+    return uz::conv_split(c, r);
 }
 extern "C" int uz_conv_bwd_data_ex(const float* dy, int Cout, int CoutTot, const float* w, float* dx, int Cin, int CinTot,
                                    int N, int H, int W, int ks, int accumulate, const float* dy_amax, const float* w_amax,
                                    void* workspace, size_t workspace_bytes, const void* packed_w, int dy_packed,
                                    const float* bn_y, int bn_yCtot, const float* bn_save, int bn_relu, float* bn_partials, void* stream) {
-    if (!dy_packed && !bn_y)
-        return uz_conv_bwd_data_packed(dy, Cout, CoutTot, w, dx, Cin, CinTot, N, H, W, ks, accumulate, dy_amax, w_amax, workspace, workspace_bytes, packed_w, stream);
-    UZ_REQUIRE(ks == 3 && uz_conv_route(1, Cin, Cout, N, H, W, ks) == 1 && uz::conv_np() == 2, "conv_bwd_data_ex: split storage / folded reduction, but this shape / math mode does not take the split-fp16 path");
-    UZ_REQUIRE(workspace && workspace_bytes >= uz::conv_split_workspace(Cout, Cin, N, H, W), "conv_bwd_data_ex: workspace too small");
-    uz::SplitOpts o;
-    o.x_packed = dy_packed;
+    const ConvRoute r = layer_route(1, Cin, Cout, N, H, W, ks);
+    ConvCall c = dgrad_call(dy, Cout, CoutTot, w, dx, Cin, CinTot, N, H, W, ks, accumulate, dy_amax, w_amax, workspace, workspace_bytes, packed_w, stream);
+    c.x_packed = dy_packed;
+    if (!dy_packed && !bn_y) return uz::conv_launch(c, r);
+    UZ_REQUIRE(ks == 3 && r.family == uz::CONV_SPLIT && uz::conv_np() == 2, "conv_bwd_data_ex: split storage / folded reduction, but this shape / math mode does not take the split-fp16 path");
+    UZ_REQUIRE(workspace && workspace_bytes >= r.ws_bytes, "conv_bwd_data_ex: workspace too small");
     if (bn_y) {
-        UZ_REQUIRE(bn_save && bn_partials && !accumulate && uz_conv_bwd_relu_partials(Cin, Cout, N, H, W, ks) > 0,
+        UZ_REQUIRE(bn_save && bn_partials && !accumulate && r.s.partials > 0,
                    "conv_bwd_data_ex: the folded BatchNorm reduction needs the statistics table, the partial rows, an overwriting unsplit launch");
-        o.mk = 2; o.mask = bn_y; o.maskCtot = bn_yCtot; o.mk_save = bn_save; o.mk_relu = bn_relu;
+        c.mk = 2; c.mask = bn_y; c.maskCtot = bn_yCtot; c.mk_save = bn_save; c.mk_relu = bn_relu; c.bn_partials = bn_partials;
     }
-    return uz::conv_split_ex(dy, Cout, CoutTot, w, Cin, nullptr, dx, Cin, CinTot, N, H, W, 1, 0, accumulate, dy_amax, w_amax, nullptr, workspace, packed_w,
-                             bn_y ? bn_partials : nullptr, uz::S(stream), o);
+    return uz::conv_split(c, r);
 }
 // bf16 STORAGE (include/uz_api.h, "bf16 storage"; BASELINE config 5): the input and / or the output tensor hold 2-byte bf16 elements
 // (same NCHW shape).  Single-piece bf16 mode (uz_set_conv_math(3)), 3x3 shapes on the matrix-pipe path with planes wider than 32;
@@ -621,35 +635,33 @@ extern "C" int uz_conv_fwd_b16(const void* x, int Cin, int CinTot, const float* 
                                void* y, int Cout, int CoutTot, int N, int H, int W, int ks,
                                void* workspace, size_t workspace_bytes, const void* packed_w, float* bn_partials,
                                int x_b16, int y_b16, void* stream) {
-    UZ_REQUIRE(ks == 3 && uz::conv_np() == 1 && uz_conv_route(0, Cin, Cout, N, H, W, ks) == 1 && (!(x_b16 || y_b16) || uz_conv_split_parts(0, Cin, Cout, N, H, W) == 1),
+    const ConvRoute r = layer_route(0, Cin, Cout, N, H, W, ks);
+    UZ_REQUIRE(ks == 3 && uz::conv_np() == 1 && r.family == uz::CONV_SPLIT && (!(x_b16 || y_b16) || r.s.parts == 1),
                "conv_fwd_b16: bf16 storage needs uz_set_conv_math(3) and a 3x3 shape on the matrix-pipe path (unsplit chunk loop)");
-    UZ_REQUIRE(workspace && workspace_bytes >= uz::conv_split_workspace(Cin, Cout, N, H, W), "conv_fwd_b16: workspace too small");
-    UZ_REQUIRE(!bn_partials || uz_conv_bn_partials(Cin, Cout, N, H, W, ks) > 0, "conv_fwd_b16: this shape writes no fused statistics (uz_conv_bn_partials() == 0)");
-    uz::SplitOpts o;
-    o.x_b16 = x_b16 != 0; o.y_b16 = y_b16 != 0;
-    return uz::conv_split_ex(static_cast<const float*>(x), Cin, CinTot, w, Cin, bias, static_cast<float*>(y), Cout, CoutTot, N, H, W, 0, 0, 0,
-                             nullptr, nullptr, nullptr, workspace, packed_w, bn_partials, uz::S(stream), o);
+    UZ_REQUIRE(workspace && workspace_bytes >= r.ws_bytes, "conv_fwd_b16: workspace too small");
+    UZ_REQUIRE(!bn_partials || r.s.partials > 0, "conv_fwd_b16: this shape writes no fused statistics (uz_conv_bn_partials() == 0)");
+    ConvCall c = fwd_call(static_cast<const float*>(x), Cin, CinTot, w, bias, static_cast<float*>(y), Cout, CoutTot, N, H, W, ks,
+                          nullptr, nullptr, nullptr, workspace, workspace_bytes, packed_w, bn_partials, stream);
+    c.x_b16 = x_b16 != 0; c.y_b16 = y_b16 != 0;
+    return uz::conv_split(c, r);
 }
 extern "C" int uz_conv_bwd_data_b16(const void* dy, int Cout, int CoutTot, const float* w, void* dx, int Cin, int CinTot,
                                     int N, int H, int W, int ks, int accumulate,
                                     void* workspace, size_t workspace_bytes, const void* packed_w, int dy_b16, int dx_b16, void* stream) {
-    UZ_REQUIRE(ks == 3 && uz::conv_np() == 1 && uz_conv_route(1, Cin, Cout, N, H, W, ks) == 1 && (!(dy_b16 || dx_b16) || uz_conv_split_parts(1, Cin, Cout, N, H, W) == 1),
+    const ConvRoute r = layer_route(1, Cin, Cout, N, H, W, ks);
+    UZ_REQUIRE(ks == 3 && uz::conv_np() == 1 && r.family == uz::CONV_SPLIT && (!(dy_b16 || dx_b16) || r.s.parts == 1),
                "conv_bwd_data_b16: bf16 storage needs uz_set_conv_math(3) and a 3x3 shape on the matrix-pipe path (unsplit chunk loop)");
-    UZ_REQUIRE(workspace && workspace_bytes >= uz::conv_split_workspace(Cout, Cin, N, H, W), "conv_bwd_data_b16: workspace too small");
-    uz::SplitOpts o;
-    o.x_b16 = dy_b16 != 0; o.y_b16 = dx_b16 != 0;
-    return uz::conv_split_ex(static_cast<const float*>(dy), Cout, CoutTot, w, Cin, nullptr, static_cast<float*>(dx), Cin, CinTot, N, H, W, 1, 0, accumulate,
-                             nullptr, nullptr, nullptr, workspace, packed_w, nullptr, uz::S(stream), o);
+    UZ_REQUIRE(workspace && workspace_bytes >= r.ws_bytes, "conv_bwd_data_b16: workspace too small");
+    ConvCall c = dgrad_call(static_cast<const float*>(dy), Cout, CoutTot, w, static_cast<float*>(dx), Cin, CinTot, N, H, W, ks, accumulate,
+                            nullptr, nullptr, workspace, workspace_bytes, packed_w, stream);
+    c.x_b16 = dy_b16 != 0; c.y_b16 = dx_b16 != 0;
+    return uz::conv_split(c, r);
 }
 extern "C" int uz_conv_bwd_data_packed(const float* dy, int Cout, int CoutTot, const float* w,
                                        float* dx, int Cin, int CinTot, int N, int H, int W, int ks, int accumulate,
                                        const float* dy_amax, const float* w_amax,
                                        void* workspace, size_t workspace_bytes, const void* packed_w, void* stream) {
-    if (ks == 1 && uz::conv1x1_small_ok(Cin, Cout)) {
-        const int rc = uz::conv1x1_small_bwd_data(dy, Cout, CoutTot, w, dx, Cin, CinTot, N, H, W, accumulate, uz::S(stream));
-        if (rc != -2) return rc;
-    }
-    return uz::conv_mfma(dy, Cout, CoutTot, w, Cin, nullptr, dx, Cin, CinTot, N, H, W, ks, 1, 0, accumulate, dy_amax, w_amax, nullptr, workspace, workspace_bytes, packed_w, nullptr, uz::S(stream));
+    return uz_conv_bwd_data_ex(dy, Cout, CoutTot, w, dx, Cin, CinTot, N, H, W, ks, accumulate, dy_amax, w_amax, workspace, workspace_bytes, packed_w, 0, nullptr, 0, nullptr, 0, nullptr, stream);
 }
 // ---- ReLU backward folded into the data gradient that produces dA (vanilla U-Net blocks: Conv -> ReLU -> Conv, unet.py:25-30)
 namespace {
@@ -662,8 +674,6 @@ __global__ __launch_bounds__(256) void chan_sum_partials_k(const float* __restri
     s = uz::wave_sum_d(s);
     if (lane == 0) out[c] = (float)s;
 }
-}  // namespace
-namespace {
 // all bias gradients of a tape in ONE launch: table rows {partials, out, n_rows, C, is_double}; blockIdx.y = row, one wave per channel
 __global__ __launch_bounds__(256) void chan_sum_table_k(const long long* __restrict__ table) {
     const long long* e = table + 5 * blockIdx.y;
@@ -687,18 +697,18 @@ extern "C" int uz_chan_sum_table(const int64_t* table, int n_entries, int max_ch
     hipLaunchKernelGGL(chan_sum_table_k, dim3(uz::ceil_div(max_channels, 4), n_entries), dim3(256), 0, uz::S(stream), reinterpret_cast<const long long*>(table));
     return uz::check_launch("chan_sum_table_k");
 }
-extern "C" int uz_conv_bwd_relu_partials(int Cin, int Cout, int N, int H, int W, int ks) {
-    if (ks != 3 || !uz::conv_split_ok(Cout, Cin, N, H, W, ks, 1)) return 0;
-    return uz::conv_split_bn_partials(Cout, Cin, N, H, W);          // 0 when the chunk loop is split over workgroups
-}
+extern "C" int uz_conv_bwd_relu_partials(int Cin, int Cout, int N, int H, int W, int ks) { return split_partials(layer_route(1, Cin, Cout, N, H, W, ks)); }
 extern "C" int uz_conv_bwd_data_relu(const float* dy, int Cout, int CoutTot, const float* w, float* dx, int Cin, int CinTot,
                                      int N, int H, int W, int ks, int accumulate, const float* dy_amax, const float* w_amax,
                                      void* workspace, size_t workspace_bytes, const void* packed_w,
                                      const float* a, int aCtot, float* partials, float* dx_amax, void* stream) {
-    UZ_REQUIRE(uz_conv_bwd_relu_partials(Cin, Cout, N, H, W, ks) > 0, "conv_bwd_data_relu: this shape does not support the folded ReLU backward (uz_conv_bwd_relu_partials() == 0)");
-    UZ_REQUIRE(workspace && workspace_bytes >= uz::conv_split_workspace(Cout, Cin, N, H, W), "conv_bwd_data_relu: workspace too small");
-    return uz::conv_split_dgrad_relu(dy, Cout, CoutTot, w, Cin, dx, Cin, CinTot, N, H, W, accumulate, dy_amax, w_amax, dx_amax, workspace, packed_w,
-                                     a, aCtot, partials, uz::S(stream));
+    const ConvRoute r = layer_route(1, Cin, Cout, N, H, W, ks);
+    UZ_REQUIRE(split_partials(r) > 0, "conv_bwd_data_relu: this shape does not support the folded ReLU backward (uz_conv_bwd_relu_partials() == 0)");
+    UZ_REQUIRE(workspace && workspace_bytes >= r.ws_bytes, "conv_bwd_data_relu: workspace too small");
+    UZ_REQUIRE(a, "conv_dgrad_relu: needs the producer's activation");
+    ConvCall c = dgrad_call(dy, Cout, CoutTot, w, dx, Cin, CinTot, N, H, W, ks, accumulate, dy_amax, w_amax, workspace, workspace_bytes, packed_w, stream);
+    c.y_amax = dx_amax; c.mk = 1; c.mask = a; c.maskCtot = aCtot; c.bn_partials = partials;
+    return uz::conv_split(c, r);
 }
 extern "C" int uz_chan_sum_partials(const float* partials, int n_rows, int C, float* out, void* stream) {
     UZ_REQUIRE(partials && out && n_rows > 0 && C > 0, "chan_sum_partials: bad arguments");

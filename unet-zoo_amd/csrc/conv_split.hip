@@ -842,16 +842,14 @@ inline int tile_w(int W) { return small_geo(W) ? 16 : 32; }
 // ... and in the single-piece bf16 mode 128 where more than 64 output channels exist (round 5, conv_*_db_kernel_4_512_32): one product per
 // operand pair makes that mode LDS- and load-issue-bound in the 64-channel tile (one fragment read per MFMA); a wave tile of 128 channels x
 // 64 pixels reads 6 fragments per 8 MFMAs and stages the patch once per 128 output channels.  UZ_COT128=0 switches it off.
-int np_mode();
 inline bool cot128_enabled() { static const bool on = !(getenv("UZ_COT128") && atoi(getenv("UZ_COT128")) == 0); return on; }
 inline int tile_cot(int Kc, int Mc, int W) {
     if (small_geo(W) || Mc <= 32 || Kc <= 32) return 32;
-    return (np_mode() == 1 && Mc > 64 && cot128_enabled()) ? 128 : 64;
+    return (uz::conv_np() == 1 && Mc > 64 && cot128_enabled()) ? 128 : 64;
 }
 
 }  // namespace
 
-namespace { int np_mode() { return uz::conv_math_mode() == 3 ? 1 : 2; } }
 namespace uz {
 
 // planes per operand under the current math mode: 1 = bf16 (UZ_CONV_MATH=bf16), 2 = fp32-accurate fp16 split
@@ -926,22 +924,27 @@ int split_parts(int Kc, int Mc, int N, int H, int W) {
     if (S > nChunks / 3) S = nChunks / 3;
     return S < 1 ? 1 : S;
 }
-size_t image_bytes(int Kc, int Mc, int W) {
-    const int cot = tile_cot(Kc, Mc, W);
-    const size_t b = (size_t)ceil_div(Kc, CK) * ceil_div(Mc, cot) * 2 * (KK * cot * CK * 2);      // sized for two planes in either mode
-    return (b + 255) / 256 * 256;
+// the packed weight image of one direction: channel tile, chunks, rows and bytes depend on the channel counts and the plane's width alone
+SplitGeom split_image(int Kc, int Mc, int W) {
+    SplitGeom g = {};
+    g.tw = tile_w(W); g.cot = tile_cot(Kc, Mc, W);
+    g.nChunks = ceil_div(Kc, CK);
+    g.rows = g.nChunks * ceil_div(Mc, g.cot) * KK * g.cot;
+    const size_t b = (size_t)g.nChunks * ceil_div(Mc, g.cot) * 2 * (KK * g.cot * CK * 2);      // sized for two planes in either mode
+    g.image_bytes = (b + 255) / 256 * 256;
+    return g;
 }
 }  // namespace
-// Number of per-channel statistics partials a forward launch with fused BatchNorm statistics writes (0: this shape does not
-// support them - off the split path, or its chunk loop is split over workgroups and the partial sums are only added later).
-int conv_split_bn_partials(int Kc, int Mc, int N, int H, int W) {
-    if (!conv_split_ok(Kc, Mc, N, H, W, 3, 0) || split_parts(Kc, Mc, N, H, W) != 1) return 0;
-    const int tw = tile_w(W), nt = tw == 16 ? 256 : 512;
-    return N * ceil_div(H, TH) * ceil_div(W, tw) * (nt / 4 / 64);
-}
-size_t conv_split_workspace(int Kc, int Mc, int N, int H, int W) {
-    const int S = split_parts(Kc, Mc, N, H, W);
-    return WS_HEAD + image_bytes(Kc, Mc, W) + (S > 1 ? (size_t)S * N * Mc * H * W * sizeof(float) : 0);
+// The matrix-pipe part of a route.  partials: number of per-channel statistics partials a forward launch with fused BatchNorm
+// statistics writes (0: its chunk loop is split over workgroups and the partial sums are only added later).
+SplitGeom split_geom(int Kc, int Mc, int N, int H, int W) {
+    SplitGeom g = split_image(Kc, Mc, W);
+    const int S = (long long)N * H * W * Mc > 0 ? split_parts(Kc, Mc, N, H, W) : 1;       // an empty shape has no tiles to count
+    g.cps = std::max(ceil_div(g.nChunks, S), 1);
+    g.parts = ceil_div(g.nChunks, g.cps);                // no empty parts
+    g.partials = g.parts == 1 ? N * ceil_div(H, TH) * ceil_div(W, g.tw) * ((g.tw == 16 ? 256 : 512) / 4 / 64) : 0;
+    g.ws_bytes = WS_HEAD + g.image_bytes + (S > 1 ? (size_t)S * N * Mc * H * W * sizeof(float) : 0);     // slabs for S parts, before the empty ones are dropped
+    return g;
 }
 
 namespace {
@@ -971,115 +974,77 @@ int absmax_flat(const float* x, size_t n, float* slot, hipStream_t st) {
     return check_launch("absmax_view_kernel");
 }
 
-// x_amax / w_amax: device scalars bounding |x| and |w| (any upper bound within ~2^10 of the true maximum keeps full
-// accuracy); NULL = measure here (one extra pass over the tensor: the stand-alone C-ABI path, the model plans pass
-// bounds that the producing kernels maintain).  y_amax (nullable): atomic max of |y| for the next consumer.
-static int conv_split_impl(const float* x, int Kc, int KcTot, const float* w, int wCi, const float* bias,
-               float* y, int Mc, int McTot, int N, int H, int W, int dgrad, int relu, int accumulate,
-               const float* x_amax, const float* w_amax, float* y_amax, void* workspace, const void* packed_w, float* bn_partials, hipStream_t st,
-               const SplitOpts& o);
-int conv_split(const float* x, int Kc, int KcTot, const float* w, int wCi, const float* bias,
-               float* y, int Mc, int McTot, int N, int H, int W, int dgrad, int relu, int accumulate,
-               const float* x_amax, const float* w_amax, float* y_amax, void* workspace, const void* packed_w, float* bn_partials, hipStream_t st) {
-    return conv_split_impl(x, Kc, KcTot, w, wCi, bias, y, Mc, McTot, N, H, W, dgrad, relu, accumulate, x_amax, w_amax, y_amax, workspace, packed_w,
-                           bn_partials, st, SplitOpts());
-}
-// ... with the round-4 options (uz_common.h, SplitOpts): input in split storage with up to two scale segments, and / or the
-// BatchNorm-backward reduction of the unit that produced the data gradient's output folded into the epilogue
-int conv_split_ex(const float* x, int Kc, int KcTot, const float* w, int wCi, const float* bias,
-                  float* y, int Mc, int McTot, int N, int H, int W, int dgrad, int relu, int accumulate,
-                  const float* x_amax, const float* w_amax, float* y_amax, void* workspace, const void* packed_w, float* bn_partials, hipStream_t st,
-                  const SplitOpts& o) {
-    return conv_split_impl(x, Kc, KcTot, w, wCi, bias, y, Mc, McTot, N, H, W, dgrad, relu, accumulate, x_amax, w_amax, y_amax, workspace, packed_w,
-                           bn_partials, st, o);
-}
-// Data gradient with the ReLU backward of the unit that PRODUCED its output's forward twin folded into the epilogue (vanilla U-Net
-// blocks, unet.py:25-30: Conv -> ReLU with no normalisation in between): dx = (a > 0) ? conv_T(dy, w) [+ dx] : 0, where `a` is that
-// unit's activation (a view of Mc channels); partials (nullable) receive the per-(tile, channel) sums of dx for the unit's bias
-// gradient in the layout of conv_split_bn_partials(); dx_amax receives max |dx|.  Unsplit chunk loops only.
-int conv_split_dgrad_relu(const float* dy, int Kc, int KcTot, const float* w, int wCi, float* dx, int Mc, int McTot, int N, int H, int W, int accumulate,
-                          const float* dy_amax, const float* w_amax, float* dx_amax, void* workspace, const void* packed_w,
-                          const float* a, int aCtot, float* partials, hipStream_t st) {
-    UZ_REQUIRE(a, "conv_dgrad_relu: needs the producer's activation");
-    SplitOpts o;
-    o.mk = 1; o.mask = a; o.maskCtot = aCtot;
-    return conv_split_impl(dy, Kc, KcTot, w, wCi, nullptr, dx, Mc, McTot, N, H, W, 1, 0, accumulate, dy_amax, w_amax, dx_amax, workspace, packed_w,
-                           partials, st, o);
-}
-static int conv_split_impl(const float* x, int Kc, int KcTot, const float* w, int wCi, const float* bias,
-               float* y, int Mc, int McTot, int N, int H, int W, int dgrad, int relu, int accumulate,
-               const float* x_amax, const float* w_amax, float* y_amax, void* workspace, const void* packed_w, float* bn_partials, hipStream_t st,
-               const SplitOpts& o) {
-    const float* relu_mask = o.mask;
+// One call on the matrix pipe (r.family == CONV_SPLIT; the workspace holds r.s.ws_bytes).  Options (uz_common.h, ConvCall): input in
+// split storage with up to two scale segments; the ReLU backward (mk 1) or the BatchNorm-backward reduction (mk 2) of the unit that
+// PRODUCED the data gradient's output's forward twin folded into the epilogue - vanilla U-Net blocks, unet.py:25-30, Conv -> ReLU with
+// no normalisation in between: dx = (a > 0) ? conv_T(dy, w) [+ dx] : 0, where `a` = mask is that unit's activation (a view of Mc
+// channels), bn_partials (nullable) receive the per-(tile, channel) sums of dx for the unit's bias gradient, r.s.partials rows, and
+// y_amax receives max |dx|.  Unsplit chunk loops only.
+int conv_split(const ConvCall& c, const ConvRoute& r) {
+    const SplitGeom& g = r.s;
+    const int Kc = c.Kc, Mc = c.Mc, N = c.N, H = c.H, W = c.W, dgrad = c.dgrad;
+    const float* x_amax = c.x_amax; const float* w_amax = c.w_amax; hipStream_t st = c.st;
     SP p;
-    p.mask = o.mask; p.maskCtot = o.maskCtot; p.mk_save = o.mk_save; p.mk_relu = o.mk_relu;
-    p.aff = o.aff; p.aff_relu = o.aff_relu;
-    float* slots = static_cast<float*>(workspace);
-    char* image = static_cast<char*>(workspace) + WS_HEAD;
+    p.mask = c.mask; p.maskCtot = c.maskCtot; p.mk_save = c.mk_save; p.mk_relu = c.mk_relu;
+    p.aff = c.aff; p.aff_relu = c.aff_relu;
+    float* slots = static_cast<float*>(c.workspace);
+    char* image = static_cast<char*>(c.workspace) + WS_HEAD;
     const int np = conv_np();                            // 1: bf16 single-piece operands (no scales, no bounds)
-    UZ_REQUIRE(np == 1 || !packed_w || w_amax, "conv_split: a pre-packed weight image needs the bound it was scaled with");
-    UZ_REQUIRE(!o.x_packed || (np == 2 && x_amax), "conv_split: input in split storage needs the two-piece mode and the bound it was scaled from");
-    UZ_REQUIRE(!o.aff || (np == 2 && x_amax && !dgrad && !o.x_packed && o.mk == 0), "conv_split: the folded BatchNorm apply serves a plain forward convolution in the two-piece mode and needs the activation's bound");
-    UZ_REQUIRE(!o.x_packed || o.seg_channels == 0 || (o.x_amax2 && o.seg_channels % CK == 0 && o.seg_channels < Kc),
+    UZ_REQUIRE(np == 1 || !c.packed_w || w_amax, "conv_split: a pre-packed weight image needs the bound it was scaled with");
+    UZ_REQUIRE(!c.x_packed || (np == 2 && x_amax), "conv_split: input in split storage needs the two-piece mode and the bound it was scaled from");
+    UZ_REQUIRE(!c.aff || (np == 2 && x_amax && !dgrad && !c.x_packed && c.mk == 0), "conv_split: the folded BatchNorm apply serves a plain forward convolution in the two-piece mode and needs the activation's bound");
+    UZ_REQUIRE(!c.x_packed || c.seg_channels == 0 || (c.x_amax2 && c.seg_channels % CK == 0 && c.seg_channels < Kc),
                "conv_split: the second scale segment must start on a multiple of 16 channels inside the view and carry its bound");
-    UZ_REQUIRE(o.mk != 2 || (o.mask && o.mk_save && dgrad && bn_partials), "conv_split: the folded BatchNorm reduction needs y, the statistics table and the partial rows");
-    p.x_amax2 = o.x_packed && o.seg_channels > 0 ? o.x_amax2 : nullptr;
-    p.segc = p.x_amax2 ? o.seg_channels / CK : -1;
+    UZ_REQUIRE(c.mk != 2 || (c.mask && c.mk_save && dgrad && c.bn_partials), "conv_split: the folded BatchNorm reduction needs y, the statistics table and the partial rows");
+    p.x_amax2 = c.x_packed && c.seg_channels > 0 ? c.x_amax2 : nullptr;
+    p.segc = p.x_amax2 ? c.seg_channels / CK : -1;
     if (np == 2 && (!x_amax || !w_amax)) {
         if (hipMemsetAsync(slots, 0, WS_HEAD, st) != hipSuccess) return fail("conv_split: memset failed");
-        if (!x_amax) { if (int rc = absmax_view(x, Kc, KcTot, N, H * W, slots, st)) return rc; x_amax = slots; }
+        if (!x_amax) { if (int rc = absmax_view(c.x, Kc, c.KcTot, N, H * W, slots, st)) return rc; x_amax = slots; }
         if (!w_amax) {
             // the weight view may be a row / column slice of the parameter: bound over the enclosing rows is still a bound
-            const size_t nw = dgrad ? (size_t)Kc * wCi * KK : (size_t)Mc * wCi * KK;
-            if (int rc = absmax_flat(w, nw, slots + AMAX_FLOATS, st)) return rc;
+            const size_t nw = dgrad ? (size_t)Kc * c.wCi * KK : (size_t)Mc * c.wCi * KK;
+            if (int rc = absmax_flat(c.w, nw, slots + AMAX_FLOATS, st)) return rc;
             w_amax = slots + AMAX_FLOATS;
         }
     }
-    p.x = x; p.wp = packed_w ? static_cast<const char*>(packed_w) : image; p.bias = bias; p.y = y;
-    p.x_amax = x_amax; p.w_amax = w_amax; p.y_amax = y_amax;
+    p.x = c.x; p.wp = c.packed_w ? static_cast<const char*>(c.packed_w) : image; p.bias = c.bias; p.y = c.y;
+    p.x_amax = x_amax; p.w_amax = w_amax; p.y_amax = c.y_amax;
     p.N = N; p.H = H; p.W = W; p.HW = H * W;
-    p.Cin = Kc; p.CinTot = KcTot; p.Cout = Mc; p.CoutTot = McTot;
-    const int tw = tile_w(W), cot = tile_cot(Kc, Mc, W);
+    p.Cin = Kc; p.CinTot = c.KcTot; p.Cout = Mc; p.CoutTot = c.McTot;
+    const int tw = g.tw, cot = g.cot;
     p.tilesX = ceil_div(W, tw); p.tilesY = ceil_div(H, TH);
-    p.relu = relu; p.accumulate = accumulate;
+    p.relu = c.relu; p.accumulate = c.accumulate;
     p.nCoTiles = ceil_div(Mc, cot);
-    p.nChunks = ceil_div(Kc, CK);
-    p.kSplit = split_parts(Kc, Mc, N, H, W);
-    p.cps = ceil_div(p.nChunks, p.kSplit);
-    p.kSplit = ceil_div(p.nChunks, p.cps);               // no empty parts
-    UZ_REQUIRE(!bn_partials || (p.kSplit == 1 && !relu && ((!accumulate && !dgrad) || relu_mask)), "conv_split: fused BatchNorm statistics need an unsplit plain forward convolution");
-    UZ_REQUIRE(!relu_mask || (p.kSplit == 1 && dgrad), "conv_split: the folded ReLU / BatchNorm backward needs an unsplit data gradient");
-    p.slab = reinterpret_cast<float*>(image + image_bytes(Kc, Mc, W));
+    p.nChunks = g.nChunks; p.kSplit = g.parts; p.cps = g.cps;
+    UZ_REQUIRE(!c.bn_partials || (p.kSplit == 1 && !c.relu && ((!c.accumulate && !dgrad) || c.mask)), "conv_split: fused BatchNorm statistics need an unsplit plain forward convolution");
+    UZ_REQUIRE(!c.mask || (p.kSplit == 1 && dgrad), "conv_split: the folded ReLU / BatchNorm backward needs an unsplit data gradient");
+    p.slab = reinterpret_cast<float*>(image + g.image_bytes);
     p.stamps = uz::debug_stamps;
     p.flags = dev_flags_ptr(); p.flag_bit = dgrad ? FLAG_DY_BOUND : FLAG_X_BOUND;
-    p.bnpart = bn_partials;
-    p.yb16 = o.y_b16;
-    UZ_REQUIRE(!(o.x_b16 || o.y_b16) || (np == 1 && p.kSplit == 1 && !relu_mask), "conv_split: bf16 storage needs the single-piece bf16 mode, an unsplit chunk loop and a plain epilogue");
+    p.bnpart = c.bn_partials;
+    p.yb16 = c.y_b16;
+    UZ_REQUIRE(!(c.x_b16 || c.y_b16) || (np == 1 && p.kSplit == 1 && !c.mask), "conv_split: bf16 storage needs the single-piece bf16 mode, an unsplit chunk loop and a plain epilogue");
     const long long grid = (long long)p.tilesX * p.tilesY * N * p.nCoTiles * p.kSplit;
     UZ_REQUIRE(grid < (1ll << 31), "conv_split: grid too large");
     // per-image buffer resources and 64-bit output addressing: only ONE image's input view has to fit 32-bit byte offsets
     UZ_REQUIRE((size_t)Kc * p.HW * 4 < (1ull << 32), "conv_split: one image's input view exceeds 4 GB");
-    const int rows = p.nChunks * p.nCoTiles * KK * cot;
-    if (packed_w) {}                                     // packed once per step by uz_conv_pack_weights
-    else if (np == 2) {
-        if (dgrad) hipLaunchKernelGGL((pack_weights_kernel<true, 2>), dim3(ceil_div(rows, 256)), dim3(256), 0, st, w, image, w_amax, Mc, Kc, wCi, p.nChunks, p.nCoTiles, cot, p.flags);
-        else hipLaunchKernelGGL((pack_weights_kernel<false, 2>), dim3(ceil_div(rows, 256)), dim3(256), 0, st, w, image, w_amax, Mc, Kc, wCi, p.nChunks, p.nCoTiles, cot, p.flags);
-    } else {
-        if (dgrad) hipLaunchKernelGGL((pack_weights_kernel<true, 1>), dim3(ceil_div(rows, 256)), dim3(256), 0, st, w, image, w_amax, Mc, Kc, wCi, p.nChunks, p.nCoTiles, cot, p.flags);
-        else hipLaunchKernelGGL((pack_weights_kernel<false, 1>), dim3(ceil_div(rows, 256)), dim3(256), 0, st, w, image, w_amax, Mc, Kc, wCi, p.nChunks, p.nCoTiles, cot, p.flags);
-    }
+    const dim3 pgrid(ceil_div(g.rows, 256));
+    const auto pack = np == 2 ? (dgrad ? pack_weights_kernel<true, 2> : pack_weights_kernel<false, 2>) : (dgrad ? pack_weights_kernel<true, 1> : pack_weights_kernel<false, 1>);
+    if (!c.packed_w)                                     // else: packed once per step by uz_conv_pack_weights
+        hipLaunchKernelGGL(pack, pgrid, dim3(256), 0, st, c.w, image, w_amax, Mc, Kc, c.wCi, p.nChunks, p.nCoTiles, cot, p.flags);
     if (int rc = check_launch("pack_weights_kernel")) return rc;
     int rc;
     if (np == 2) {
-        if (tw == 16) rc = launch<1, 256, 16, 2>(p, (int)grid, st, o.mk, o.x_packed, o.x_b16);
-        else rc = cot == 32 ? launch<1, 512, 32, 2>(p, (int)grid, st, o.mk, o.x_packed, o.x_b16) : launch<2, 512, 32, 2>(p, (int)grid, st, o.mk, o.x_packed, o.x_b16);
+        if (tw == 16) rc = launch<1, 256, 16, 2>(p, (int)grid, st, c.mk, c.x_packed, c.x_b16);
+        else rc = cot == 32 ? launch<1, 512, 32, 2>(p, (int)grid, st, c.mk, c.x_packed, c.x_b16) : launch<2, 512, 32, 2>(p, (int)grid, st, c.mk, c.x_packed, c.x_b16);
     } else {
-        if (tw == 16) rc = launch<1, 256, 16, 1>(p, (int)grid, st, o.mk, o.x_packed, o.x_b16);
-        else rc = cot == 32 ? launch<1, 512, 32, 1>(p, (int)grid, st, o.mk, o.x_packed, o.x_b16)
-                : cot == 128 ? launch<4, 512, 32, 1>(p, (int)grid, st, o.mk, o.x_packed, o.x_b16) : launch<2, 512, 32, 1>(p, (int)grid, st, o.mk, o.x_packed, o.x_b16);
+        if (tw == 16) rc = launch<1, 256, 16, 1>(p, (int)grid, st, c.mk, c.x_packed, c.x_b16);
+        else rc = cot == 32 ? launch<1, 512, 32, 1>(p, (int)grid, st, c.mk, c.x_packed, c.x_b16)
+                : cot == 128 ? launch<4, 512, 32, 1>(p, (int)grid, st, c.mk, c.x_packed, c.x_b16) : launch<2, 512, 32, 1>(p, (int)grid, st, c.mk, c.x_packed, c.x_b16);
     }
     if (rc || p.kSplit == 1) return rc;
-    return splitk_reduce(p.slab, p.kSplit, bias, y, Mc, McTot, N, H * W, relu, accumulate, y_amax, st);
+    return splitk_reduce(p.slab, p.kSplit, c.bias, c.y, Mc, c.McTot, N, H * W, c.relu, c.accumulate, c.y_amax, st);
 }
 
 }  // namespace uz
@@ -1123,19 +1088,12 @@ __global__ __launch_bounds__(256) void pack_all_kernel(const long long* __restri
 // Number of workgroups the matrix-pipe kernel shares one tile's chunk loop out over (kind 0 forward, 1 data gradient); > 1: partial
 // sums go through fp32 slabs and a reduce launch - such shapes have no bf16-storage form (uz_conv_fwd_b16 / uz_conv_bwd_data_b16)
 extern "C" int uz_conv_split_parts(int kind, int Cin, int Cout, int N, int H, int W) {
-    const int Kc = kind == 1 ? Cout : Cin, Mc = kind == 1 ? Cin : Cout;
-    const int nChunks = uz::ceil_div(Kc, CK);
-    const int S = uz::split_parts(Kc, Mc, N, H, W);
-    return uz::ceil_div(nChunks, uz::ceil_div(nChunks, S));
+    return kind == 1 ? uz::split_geom(Cout, Cin, N, H, W).parts : uz::split_geom(Cin, Cout, N, H, W).parts;
 }
-extern "C" size_t uz_conv_packed_bytes(int Cin, int Cout, int W, int dgrad) {
-    return dgrad ? uz::image_bytes(Cout, Cin, W) : uz::image_bytes(Cin, Cout, W);
-}
-extern "C" int uz_conv_pack_rows(int Cin, int Cout, int W, int dgrad) {
-    const int Kc = dgrad ? Cout : Cin, Mc = dgrad ? Cin : Cout, cot = tile_cot(Kc, Mc, W);
-    return uz::ceil_div(Kc, CK) * uz::ceil_div(Mc, cot) * KK * cot;
-}
-extern "C" int uz_conv_pack_cot(int Cin, int Cout, int W, int dgrad) { return tile_cot(dgrad ? Cout : Cin, dgrad ? Cin : Cout, W); }
+static uz::SplitGeom pack_image(int Cin, int Cout, int W, int dgrad) { return dgrad ? uz::split_image(Cout, Cin, W) : uz::split_image(Cin, Cout, W); }
+extern "C" size_t uz_conv_packed_bytes(int Cin, int Cout, int W, int dgrad) { return pack_image(Cin, Cout, W, dgrad).image_bytes; }
+extern "C" int uz_conv_pack_rows(int Cin, int Cout, int W, int dgrad) { return pack_image(Cin, Cout, W, dgrad).rows; }
+extern "C" int uz_conv_pack_cot(int Cin, int Cout, int W, int dgrad) { return pack_image(Cin, Cout, W, dgrad).cot; }
 extern "C" int uz_conv_pack_weights(const int64_t* table, int n_layers, int total_rows, const float* w_amax, void* stream) {
     UZ_REQUIRE(table && w_amax && n_layers >= 0 && total_rows >= 0, "conv_pack_weights: null argument");
     if (n_layers == 0 || total_rows == 0) return 0;

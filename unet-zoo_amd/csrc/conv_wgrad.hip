@@ -520,7 +520,11 @@ inline bool wgrad_thin_ok(int Cin, int Cout, int N, int H, int W, int ks) {
 constexpr int THIN_SLABS = 512;
 inline int wgrad_thin_slabs(int N, int H) { const int t = N * (H / THIN_ROWS); return t < THIN_SLABS ? t : THIN_SLABS; }
 
-struct WGeom { int TW, TH, TB, PW, PSI, PS, tilesX, tilesY, tilesB, T, S, nCoT, nCiT, WM, WN, WK, pf, fast, SW; };   // SW: slabs per pixel split
+using uz::WGeom;
+// the split-fp16 and the fast fp32 kernels address a whole tensor through one buffer resource (32-bit byte offsets)
+inline bool wgrad_huge(int Cin, int Cout, int N, int H, int W) {
+    return (size_t)N * Cin * H * W >= (1ull << 30) || (size_t)N * Cout * H * W >= (1ull << 30);
+}
 
 WGeom pick_wgeom(int Cin, int Cout, int N, int H, int W, int halo) {
     WGeom g;
@@ -549,7 +553,7 @@ WGeom pick_wgeom(int Cin, int Cout, int N, int H, int W, int halo) {
     g.pf = (32 * g.WN * g.PS <= 18 * 512) ? 1 : 0;
     // the fast kernels address a whole tensor through one buffer resource (32-bit byte offsets): tensors of 2^30 elements
     // or more take the generic kernel (64-bit pointers)
-    const bool huge = (size_t)N * Cin * H * W >= (1ull << 30) || (size_t)N * Cout * H * W >= (1ull << 30);
+    const bool huge = wgrad_huge(Cin, Cout, N, H, W);
     g.fast = halo == 1 && g.TB == 1 && !huge &&
              ((g.TW == 32 && (g.TH == 2 || g.TH == 4)) || (g.TW == 16 && g.TH == 4) || (g.TW == 8 && g.TH == 8));
     g.SW = g.fast ? 1 : g.WK;                 // the fast kernels fold their WK partial sums in LDS
@@ -577,52 +581,48 @@ WGeom pick_wgeom(int Cin, int Cout, int N, int H, int W, int halo) {
 
 }  // namespace
 
+namespace uz {
+
+// The weight gradient's route.  The families in the order the dispatch asks: 1x1 head, thin input, matrix pipe, fp32.
+WgradRoute wgrad_route(int Cin, int Cout, int CinTot, int CoutTot, int N, int H, int W, int ks) {
+    WgradRoute r;
+    const size_t slab = (size_t)ks * ks * Cout * Cin * sizeof(float);
+    r.g = pick_wgeom(Cin, Cout, N, H, W, ks / 2);
+    r.f32_bytes = (size_t)r.g.S * r.g.SW * slab;
+    const bool head = ks == 1 && conv1x1_small_ok(Cin, Cout), thin = wgrad_thin_ok(Cin, Cout, N, H, W, ks);
+    r.split_eligible = wgrad_split_ok(Cin, Cout, N, H, W, ks);
+    // tensors of 2^30 elements or more take the generic fp32 kernel (64-bit pointers) instead of failing
+    r.huge = wgrad_huge(CinTot, CoutTot, N, H, W);
+    r.family = head ? WG_HEAD : thin ? WG_THIN : r.split_eligible && !r.huge ? WG_SPLIT : r.g.fast ? WG_FAST : WG_GENERIC;
+    r.ws_bytes = std::max(r.f32_bytes, (size_t)Cout * CSB * sizeof(double));       // ... or the bias gradient's fp64 partials
+    int thin_slabs = 0, splits = 0;
+    if (thin) {
+        const int total = N * (H / THIN_ROWS);
+        r.per_wg = ceil_div(total, wgrad_thin_slabs(N, H));
+        thin_slabs = ceil_div(total, r.per_wg);
+        r.ws_bytes = std::max(r.ws_bytes, (size_t)wgrad_thin_slabs(N, H) * slab);
+    }
+    if (r.split_eligible && Cin > 0 && Cout > 0) {
+        splits = wgrad_split_splits(Cin, Cout, N, H, W, r.tw, r.ct);
+        r.ws_bytes = std::max(r.ws_bytes, (size_t)splits * slab + 2 * AMAX_FLOATS * sizeof(float));    // + fallback bound slots
+    }
+    if (head) r.ws_bytes = std::max(r.ws_bytes, conv1x1_small_bwd_weight_ws(Cin, Cout, N, H, W));
+    r.slabs = head ? 0 : thin ? thin_slabs : r.family == WG_SPLIT ? splits : r.g.S * r.g.SW;
+    //  uz_conv_bwd_weight_slabs sees the VIEW's channels: a channel slice of a >= 2^30-element buffer leaves the split path, not its query
+    r.view_slabs = r.family < WG_SPLIT ? r.slabs : r.split_eligible && !wgrad_huge(Cin, Cout, N, H, W) ? splits : r.g.S * r.g.SW;
+    return r;
+}
+
+}  // namespace uz
+
 extern "C" size_t uz_conv_bwd_weight_workspace(int Cin, int Cout, int N, int H, int W, int ks) {
-    const WGeom g = pick_wgeom(Cin, Cout, N, H, W, ks / 2);
-    const size_t slabs = (size_t)g.S * g.SW * ks * ks * Cout * Cin * sizeof(float);
-    const size_t dbp = (size_t)Cout * CSB * sizeof(double);
-    size_t need = slabs > dbp ? slabs : dbp;
-    if (wgrad_thin_ok(Cin, Cout, N, H, W, ks)) {
-        const size_t th = (size_t)wgrad_thin_slabs(N, H) * 9 * Cout * Cin * sizeof(float);
-        if (th > need) need = th;
-    }
-    if (uz::wgrad_split_ok(Cin, Cout, N, H, W, ks)) {
-        const size_t sp = (size_t)uz::wgrad_split_splits(Cin, Cout, N, H, W) * ks * ks * Cout * Cin * sizeof(float) + 2 * uz::AMAX_FLOATS * sizeof(float);    // + fallback bound slots
-        if (sp > need) need = sp;
-    }
-    if (ks == 1 && uz::conv1x1_small_ok(Cin, Cout)) {
-        const size_t sm = uz::conv1x1_small_bwd_weight_ws(Cin, Cout, N, H, W);
-        if (sm > need) need = sm;
-    }
-    return need;
+    return uz::wgrad_route(Cin, Cout, Cin, Cout, N, H, W, ks).ws_bytes;
 }
-
-// Which kernel family a convolution call takes under the current math mode (diagnostics / roofline bookkeeping):
-// kind 0 = forward, 1 = data gradient, 2 = weight gradient; returns 0 fp32 MFMA, 1 split-fp16 MFMA, 2 streaming VALU (1x1 heads).
-extern "C" int uz_conv_route(int kind, int Cin, int Cout, int N, int H, int W, int ks) {
-    if (ks == 1 && uz::conv1x1_small_ok(Cin, Cout)) return 2;
-    const bool thin = ks == 3 && Cin <= 4 && (long long)N * H * W >= 64 * 1024;       // 1..4-channel input layers: streaming kernels
-    if (kind == 0 && thin && Cout <= 256 && N <= 65535) return 2;
-    if (kind == 2 && wgrad_thin_ok(Cin, Cout, N, H, W, ks)) return 2;
-    if (kind == 0) return uz::conv_split_ok(Cin, Cout, N, H, W, ks, 0) ? 1 : 0;
-    if (kind == 1) return uz::conv_split_ok(Cout, Cin, N, H, W, ks, 1) ? 1 : 0;
-    return uz::wgrad_split_ok(Cin, Cout, N, H, W, ks) ? 1 : 0;
-}
-
 // Number of partial-sum slabs [ks*ks][Cout][Cin] a weight-gradient call of this shape writes before its reduction (0: the call does
-// not go through slabs - the streaming 1x1 heads).  Mirrors the dispatch of uz_conv_bwd_weight_ex below.
+// not go through slabs - the streaming 1x1 heads).
 extern "C" int uz_conv_bwd_weight_slabs(int Cin, int Cout, int N, int H, int W, int ks) {
     if ((ks != 1 && ks != 3) || Cin <= 0 || Cout <= 0 || N <= 0 || H <= 0 || W <= 0) return 0;
-    if (ks == 1 && uz::conv1x1_small_ok(Cin, Cout)) return 0;
-    if (wgrad_thin_ok(Cin, Cout, N, H, W, ks)) {
-        const int total = N * (H / THIN_ROWS);
-        const int per_wg = uz::ceil_div(total, wgrad_thin_slabs(N, H));
-        return uz::ceil_div(total, per_wg);
-    }
-    const bool huge = (size_t)N * Cin * H * W >= (1ull << 30) || (size_t)N * Cout * H * W >= (1ull << 30);
-    if (!huge && uz::wgrad_split_ok(Cin, Cout, N, H, W, ks)) return uz::wgrad_split_splits(Cin, Cout, N, H, W);
-    const WGeom g = pick_wgeom(Cin, Cout, N, H, W, ks / 2);
-    return g.S * g.SW;
+    return uz::wgrad_route(Cin, Cout, Cin, Cout, N, H, W, ks).slabs;
 }
 namespace {
 // All slab reductions of a tape in ONE launch.  table: n_layers rows of 8 int64 {slabs (address), dw (address), S, Cout, Cin, ks*ks,
@@ -684,68 +684,23 @@ extern "C" int uz_wgrad_reduce_table(const int64_t* table, int n_layers, int tot
     return uz::check_launch("wgrad_reduce_table_k");
 }
 
-extern "C" int uz_conv_bwd_weight(const float* x, int Cin, int CinTot, const float* dy, int Cout, int CoutTot,
-                                  float* dw, float* db, int N, int H, int W, int ks,
-                                  const float* x_amax, const float* dy_amax,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-    return uz_conv_bwd_weight_ex(x, Cin, CinTot, dy, Cout, CoutTot, dw, db, N, H, W, ks, x_amax, dy_amax, workspace, workspace_bytes, 0, nullptr, 0, 0, nullptr, stream);
+namespace {
+// 1..4 input channels: streaming reduction (same slab layout, ordered reduce like the others), r.slabs slabs into `slab`
+int wgrad_thin(const uz::WgradCall& c, const uz::WgradRoute& r, float* slab) {
+    UZ_REQUIRE(c.workspace_bytes >= (size_t)r.slabs * 9 * c.Cout * c.Cin * sizeof(float), "conv_bwd_weight: workspace too small for the thin-input path");
+    const dim3 tg(r.slabs, uz::ceil_div(c.Cout, THIN_CO));
+    static const decltype(&wgrad_thin_kernel<1>) kern[] = {wgrad_thin_kernel<1>, wgrad_thin_kernel<2>, wgrad_thin_kernel<3>, wgrad_thin_kernel<4>};
+    hipLaunchKernelGGL(kern[c.Cin >= 1 && c.Cin <= 3 ? c.Cin - 1 : 3], tg, dim3(256), 0, c.st, c.x, c.CinTot, c.dy, c.CoutTot, c.Cout, slab, c.N, c.H, c.W, c.H / THIN_ROWS, r.per_wg);
+    return 0;
 }
-// ... with either operand in split storage (include/uz_api.h, round 4): only on the split-fp16 path, bias gradient not available
-// (db reads dy as fp32).
-static int conv_bwd_weight_impl(const float* x, int Cin, int CinTot, const float* dy, int Cout, int CoutTot,
-                                float* dw, float* db, int N, int H, int W, int ks,
-                                const float* x_amax, const float* dy_amax, void* workspace, size_t workspace_bytes,
-                                int x_packed, const float* x_amax2, int seg_channels, int dy_packed, float* slabs_out, void* stream,
-                                int x_b16, int dy_b16);
-extern "C" int uz_conv_bwd_weight_ex(const float* x, int Cin, int CinTot, const float* dy, int Cout, int CoutTot,
-                                     float* dw, float* db, int N, int H, int W, int ks,
-                                     const float* x_amax, const float* dy_amax, void* workspace, size_t workspace_bytes,
-                                     int x_packed, const float* x_amax2, int seg_channels, int dy_packed, float* slabs_out, void* stream) {
-    return conv_bwd_weight_impl(x, Cin, CinTot, dy, Cout, CoutTot, dw, db, N, H, W, ks, x_amax, dy_amax, workspace, workspace_bytes,
-                                x_packed, x_amax2, seg_channels, dy_packed, slabs_out, stream, 0, 0);
-}
-// bf16 STORAGE (include/uz_api.h, "bf16 storage"): x and / or dy hold 2-byte bf16 elements; single-piece bf16 mode, 3x3 shapes on the
-// matrix-pipe path with rows a multiple of 32 wide; the gradient itself stays fp32 (fp32 accumulation, fp32 slabs, ordered reduce).
-extern "C" int uz_conv_bwd_weight_b16(const void* x, int Cin, int CinTot, const void* dy, int Cout, int CoutTot,
-                                      float* dw, int N, int H, int W, int ks, void* workspace, size_t workspace_bytes,
-                                      int x_b16, int dy_b16, float* slabs_out, void* stream) {
-    UZ_REQUIRE(uz::conv_np() == 1 && ks == 3 && W % 32 == 0 && uz_conv_route(2, Cin, Cout, N, H, W, ks) == 1,
-               "conv_bwd_weight_b16: bf16 storage needs uz_set_conv_math(3), a 3x3 shape on the matrix-pipe path and rows a multiple of 32 wide");
-    return conv_bwd_weight_impl(static_cast<const float*>(x), Cin, CinTot, static_cast<const float*>(dy), Cout, CoutTot, dw, nullptr, N, H, W, ks,
-                                nullptr, nullptr, workspace, workspace_bytes, 0, nullptr, 0, 0, slabs_out, stream, x_b16 != 0, dy_b16 != 0);
-}
-static int conv_bwd_weight_impl(const float* x, int Cin, int CinTot, const float* dy, int Cout, int CoutTot,
-                                float* dw, float* db, int N, int H, int W, int ks,
-                                const float* x_amax, const float* dy_amax, void* workspace, size_t workspace_bytes,
-                                int x_packed, const float* x_amax2, int seg_channels, int dy_packed, float* slabs_out, void* stream,
-                                int x_b16, int dy_b16) {
-    UZ_REQUIRE(ks == 1 || ks == 3, "conv_bwd_weight: kernel size %d unsupported", ks);
-    // slabs_out: the call stops behind its main kernel and leaves its uz_conv_bwd_weight_slabs() partial-sum slabs [S][ks*ks][Cout][Cin]
-    // there; uz_wgrad_reduce_table adds the slabs of MANY layers in one launch (the plans: one at the end of the backward tape
-    // instead of one or two reduction launches behind every weight gradient).  dw is not written, db must be NULL.
-    // (a depth window - 3 C view channels over a C-channel buffer - may leave slabs too: its table row carries C, and the table kernel
-    //  writes the Conv3d parameter layout exactly as this call's own reduction does)
-    UZ_REQUIRE(!slabs_out || (!db && uz_conv_bwd_weight_slabs(Cin, Cout, N, H, W, ks) > 0),
-               "conv_bwd_weight_ex: slabs_out on a call that writes no slabs (uz_conv_bwd_weight_slabs() == 0) or asks for a bias gradient");
-    const bool any_packed = x_packed || dy_packed;
-    UZ_REQUIRE(!any_packed || (uz_conv_route(2, Cin, Cout, N, H, W, ks) == 1 && uz::conv_np() == 2 && !(dy_packed && db)),
-               "conv_bwd_weight_ex: an operand in split storage, but this shape / math mode does not take the split-fp16 path (or a bias gradient was requested)");
-    UZ_REQUIRE((!x_packed || x_amax) && (!dy_packed || dy_amax), "conv_bwd_weight_ex: an operand in split storage needs the bound it was scaled from");
-    UZ_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv_bwd_weight: empty tensor");
-    UZ_REQUIRE(H < 1024 && W < 1024, "conv_bwd_weight: spatial size too large");
-    if (ks == 1 && uz::conv1x1_small_ok(Cin, Cout)) {                 // heads with 1, 2, 3, 4, 6 or 8 outputs, Cin <= 512 (conv1x1_small_ok): streaming VALU kernel; -2 cannot come back behind that check
-        UZ_REQUIRE(workspace && workspace_bytes >= uz::conv1x1_small_bwd_weight_ws(Cin, Cout, N, H, W), "conv_bwd_weight: workspace too small");
-        const int rc = uz::conv1x1_small_bwd_weight(x, Cin, CinTot, dy, Cout, CoutTot, dw, db, N, H, W, workspace, uz::S(stream));
-        if (rc != -2) return rc;
-    }
-    const WGeom g = pick_wgeom(Cin, Cout, N, H, W, ks / 2);
-    const size_t need = (size_t)g.S * g.SW * ks * ks * Cout * Cin * sizeof(float);
-    UZ_REQUIRE(workspace && workspace_bytes >= need, "conv_bwd_weight: workspace %zu < %zu bytes", workspace_bytes, need);
-    hipStream_t st = uz::S(stream);
+// the fp32 kernels (WG_FAST, WG_GENERIC): r.g.S * r.g.SW slabs into `slab`
+int wgrad_f32(const uz::WgradCall& c, const uz::WgradRoute& r, float* slab) {
+    const WGeom& g = r.g;
+    hipStream_t st = c.st;
     WgP p;
-    p.x = x; p.dy = dy; p.slab = slabs_out ? slabs_out : static_cast<float*>(workspace);
-    p.N = N; p.H = H; p.W = W; p.HW = H * W;
-    p.Cin = Cin; p.CinTot = CinTot; p.Cout = Cout; p.CoutTot = CoutTot;
+    p.x = c.x; p.dy = c.dy; p.slab = slab;
+    p.N = c.N; p.H = c.H; p.W = c.W; p.HW = c.H * c.W;
+    p.Cin = c.Cin; p.CinTot = c.CinTot; p.Cout = c.Cout; p.CoutTot = c.CoutTot;
     p.TW = g.TW; p.TH = g.TH; p.TB = g.TB; p.lgTW = uz::ilog2(g.TW); p.lgTH = uz::ilog2(g.TH);
     p.tilesX = g.tilesX; p.tilesY = g.tilesY; p.T = g.T; p.S = g.S;
     p.PW = g.PW; p.PSI = g.PSI; p.PS = g.PS; p.PSP = g.PS | 1;
@@ -758,68 +713,10 @@ static int conv_bwd_weight_impl(const float* x, int Cin, int CinTot, const float
         if (fold > smem) smem = fold;
     }
     const int grid = g.nCoT * g.nCiT * g.S;
-    int Stot = g.S * g.SW;
-    const bool thin = wgrad_thin_ok(Cin, Cout, N, H, W, ks);
-    if (thin) {                                   // 1..4 input channels: streaming reduction (same slab layout, ordered reduce below)
-        const int tiles_img = H / THIN_ROWS, total = N * tiles_img;
-        Stot = wgrad_thin_slabs(N, H);
-        const int per_wg = uz::ceil_div(total, Stot);
-        Stot = uz::ceil_div(total, per_wg);
-        UZ_REQUIRE(workspace_bytes >= (size_t)Stot * 9 * Cout * Cin * sizeof(float), "conv_bwd_weight: workspace too small for the thin-input path");
-        const dim3 tg(Stot, uz::ceil_div(Cout, THIN_CO));
-#define UZ_THIN(C_) hipLaunchKernelGGL(wgrad_thin_kernel<C_>, tg, dim3(256), 0, st, x, CinTot, dy, CoutTot, Cout, p.slab, N, H, W, tiles_img, per_wg)
-        if (Cin == 1) UZ_THIN(1); else if (Cin == 2) UZ_THIN(2); else if (Cin == 3) UZ_THIN(3); else UZ_THIN(4);
-#undef UZ_THIN
-    }
-    // The split-fp16 and the fast fp32 kernels address a whole tensor through one buffer resource (32-bit byte offsets): tensors
-    // of 2^30 elements or more take the generic fp32 kernel (64-bit pointers) instead of failing.
-    const bool huge = (size_t)N * CinTot * H * W >= (1ull << 30) || (size_t)N * CoutTot * H * W >= (1ull << 30);
-    UZ_REQUIRE(!(huge && g.fast), "conv_bwd_weight: a channel-slice view of a buffer of 2^30 elements or more is not supported by the tiled kernels");
-    const bool split_math = !thin && !huge && uz::wgrad_split_ok(Cin, Cout, N, H, W, ks);
-    //  the slab-count query sees the VIEW's channels, this dispatch the buffer's: a channel slice of a >= 2^30-element
-    // buffer leaves the split path here but not there - a caller that sized slabs_out from the query must not be handed more slabs
-    UZ_REQUIRE(!slabs_out || (split_math ? uz::wgrad_split_splits(Cin, Cout, N, H, W) : Stot) == uz_conv_bwd_weight_slabs(Cin, Cout, N, H, W, ks),
-               "conv_bwd_weight_ex: slabs_out was sized for %d slabs (uz_conv_bwd_weight_slabs), this call writes another number (a channel-slice view of a huge buffer?)",
-               uz_conv_bwd_weight_slabs(Cin, Cout, N, H, W, ks));
-    UZ_REQUIRE(!any_packed || split_math, "conv_bwd_weight_ex: split storage on a call that left the split-fp16 path");
-    UZ_REQUIRE(!(x_b16 || dy_b16) || (split_math && !db), "conv_bwd_weight_b16: bf16 storage on a call that left the matrix-pipe path");
-    if (split_math) {                              // large layers: split-fp16 matrix pipe (conv_wgrad_split.hip), same slab layout
-        Stot = uz::wgrad_split_splits(Cin, Cout, N, H, W);
-        const size_t slab_bytes = (size_t)Stot * 9 * Cout * Cin * sizeof(float);
-        constexpr size_t slot_bytes = uz::AMAX_FLOATS * sizeof(float);
-        UZ_REQUIRE(workspace_bytes >= slab_bytes + 2 * slot_bytes, "conv_bwd_weight: workspace too small for the split path");
-        if (uz::conv_np() == 2 && (!x_amax || !dy_amax)) {             // no bounds from the caller: measure them (stand-alone C-ABI path; the bf16 mode has no scales)
-            float* slots = reinterpret_cast<float*>(static_cast<char*>(workspace) + slab_bytes);
-            if (hipMemsetAsync(slots, 0, 2 * slot_bytes, st) != hipSuccess) return uz::fail("conv_bwd_weight: memset failed");
-            if (!x_amax) { if (int rc = uz::absmax_view(x, Cin, CinTot, N, H * W, slots, st)) return rc; x_amax = slots; }
-            if (!dy_amax) { if (int rc = uz::absmax_view(dy, Cout, CoutTot, N, H * W, slots + uz::AMAX_FLOATS, st)) return rc; dy_amax = slots + uz::AMAX_FLOATS; }
-        }
-        if (int rc = uz::wgrad_split(x, Cin, CinTot, dy, Cout, CoutTot, p.slab, N, H, W, Stot, x_amax, dy_amax, st, x_packed, x_amax2, seg_channels, dy_packed, x_b16, dy_b16)) return rc;
-    }
-#define UZ_WG_LAUNCH(KS_, WM_, WN_, PF_)                                                                         \
+#define UZ_WG_LAUNCH(KERN_)                                                                                      \
     do {                                                                                                         \
         static bool attr = false;                                                                                \
-        auto kern = wgrad_kernel<KS_, WM_, WN_, PF_>;                                                            \
-        if (!attr) {                                                                                             \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
-                return uz::fail("wgrad: cannot raise dynamic LDS limit");                                        \
-            attr = true;                                                                                         \
-        }                                                                                                        \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), smem, st, p);                                            \
-    } while (0)
-#define UZ_WG_PF(KS_, WM_, WN_) UZ_WG_LAUNCH(KS_, WM_, WN_, false)
-#define UZ_WG_TILE(KS_)                                                              \
-    do {                                                                             \
-        if (g.WM == 2 && g.WN == 2) UZ_WG_PF(KS_, 2, 2);                             \
-        else if (g.WM == 2) UZ_WG_PF(KS_, 2, 1);                                     \
-        else if (g.WN == 2) UZ_WG_PF(KS_, 1, 2);                                     \
-        else UZ_WG_PF(KS_, 1, 1);                                                    \
-    } while (0)
-    const bool fast = g.fast != 0;
-#define UZ_WG_FAST(WM_, WN_, THF_, TW_)                                                                            \
-    do {                                                                                                         \
-        static bool attr = false;                                                                                \
-        auto kern = wgrad_fast_kernel<WM_, WN_, THF_, TW_>;                                                      \
+        auto kern = KERN_;                                                                                       \
         if (!attr) {                                                                                             \
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) \
                 return uz::fail("wgrad: cannot raise dynamic LDS limit");                                        \
@@ -827,46 +724,140 @@ static int conv_bwd_weight_impl(const float* x, int Cin, int CinTot, const float
         }                                                                                                        \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), smem, st, p);                                             \
     } while (0)
+#define UZ_WG_TILE(KS_)                                                              \
+    do {                                                                             \
+        if (g.WM == 2 && g.WN == 2) UZ_WG_LAUNCH((wgrad_kernel<KS_, 2, 2, false>));  \
+        else if (g.WM == 2) UZ_WG_LAUNCH((wgrad_kernel<KS_, 2, 1, false>));          \
+        else if (g.WN == 2) UZ_WG_LAUNCH((wgrad_kernel<KS_, 1, 2, false>));          \
+        else UZ_WG_LAUNCH((wgrad_kernel<KS_, 1, 1, false>));                         \
+    } while (0)
 #define UZ_WG_FAST_T(THF_, TW_)                                                      \
     do {                                                                             \
-        if (g.WM == 2 && g.WN == 2) UZ_WG_FAST(2, 2, THF_, TW_);                     \
-        else if (g.WM == 2) UZ_WG_FAST(2, 1, THF_, TW_);                             \
-        else if (g.WN == 2) UZ_WG_FAST(1, 2, THF_, TW_);                             \
-        else UZ_WG_FAST(1, 1, THF_, TW_);                                            \
+        if (g.WM == 2 && g.WN == 2) UZ_WG_LAUNCH((wgrad_fast_kernel<2, 2, THF_, TW_>)); \
+        else if (g.WM == 2) UZ_WG_LAUNCH((wgrad_fast_kernel<2, 1, THF_, TW_>));      \
+        else if (g.WN == 2) UZ_WG_LAUNCH((wgrad_fast_kernel<1, 2, THF_, TW_>));      \
+        else UZ_WG_LAUNCH((wgrad_fast_kernel<1, 1, THF_, TW_>));                     \
     } while (0)
-    if (split_math || thin) {
-    } else if (fast) {
+    if (r.family == uz::WG_FAST) {
         if (g.TW == 32 && g.TH == 4) UZ_WG_FAST_T(4, 32);
         else if (g.TW == 32) UZ_WG_FAST_T(2, 32);
         else if (g.TW == 16) UZ_WG_FAST_T(4, 16);
         else UZ_WG_FAST_T(8, 8);
-    } else if (ks == 3) UZ_WG_TILE(3); else UZ_WG_TILE(1);
+    } else if (c.ks == 3) UZ_WG_TILE(3); else UZ_WG_TILE(1);
+#undef UZ_WG_LAUNCH
+#undef UZ_WG_TILE
+#undef UZ_WG_FAST_T
+    return 0;
+}
+
+// slabs_out: the call stops behind its main kernel and leaves its uz_conv_bwd_weight_slabs() partial-sum slabs [S][ks*ks][Cout][Cin]
+// there; uz_wgrad_reduce_table adds the slabs of MANY layers in one launch (the plans: one at the end of the backward tape
+// instead of one or two reduction launches behind every weight gradient).  dw is not written, db must be NULL.
+// (a depth window - 3 C view channels over a C-channel buffer - may leave slabs too: its table row carries C, and the table kernel
+//  writes the Conv3d parameter layout exactly as this call's own reduction does)
+int conv_bwd_weight(const uz::WgradCall& c, bool b16_entry = false) {
+    const int Cin = c.Cin, Cout = c.Cout, N = c.N, H = c.H, W = c.W, ks = c.ks;
+    hipStream_t st = c.st;
+    const uz::WgradRoute r = uz::wgrad_route(Cin, Cout, c.CinTot, c.CoutTot, N, H, W, ks);
+    const bool on_split = r.family >= uz::WG_SPLIT && r.split_eligible;       // uz_conv_route(2, ...) == 1
+    UZ_REQUIRE(!b16_entry || (uz::conv_np() == 1 && ks == 3 && W % 32 == 0 && on_split),
+               "conv_bwd_weight_b16: bf16 storage needs uz_set_conv_math(3), a 3x3 shape on the matrix-pipe path and rows a multiple of 32 wide");
+    UZ_REQUIRE(ks == 1 || ks == 3, "conv_bwd_weight: kernel size %d unsupported", ks);
+    const bool valid = Cin > 0 && Cout > 0 && N > 0 && H > 0 && W > 0;
+    UZ_REQUIRE(!c.slabs_out || (!c.db && valid && r.view_slabs > 0),
+               "conv_bwd_weight_ex: slabs_out on a call that writes no slabs (uz_conv_bwd_weight_slabs() == 0) or asks for a bias gradient");
+    const bool any_packed = c.x_packed || c.dy_packed;
+    UZ_REQUIRE(!any_packed || (on_split && uz::conv_np() == 2 && !(c.dy_packed && c.db)),
+               "conv_bwd_weight_ex: an operand in split storage, but this shape / math mode does not take the split-fp16 path (or a bias gradient was requested)");
+    UZ_REQUIRE((!c.x_packed || c.x_amax) && (!c.dy_packed || c.dy_amax), "conv_bwd_weight_ex: an operand in split storage needs the bound it was scaled from");
+    UZ_REQUIRE(valid, "conv_bwd_weight: empty tensor");
+    UZ_REQUIRE(H < 1024 && W < 1024, "conv_bwd_weight: spatial size too large");
+    if (r.family == uz::WG_HEAD) {                // heads with 1, 2, 3, 4, 6 or 8 outputs, Cin <= 512 (conv1x1_small_ok): streaming VALU kernel
+        UZ_REQUIRE(c.workspace && c.workspace_bytes >= uz::conv1x1_small_bwd_weight_ws(Cin, Cout, N, H, W), "conv_bwd_weight: workspace too small");
+        return uz::conv1x1_small_bwd_weight(c.x, Cin, c.CinTot, c.dy, Cout, c.CoutTot, c.dw, c.db, N, H, W, c.workspace, st);
+    }
+    UZ_REQUIRE(c.workspace && c.workspace_bytes >= r.f32_bytes, "conv_bwd_weight: workspace %zu < %zu bytes", c.workspace_bytes, r.f32_bytes);
+    float* slab = c.slabs_out ? c.slabs_out : static_cast<float*>(c.workspace);
+    const int Stot = r.slabs;
+    if (r.family == uz::WG_THIN) { if (int rc = wgrad_thin(c, r, slab)) return rc; }
+    UZ_REQUIRE(!(r.huge && r.g.fast), "conv_bwd_weight: a channel-slice view of a buffer of 2^30 elements or more is not supported by the tiled kernels");
+    const bool split_math = r.family == uz::WG_SPLIT;
+    // a caller that sized slabs_out from the query must not be handed more slabs
+    UZ_REQUIRE(!c.slabs_out || Stot == r.view_slabs,
+               "conv_bwd_weight_ex: slabs_out was sized for %d slabs (uz_conv_bwd_weight_slabs), this call writes another number (a channel-slice view of a huge buffer?)", r.view_slabs);
+    UZ_REQUIRE(!any_packed || split_math, "conv_bwd_weight_ex: split storage on a call that left the split-fp16 path");
+    UZ_REQUIRE(!(c.x_b16 || c.dy_b16) || (split_math && !c.db), "conv_bwd_weight_b16: bf16 storage on a call that left the matrix-pipe path");
+    if (split_math) {                              // large layers: split-fp16 matrix pipe (conv_wgrad_split.hip), same slab layout
+        const float* x_amax = c.x_amax; const float* dy_amax = c.dy_amax;
+        const size_t slab_bytes = (size_t)Stot * 9 * Cout * Cin * sizeof(float);
+        constexpr size_t slot_bytes = uz::AMAX_FLOATS * sizeof(float);
+        UZ_REQUIRE(c.workspace_bytes >= slab_bytes + 2 * slot_bytes, "conv_bwd_weight: workspace too small for the split path");
+        if (uz::conv_np() == 2 && (!x_amax || !dy_amax)) {             // no bounds from the caller: measure them (stand-alone C-ABI path; the bf16 mode has no scales)
+            float* slots = reinterpret_cast<float*>(static_cast<char*>(c.workspace) + slab_bytes);
+            if (hipMemsetAsync(slots, 0, 2 * slot_bytes, st) != hipSuccess) return uz::fail("conv_bwd_weight: memset failed");
+            if (!x_amax) { if (int rc = uz::absmax_view(c.x, Cin, c.CinTot, N, H * W, slots, st)) return rc; x_amax = slots; }
+            if (!dy_amax) { if (int rc = uz::absmax_view(c.dy, Cout, c.CoutTot, N, H * W, slots + uz::AMAX_FLOATS, st)) return rc; dy_amax = slots + uz::AMAX_FLOATS; }
+        }
+        if (int rc = uz::wgrad_split(c, r, slab, x_amax, dy_amax)) return rc;
+    } else if (r.family != uz::WG_THIN) {
+        if (int rc = wgrad_f32(c, r, slab)) return rc;
+    }
     if (int rc = uz::check_launch("wgrad_kernel")) return rc;
-    if (slabs_out) return 0;
+    if (c.slabs_out) return 0;
     const int n = ks * ks * Cout * Cin;
     int rgrid = uz::ceil_div(n, 256);
     if (rgrid > 4096) rgrid = 4096;
     int RG = 1;
     if (Stot > 64) {
         RG = 32;
-        hipLaunchKernelGGL(wgrad_reduce_groups, dim3(rgrid, uz::ceil_div(Stot, RG)), dim3(256), 0, st, p.slab, Stot, RG, n);
+        hipLaunchKernelGGL(wgrad_reduce_groups, dim3(rgrid, uz::ceil_div(Stot, RG)), dim3(256), 0, st, slab, Stot, RG, n);
         if (int rc = uz::check_launch("wgrad_reduce_groups")) return rc;
     }
     const int fgrid = uz::ceil_div(Cout * Cin, 256);
     // a depth window (csrc/vol.hip: Conv3d = the 2-D kernel over D slices with 3 C contraction channels on a C-channel buffer) is the
     // only call with more view channels than the buffer has: its gradient leaves in the Conv3d parameter layout
-    const int volC = (ks == 3 && Cin == 3 * CinTot) ? CinTot : 0;
-    if (ks == 3) hipLaunchKernelGGL(wgrad_reduce_kernel<9>, dim3(fgrid, 9), dim3(256), 0, st, p.slab, dw, Stot, RG, Cout, Cin, volC);
-    else hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3(fgrid, 1), dim3(256), 0, st, p.slab, dw, Stot, RG, Cout, Cin, 0);
+    const int volC = (ks == 3 && Cin == 3 * c.CinTot) ? c.CinTot : 0;
+    if (ks == 3) hipLaunchKernelGGL(wgrad_reduce_kernel<9>, dim3(fgrid, 9), dim3(256), 0, st, slab, c.dw, Stot, RG, Cout, Cin, volC);
+    else hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3(fgrid, 1), dim3(256), 0, st, slab, c.dw, Stot, RG, Cout, Cin, 0);
     if (int rc = uz::check_launch("wgrad_reduce_kernel")) return rc;
-    if (db) {
+    if (c.db) {
         // the slab workspace is free again after the reduction above; it holds the fp64 partials
-        UZ_REQUIRE(workspace_bytes >= (size_t)Cout * CSB * sizeof(double), "conv_bwd_weight: workspace too small for the bias gradient");
-        double* part = static_cast<double*>(workspace);
-        hipLaunchKernelGGL(channel_sum_partial, dim3(Cout, CSB), dim3(256), 0, st, dy, CoutTot, N, H * W, part);
+        UZ_REQUIRE(c.workspace_bytes >= (size_t)Cout * CSB * sizeof(double), "conv_bwd_weight: workspace too small for the bias gradient");
+        double* part = static_cast<double*>(c.workspace);
+        hipLaunchKernelGGL(channel_sum_partial, dim3(Cout, CSB), dim3(256), 0, st, c.dy, c.CoutTot, N, H * W, part);
         if (int rc = uz::check_launch("channel_sum_partial")) return rc;
-        hipLaunchKernelGGL(channel_sum_final, dim3(Cout), dim3(64), 0, st, part, db);
+        hipLaunchKernelGGL(channel_sum_final, dim3(Cout), dim3(64), 0, st, part, c.db);
         if (int rc = uz::check_launch("channel_sum_final")) return rc;
     }
     return 0;
+}
+}  // namespace
+// ... with either operand in split storage (include/uz_api.h, round 4): only on the split-fp16 path, bias gradient not available
+// (db reads dy as fp32).
+extern "C" int uz_conv_bwd_weight_ex(const float* x, int Cin, int CinTot, const float* dy, int Cout, int CoutTot,
+                                     float* dw, float* db, int N, int H, int W, int ks,
+                                     const float* x_amax, const float* dy_amax, void* workspace, size_t workspace_bytes,
+                                     int x_packed, const float* x_amax2, int seg_channels, int dy_packed, float* slabs_out, void* stream) {
+    uz::WgradCall c;
+    c.x = x; c.Cin = Cin; c.CinTot = CinTot; c.dy = dy; c.Cout = Cout; c.CoutTot = CoutTot; c.dw = dw; c.db = db;
+    c.N = N; c.H = H; c.W = W; c.ks = ks; c.x_amax = x_amax; c.dy_amax = dy_amax; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.x_packed = x_packed; c.x_amax2 = x_amax2; c.seg_channels = seg_channels; c.dy_packed = dy_packed; c.slabs_out = slabs_out; c.st = uz::S(stream);
+    return conv_bwd_weight(c);
+}
+extern "C" int uz_conv_bwd_weight(const float* x, int Cin, int CinTot, const float* dy, int Cout, int CoutTot,
+                                  float* dw, float* db, int N, int H, int W, int ks,
+                                  const float* x_amax, const float* dy_amax,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    return uz_conv_bwd_weight_ex(x, Cin, CinTot, dy, Cout, CoutTot, dw, db, N, H, W, ks, x_amax, dy_amax, workspace, workspace_bytes, 0, nullptr, 0, 0, nullptr, stream);
+}
+// bf16 STORAGE (include/uz_api.h, "bf16 storage"): x and / or dy hold 2-byte bf16 elements; single-piece bf16 mode, 3x3 shapes on the
+// matrix-pipe path with rows a multiple of 32 wide; the gradient itself stays fp32 (fp32 accumulation, fp32 slabs, ordered reduce).
+extern "C" int uz_conv_bwd_weight_b16(const void* x, int Cin, int CinTot, const void* dy, int Cout, int CoutTot,
+                                      float* dw, int N, int H, int W, int ks, void* workspace, size_t workspace_bytes,
+                                      int x_b16, int dy_b16, float* slabs_out, void* stream) {
+    uz::WgradCall c;
+    c.x = static_cast<const float*>(x); c.Cin = Cin; c.CinTot = CinTot; c.dy = static_cast<const float*>(dy); c.Cout = Cout; c.CoutTot = CoutTot; c.dw = dw;
+    c.N = N; c.H = H; c.W = W; c.ks = ks; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.x_b16 = x_b16 != 0; c.dy_b16 = dy_b16 != 0; c.slabs_out = slabs_out; c.st = uz::S(stream);
+    return conv_bwd_weight(c, true);
 }

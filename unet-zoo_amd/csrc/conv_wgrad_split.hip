@@ -406,10 +406,10 @@ extern "C" int uz_get_wgrad_target(void) {
     return env > 0 ? env : (g_wgs_target > 0 ? g_wgs_target : 256);
 }
 // number of pixel splits: at most one split per pixel tile
-int wgrad_split_splits(int Cin, int Cout, int N, int H, int W) {
-    const int ct = chan_tile(Cin, Cout);
+int wgrad_split_splits(int Cin, int Cout, int N, int H, int W, int& tw, int& ct) {
+    ct = chan_tile(Cin, Cout);
     const int nt = ceil_div(Cout, ct) * ceil_div(Cin, ct);
-    const int tw = tile_w(W);
+    tw = tile_w(W);
     const int T = N * ceil_div(H, PT / tw) * (W / tw);
     const int target = uz_get_wgrad_target();
     // one workgroup per CU either way (the 32-channel kernel's 166 VGPRs allow no second one: 512 splits measured 6 % slower).  (192
@@ -465,21 +465,18 @@ static int launch_wgrad(const WS& p, int grid, hipStream_t st, int xpk, int dpk,
     return dpk ? launch_wgrad_np<TWv, CT, 2, 0, 1>(p, grid, st) : launch_wgrad_np<TWv, CT, 2, 0, 0>(p, grid, st);
 }
 
-int wgrad_split(const float* x, int Cin, int CinTot, const float* dy, int Cout, int CoutTot, float* slab,
-                int N, int H, int W, int S, const float* x_amax, const float* dy_amax, hipStream_t st,
-                int x_packed, const float* x_amax2, int seg_channels, int dy_packed, int x_b16, int dy_b16) {
+int wgrad_split(const WgradCall& c, const WgradRoute& r, float* slab, const float* x_amax, const float* dy_amax) {
+    const int Cin = c.Cin, Cout = c.Cout, N = c.N, H = c.H, W = c.W, S = r.slabs, tw = r.tw, ct = r.ct;
     WS p;
-    p.x_amax2 = (x_packed && seg_channels > 0) ? x_amax2 : nullptr; p.seg_channels = seg_channels;
-    UZ_REQUIRE(!x_packed || seg_channels == 0 || (x_amax2 && seg_channels < Cin), "wgrad_split: the second scale segment needs its bound");
-    p.x = x; p.dy = dy; p.slab = slab; p.x_amax = x_amax; p.dy_amax = dy_amax; p.stamps = debug_stamps; p.flags = dev_flags_ptr();
-    p.N = N; p.H = H; p.W = W; p.HW = H * W; p.Cin = Cin; p.CinTot = CinTot; p.Cout = Cout; p.CoutTot = CoutTot;
-    const int tw = tile_w(W), ct = chan_tile(Cin, Cout);
+    p.x_amax2 = (c.x_packed && c.seg_channels > 0) ? c.x_amax2 : nullptr; p.seg_channels = c.seg_channels;
+    UZ_REQUIRE(!c.x_packed || c.seg_channels == 0 || (c.x_amax2 && c.seg_channels < Cin), "wgrad_split: the second scale segment needs its bound");
+    p.x = c.x; p.dy = c.dy; p.slab = slab; p.x_amax = x_amax; p.dy_amax = dy_amax; p.stamps = debug_stamps; p.flags = dev_flags_ptr();
+    p.N = N; p.H = H; p.W = W; p.HW = H * W; p.Cin = Cin; p.CinTot = c.CinTot; p.Cout = Cout; p.CoutTot = c.CoutTot;
     p.tilesX = W / tw; p.tilesY = ceil_div(H, PT / tw); p.T = N * p.tilesX * p.tilesY; p.S = S;
     p.nCoT = ceil_div(Cout, ct); p.nCiT = ceil_div(Cin, ct);
-    UZ_REQUIRE((size_t)N * CinTot * p.HW < (1ull << 30) && (size_t)N * CoutTot * p.HW < (1ull << 30), "wgrad_split: tensor too large for 32-bit offsets (the dispatcher routes such tensors to the fp32 kernel)");
     const int grid = p.nCoT * p.nCiT * S;
-    if (ct == 32) return tw == 16 ? launch_wgrad<16, 32>(p, grid, st, x_packed, dy_packed, x_b16, dy_b16) : launch_wgrad<32, 32>(p, grid, st, x_packed, dy_packed, x_b16, dy_b16);
-    return tw == 16 ? launch_wgrad<16, 64>(p, grid, st, x_packed, dy_packed, x_b16, dy_b16) : launch_wgrad<32, 64>(p, grid, st, x_packed, dy_packed, x_b16, dy_b16);
+    if (ct == 32) return tw == 16 ? launch_wgrad<16, 32>(p, grid, c.st, c.x_packed, c.dy_packed, c.x_b16, c.dy_b16) : launch_wgrad<32, 32>(p, grid, c.st, c.x_packed, c.dy_packed, c.x_b16, c.dy_b16);
+    return tw == 16 ? launch_wgrad<16, 64>(p, grid, c.st, c.x_packed, c.dy_packed, c.x_b16, c.dy_b16) : launch_wgrad<32, 64>(p, grid, c.st, c.x_packed, c.dy_packed, c.x_b16, c.dy_b16);
 }
 
 }  // namespace uz

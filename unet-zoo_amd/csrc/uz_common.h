@@ -184,45 +184,85 @@ static inline bool bytes_overlap(const void* a_, const void* b_, long long bytes
     return !(a + (uintptr_t)bytes <= b || b + (uintptr_t)bytes <= a);
 }
 
-// conv_split.hip: 3x3 forward / data gradient on the fp16 matrix pipe with two-piece split operands (fp32-accurate)
-bool conv_split_ok(int Kc, int Mc, int N, int H, int W, int ks, int dgrad);
-size_t conv_split_workspace(int Kc, int Mc, int N, int H, int W);
-int splitk_reduce(const float* slab, int ksplit, const float* bias, float* y, int Mc, int McTot, int N, int HW, int relu, int accumulate,
-                  float* y_amax, hipStream_t st);      // conv_mfma.hip
-int conv_split(const float* x, int Kc, int KcTot, const float* w, int wCi, const float* bias,
-               float* y, int Mc, int McTot, int N, int H, int W, int dgrad, int relu, int accumulate,
-               const float* x_amax, const float* w_amax, float* y_amax, void* workspace, const void* packed_w, float* bn_partials, hipStream_t st);
-// round-4 options of the split path
-struct SplitOpts {
+// ---- How a convolution call is routed, and the call itself.  Forward and data gradient: Kc contraction, Mc output channels.
+enum { CONV_F32 = 0, CONV_SPLIT = 1, CONV_STREAM = 2, STREAM_HEAD = 1, STREAM_THIN = 2 };     // ConvRoute::family = what uz_conv_route returns; ::stream: 1x1 head | 1..4 input channels
+struct Geom { int TW, TH, TB, PW, PSI, PS, tilesX, tilesY, tilesB; };       // fp32 kernel: pixel tile and its LDS patch
+struct SplitGeom {                  // matrix-pipe kernel (conv_split.hip)
+    int tw, cot;                    // tile width (16: 16 x 16 tiles, 256 threads; 32: 16 x 32 tiles, 512 threads), output channels per tile
+    int nChunks, rows;              // chunks of the contraction, rows of the packed weight image
+    size_t image_bytes, ws_bytes;   // ... its bytes (all above depend on Kc, Mc and W alone: split_image); workspace = bound slots + image + slabs
+    int parts, cps, partials;       // workgroups one tile's chunk loop is shared out over (no empty parts), chunks per part; rows of per-channel partials a fused epilogue writes (0: split loop)
+};
+struct ConvRoute {
+    int family = CONV_F32, stream = 0;
+    SplitGeom s = {};               // CONV_SPLIT
+    Geom g = {}; int msub = 0, jmax = 0, ksplit = 1, cps = 0;      // CONV_F32: tile, 32-channel sub-tiles per tile, pixel sub-tiles per wave, split of the chunk loop, chunks per part
+    size_t smem = 0, ws_bytes = 0;  // workspace of the family (CONV_F32: the split-K slabs)
+};
+// streaming = false: the matrix kernels' route (a head with a ReLU epilogue, a thin-input layer with a pre-packed weight image, uz_conv_workspace).
+// Pure: reads the math mode and the policy's getenv statics.  Any integers are safe; the entry points refuse empty shapes behind it.
+ConvRoute conv_route(int dgrad, int Kc, int Mc, int N, int H, int W, int ks, bool streaming = true);
+SplitGeom split_geom(int Kc, int Mc, int N, int H, int W);         // conv_split.hip
+struct ConvCall {
+    const float* x = nullptr; int Kc = 0, KcTot = 0;               // input view (dy for a data gradient)
+    const float* w = nullptr; int wCi = 0; const float* bias = nullptr;     // PyTorch [Cout][Cin][ks][ks] parameter and its Cin
+    float* y = nullptr; int Mc = 0, McTot = 0;                      // output view (dx)
+    int N = 0, H = 0, W = 0, ks = 0, dgrad = 0, relu = 0, accumulate = 0;
+    // x_amax / w_amax: device scalars bounding |x| and |w| (any upper bound within ~2^10 of the true maximum keeps full
+    // accuracy); NULL = measure here (one extra pass over the tensor: the stand-alone C-ABI path, the model plans pass
+    // bounds that the producing kernels maintain).  y_amax (nullable): atomic max of |y| for the next consumer.
+    const float* x_amax = nullptr; const float* w_amax = nullptr; float* y_amax = nullptr;
+    void* workspace = nullptr; size_t workspace_bytes = 0;
+    const void* packed_w = nullptr;                                 // weight image packed once per step (uz_conv_pack_weights)
+    float* bn_partials = nullptr;                                   // fused BatchNorm statistics / the folded epilogue's partial rows
+    // slabs_only: stop after the split-K main kernel and leave the partial sums [ksplit][N][Mc][HW] in slabs_out, or at the start of
+    // the workspace (the caller's BatchNorm adds them, uz_bn_relu_fwd_slabs / uz_bn_relu_bwd_ex); only legal where the fp32 route's ksplit > 1.
+    float* slabs_out = nullptr; bool slabs_only = false; hipStream_t st = nullptr;
+    // round-4 options of the split path
     int x_packed = 0;                       // the input operand (x, or dy for a data gradient) is split storage (split_f16.h)
-    const float* x_amax2 = nullptr;         // ... whose channels from seg_channels on were scaled from this bound instead of x_amax
-    int seg_channels = 0;
+    const float* x_amax2 = nullptr; int seg_channels = 0;      // ... whose channels from seg_channels on were scaled from this bound instead of x_amax
     int mk = 0;                             // epilogue: 0 plain, 1 ReLU mask of the producing unit (mask = its activation), 2 BatchNorm-backward reduction
     const float* mask = nullptr; int maskCtot = 0;
-    const float* mk_save = nullptr;         // mk == 2: [4][C] {mean, rstd, alpha, beta'} of the producing unit (uz_bn_relu_fwd_ex)
-    int mk_relu = 1;
+    const float* mk_save = nullptr; int mk_relu = 1;           // mk == 2: [4][C] {mean, rstd, alpha, beta'} of the producing unit (uz_bn_relu_fwd_ex)
     // bf16 STORAGE (single-piece bf16 mode only, unsplit chunk loops): the input operand / the output tensor hold 2-byte bf16 elements
     int x_b16 = 0, y_b16 = 0;
     // round 6: x is the pre-normalisation output of the Conv -> BatchNorm -> ReLU unit in front (fp32) and aff its [4][Kc] {mean, rstd, alpha, beta'} table:
     // the forward convolution's staging applies the unit's BatchNorm + ReLU itself (x_amax = the bound of the APPLIED activation)
     const float* aff = nullptr; int aff_relu = 0;
 };
-int conv_split_ex(const float* x, int Kc, int KcTot, const float* w, int wCi, const float* bias,
-                  float* y, int Mc, int McTot, int N, int H, int W, int dgrad, int relu, int accumulate,
-                  const float* x_amax, const float* w_amax, float* y_amax, void* workspace, const void* packed_w, float* bn_partials, hipStream_t st,
-                  const SplitOpts& o);
-int conv_split_dgrad_relu(const float* dy, int Kc, int KcTot, const float* w, int wCi, float* dx, int Mc, int McTot, int N, int H, int W, int accumulate,
-                          const float* dy_amax, const float* w_amax, float* dx_amax, void* workspace, const void* packed_w,
-                          const float* a, int aCtot, float* partials, hipStream_t st);   // conv_split.hip
-int conv_split_bn_partials(int Kc, int Mc, int N, int H, int W);
+// conv_split.hip: 3x3 forward / data gradient on the fp16 matrix pipe with two-piece split operands (fp32-accurate)
+bool conv_split_ok(int Kc, int Mc, int N, int H, int W, int ks, int dgrad);
+int conv_split(const ConvCall& c, const ConvRoute& r);
+int splitk_reduce(const float* slab, int ksplit, const float* bias, float* y, int Mc, int McTot, int N, int HW, int relu, int accumulate,
+                  float* y_amax, hipStream_t st);      // conv_mfma.hip
 
-// conv_wgrad_split.hip: 3x3 weight gradient on the fp16 matrix pipe with two-piece split operands
+// ---- weight gradient
+enum { WG_HEAD, WG_THIN, WG_SPLIT, WG_FAST, WG_GENERIC };   // streaming 1x1 head | 1..4 input channels | matrix pipe | fp32, one buffer resource | fp32, 64-bit pointers
+struct WGeom { int TW, TH, TB, PW, PSI, PS, tilesX, tilesY, tilesB, T, S, nCoT, nCiT, WM, WN, WK, pf, fast, SW; };   // SW: slabs per pixel split
+struct WgradRoute {
+    int family = WG_GENERIC;
+    int slabs = 0, view_slabs = 0;  // partial-sum slabs [ks*ks][Cout][Cin] the call writes before its reduction (0: WG_HEAD) | ... a call on a buffer of the view's size would
+    size_t ws_bytes = 0;            // uz_conv_bwd_weight_workspace: enough for every family the shape is eligible for, and the bias gradient
+    WGeom g = {}; size_t f32_bytes = 0;     // the fp32 geometry, of every shape: its slab bytes enter ws_bytes, and the entry point asks every call for them
+    int per_wg = 0;                 // WG_THIN: row pairs per workgroup
+    bool split_eligible = false, huge = false;      // wgrad_split_ok | the BUFFER has 2^30 elements or more: such a call leaves the matrix pipe
+    int tw = 0, ct = 0;             // split_eligible: tile width, channel tile (conv_wgrad_split.hip)
+};
+// Cin, Cout: the views' channels; CinTot, CoutTot: the buffers' (a query passes the views' for both).  Pure, like conv_route().
+WgradRoute wgrad_route(int Cin, int Cout, int CinTot, int CoutTot, int N, int H, int W, int ks);
+struct WgradCall {
+    const float* x = nullptr; int Cin = 0, CinTot = 0; const float* dy = nullptr; int Cout = 0, CoutTot = 0;
+    float* dw = nullptr; float* db = nullptr; int N = 0, H = 0, W = 0, ks = 0;
+    const float* x_amax = nullptr; const float* dy_amax = nullptr;
+    void* workspace = nullptr; size_t workspace_bytes = 0;
+    int x_packed = 0; const float* x_amax2 = nullptr; int seg_channels = 0; int dy_packed = 0;      // *_packed: operand in split storage
+    int x_b16 = 0, dy_b16 = 0;                                                                        // *_b16: operand stored as bf16 (single-piece mode)
+    float* slabs_out = nullptr; hipStream_t st = nullptr;
+};
+// conv_wgrad_split.hip: 3x3 weight gradient on the fp16 matrix pipe with two-piece split operands; r.slabs slabs into `slab`
 bool wgrad_split_ok(int Cin, int Cout, int N, int H, int W, int ks);
-int wgrad_split_splits(int Cin, int Cout, int N, int H, int W);
-int wgrad_split(const float* x, int Cin, int CinTot, const float* dy, int Cout, int CoutTot, float* slab,
-                int N, int H, int W, int S, const float* x_amax, const float* dy_amax, hipStream_t st,
-                int x_packed = 0, const float* x_amax2 = nullptr, int seg_channels = 0, int dy_packed = 0,       // *_packed: operand in split storage
-                int x_b16 = 0, int dy_b16 = 0);                                                                    // *_b16: operand stored as bf16 (single-piece mode)
+int wgrad_split_splits(int Cin, int Cout, int N, int H, int W, int& tw, int& ct);       // ... and the tile width and channel tile
+int wgrad_split(const WgradCall& c, const WgradRoute& r, float* slab, const float* x_amax, const float* dy_amax);
 
 // conv1x1_small.hip: streaming VALU kernels for 1x1 convolutions with 1, 2, 3, 4, 6 or 8 outputs (conv1x1_small_ok says exactly which
 // shapes; -2 = output count not instantiated, unreachable behind that check)
