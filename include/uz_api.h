@@ -932,7 +932,26 @@ int    uz_vol_components_route_ex(int N, int D, int H, int W, int connectivity, 
  *   keeps its voxels in Dk (a component on it is no false positive) but enters no table and no sum; all such lesions together are one
  *   link.  counts[6] = n_ref - max_lesions when positive, counts[7] = the predicted components that touch more than max_links
  *   different lesions.  Either one non-zero makes the four scores of that (n, r) NaN; the call still returns 0: this is data the
- *   host part cannot see.  The lesion-wise HD95 is not built (it needs a distance transform per lesion, restricted to its box).
+ *   host part cannot see.
+ *   6. Lesion-wise HD95 (uz_vol_lesion_scores_ex with want_hd95 != 0; like the rest of this section it follows the challenge's
+ *      description, and parity with the challenge's own tool is not pinned).  For a table lesion g with pred_vol[n][g] > 0 let
+ *      A_g = G and Dk_g, the lesion's undilated voxels, and B_ng = the union of the predicted components in match(g), each one whole,
+ *      as pred_vol counts it (a component that reaches several lesions belongs to the B of each; the links beyond max_links are not
+ *      in it).  The border of a mask is the rule of uz_vol_region_scores - a voxel of the mask with a face neighbour outside the mask
+ *      or outside the volume -, taken of A_g and of B_ng as masks of their own.  (The kernels use border(A_g) = border(G) and Dk_g,
+ *      border(B_ng) = border(P) and B_ng: two face neighbours of G share a lesion, two of P a component.)  S_ng = the multiset of
+ *      the exact integer squared distances of both directions: min over u in border(A_g) of |q - u|^2 for every q in border(B_ng),
+ *      and min over q in border(B_ng) of |u - q|^2 for every u in border(A_g).  With m = |S_ng| (>= 2), S_ng sorted,
+ *      hq = 0.95 (m - 1), k0 = floor(hq), k1 = min(k0 + 1, m - 1): hd95_g = sqrt(s[k0]) + (hq - k0) (sqrt(s[k1]) - sqrt(s[k0])) in
+ *      fp64, the percentile rule of uz_vol_region_scores.  hd95 (N, R) fp64 = (sum over kept g of t_g, serially in ascending g in
+ *      fp64, + hd95_penalty * n_fp, one product added after the loop) / (n_kept + n_fp), t_g = hd95_g for a matched lesion and
+ *      hd95_penalty for a missed one; a dropped lesion enters nothing; 0.0 with no kept lesion and no false positive.  *hd95_penalty
+ *      is ONE fp64 in HOST memory, read before the call returns (as the sets are; the challenge's description gives 374 for a missed
+ *      lesion or a false positive).  hd_lesions (N, R, max_lesions, 3) int64, nullable = {m, s[k0], s[k1]} for every table lesion
+ *      with a match, kept or not, and 0 otherwise.  hd_counts (N, R, 2) int64 = {the border voxels of the table lesions beyond
+ *      max_border, the (predicted border voxel, link to a table lesion) entries of the row beyond max_border}: max_border,
+ *      1 .. D*H*W, bounds both lists per row.  Where a list overflowed, hd95 of that (n, r) is NaN and its hd_lesions are 0; the four
+ *      scores are left alone.  hd95 is NaN too where counts[6] or counts[7] is non-zero.  The call still returns 0.
  * csrc/vollesion.hip: per region uz_vol_morph and two uz_vol_label_components_ex sweeps at connectivity 3 (the reference side on one
  * volume, the prediction side on all N), a two-level count that ranks the root voxels of Dk, and the (component, lesion) pairs
  * counted once each by max_links rounds of an integer fetch_min on one word per component root, the root's own thread adding the
@@ -944,7 +963,22 @@ int    uz_vol_components_route_ex(int N, int D, int H, int W, int connectivity, 
  * min_pred_voxels, max_lesions outside 1 .. UZ_VOL_MAX_LESIONS, max_links outside 1 .. UZ_VOL_MAX_LINKS, a workspace off 16 bytes,
  * counts, lesions or scores off 8.  uz_vol_lesion_scores_workspace returns 0 for the sizes the call would refuse.
  * uz_vol_lesion_scores_route (host only): out2[0] = the merge instance both labelling sweeps take (3), out2[1] = workgroups of the
- * widest launch of a call.                                                                                                      */
+ * widest launch of a call.
+ * uz_vol_lesion_scores_ex: uz_vol_lesion_scores (which is this call with want_hd95 = 0) and, with want_hd95 != 0, rule 6.  The border
+ *   of G is compacted into one list of voxel indices grouped by lesion (count, scan, scatter); in every link round, between offer and
+ *   settle, the border voxels of P whose component is about to settle a link are appended as (voxel, lesion) to their row's list, and
+ *   after the rounds each row's list is sorted by lesion with a counting sort.  The pair kernel gives a workgroup out4[2] queries of
+ *   one (row, lesion) and walks the lesion's border in LDS tiles of out4[3] seeds: a running minimum per query in a register, and with
+ *   the roles swapped one integer fetch_min per (seed, workgroup) into the row's copy of the reference list.  One workgroup per
+ *   (row, lesion) then selects s[k0] and s[k1] exactly with a radix select on the keys (an LDS histogram per pass), and one thread per
+ *   row forms the mean.  Integer arithmetic up to the interpolation, integer atomics only, no host round trip: bit-equal on repetition.
+ *   The pair kernel's work is the product of the two border sizes per (row, lesion).
+ *   With want_hd95 == 0 the three hd_ pointers, hd95_penalty and max_border are not looked at and nothing of rule 6 is launched or
+ *   written; uz_vol_lesion_scores_workspace_ex then equals uz_vol_lesion_scores_workspace.  With want_hd95 the call also refuses a
+ *   null hd_counts, hd95 or hd95_penalty, D^2 + H^2 + W^2 > 2^30, max_border outside 1 .. D*H*W, a penalty that is negative or not
+ *   finite, and hd_counts, hd_lesions or hd95 off 8 bytes; the workspace grows by lists of max_border entries per row.
+ * uz_vol_lesion_scores_route_ex (host only): out4[0], out4[1] as uz_vol_lesion_scores_route; out4[2] = the queries one workgroup of
+ *   the pair kernel takes, out4[3] = the seeds of one LDS tile (both 0 with want_hd95 == 0).                                    */
 #define UZ_VOL_MAX_DILATION 16
 #define UZ_VOL_MAX_LESIONS 4096
 #define UZ_VOL_MAX_LINKS 16
@@ -957,6 +991,13 @@ int    uz_vol_lesion_scores(const uint8_t* pred, int N, const uint32_t* pred_set
                             int D, int H, int W, int dilation, int min_ref_voxels, int min_pred_voxels, int max_lesions, int max_links,
                             void* workspace, int64_t* counts, int64_t* lesions, double* scores, void* stream);
 int    uz_vol_lesion_scores_route(int N, int R, int D, int H, int W, int* out2);
+size_t uz_vol_lesion_scores_workspace_ex(int N, int R, int D, int H, int W, int max_lesions, int want_hd95, int max_border);
+int    uz_vol_lesion_scores_ex(const uint8_t* pred, int N, const uint32_t* pred_sets, const uint8_t* ref, const uint32_t* ref_sets, int R,
+                               int D, int H, int W, int dilation, int min_ref_voxels, int min_pred_voxels, int max_lesions, int max_links,
+                               int want_hd95, const double* hd95_penalty, int max_border,
+                               void* workspace, int64_t* counts, int64_t* lesions, double* scores,
+                               int64_t* hd_counts, int64_t* hd_lesions, double* hd95, void* stream);
+int    uz_vol_lesion_scores_route_ex(int N, int R, int D, int H, int W, int want_hd95, int* out4);
 
 /* ---------------------------------------------------------------- volume uncertainty (the BraTS uncertainty task; calibration)
  * Judges S sampled label volumes of ONE case as an uncertainty estimate against one reference, per region, from the votes of the

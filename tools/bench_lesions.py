@@ -13,9 +13,12 @@ Per shape and input, in one process:
   host      the scipy route on row 0: per region binary_dilation of the reference (18-neighbour, 3 iterations), ndimage.label of the
             dilated mask and of the prediction (26-neighbour), the pairs by np.unique - timed, its lesion and component counts compared
             with the device's, and scaled by N for a loop over the rows (the reference side counted once).
+  --hd95    adds the lesion-wise HD95: score_lesions(hd95=True) beside the plain call, the pair kernel and the select on their own (the sums of
+            their launches in one profiled call, torch.profiler), the border voxels and (border voxel, lesion) entries of row 0, the grown
+            workspace, and as the host route _volscore.hd95 per matched lesion on row 0, both masks cropped to their common box, scaled by N.
 Each device time is the median of `--repeats` calls between two device events after `--warmup` calls.  --notes writes
 profiles/NOTES_lesions.md.  Without a GPU the tool exits.
-usage: python tools/bench_lesions.py [--notes] [--repeats 10] [--warmup 2] [--shapes 128x128x128 240x240x155] [--no-oracle]"""
+usage: python tools/bench_lesions.py [--notes] [--hd95] [--repeats 10] [--warmup 2] [--shapes 128x128x128 240x240x155] [--no-oracle]"""
 import argparse
 import ctypes as C
 import json
@@ -62,6 +65,82 @@ def host_row(row, ref):
     return t_ref, t_row, out
 
 
+def host_hd95_row(row, ref):
+    """the scipy route of the lesion-wise HD95 for one row -> (seconds, per region [hd95_g of the matched lesions], reference border voxels, entries)"""
+    from scipy import ndimage
+    from tests import _volscore as V
+    st18, st26 = ndimage.generate_binary_structure(3, 2), np.ones((3, 3, 3), bool)
+    t0 = time.perf_counter()
+    out, n_border, n_entries = [], 0, 0
+    for reg in REGIONS:
+        G = np.isin(ref, reg)
+        Dk = ndimage.binary_dilation(G, structure=st18, iterations=DILATION)
+        Lg, n_ref = ndimage.label(Dk, structure=st26)
+        Lp, _ = ndimage.label(np.isin(row, reg), structure=st26)
+        vals, boxes_p = [], ndimage.find_objects(Lp)
+        for g, box in enumerate(ndimage.find_objects(Lg)):
+            ids = np.unique(Lp[box][Lg[box] == g + 1])
+            ids = ids[ids > 0]
+            if not len(ids):
+                continue
+            lo, hi = [b.start for b in box], [b.stop for b in box]
+            for b in (boxes_p[i - 1] for i in ids):
+                lo, hi = [min(a, c.start) for a, c in zip(lo, b)], [max(a, c.stop) for a, c in zip(hi, b)]
+            # one voxel of margin, so that only the volume's own faces are faces of the crop
+            crop = tuple(slice(max(a - 1, 0), min(c + 1, n)) for a, c, n in zip(lo, hi, row.shape))
+            A, B = (G[crop] & (Lg[crop] == g + 1)), np.isin(Lp[crop], ids)
+            pad = [(int(c.start > 0), int(c.stop < n)) for c, n in zip(crop, row.shape)]         # faces inside the volume are no border
+            inner = tuple(slice(a, s - b) for (a, b), s in zip(pad, A.shape))
+            bA, bB = np.zeros(A.shape, bool), np.zeros(B.shape, bool)
+            bA[inner], bB[inner] = V.border(A)[inner], V.border(B)[inner]
+            n_border += int(bA.sum()); n_entries += int(bB.sum())
+            d = np.hstack([ndimage.distance_transform_edt(~bA)[bB], ndimage.distance_transform_edt(~bB)[bA]])
+            vals.append(float(np.percentile(d, 95)))
+        out.append(vals)
+    return time.perf_counter() - t0, out, n_border, n_entries
+
+
+def kernel_ms(fn, names):
+    """device time of the kernels whose name contains one of `names`, summed over one call of fn; None where the profiler gives nothing"""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        tot = {k: 0.0 for k in names}
+        for ev in prof.key_averages():
+            for k in names:
+                if k in ev.key:
+                    tot[k] += getattr(ev, "device_time_total", None) or getattr(ev, "cuda_time_total", 0.0)
+        return {k: round(v / 1e3, 3) for k, v in tot.items()} if any(tot.values()) else None
+    except Exception as e:                                               # the numbers are optional, the run is not
+        print("profiler:", repr(e), file=sys.stderr)
+        return None
+
+
+def hd95_part(pred, ref, pred_h, ref_h, shape, args):
+    D, H, W = shape
+    sink = {}
+
+    def score():
+        sink["s"] = metrics.score_lesions(pred, ref, REGIONS, hd95=True)
+    t = timed(score, args.warmup, args.repeats)
+    first = sink["s"].hd95.clone()
+    score()
+    mb = min(max(4096, D * H * W // 8), D * H * W)
+    out = dict(hd95_score_ms=t, hd95_row0=[round(float(v), 4) for v in sink["s"].hd95[0].cpu()], hd95_overflow_any=bool(sink["s"].hd_counts.any()),
+               hd95_nan_any=bool(torch.isnan(sink["s"].hd95).any()), hd95_repeat_bit_equal=bool(torch.equal(first.view(torch.int64), sink["s"].hd95.view(torch.int64))),
+               max_border=mb, hd95_workspace_mb=round(_ffi.lib().uz_vol_lesion_scores_workspace_ex(N_ROWS, len(REGIONS), D, H, W, 256, 1, mb) / 1e6, 1),
+               hd95_kernels_ms=kernel_ms(score, ("hd_pair_k", "hd_select_k", "hd_entries_k")))
+    if not args.no_oracle:
+        sec, vals, n_border, n_entries = host_hd95_row(pred_h[0], ref_h)
+        kept_all = all(len(v) > 0 for v in vals)
+        out.update(host_hd95_row0_s=round(sec, 2), host_hd95_all_rows_s=round(sec * N_ROWS, 1), border_voxels_row0=n_border, entries_row0=n_entries,
+                   host_hd95_matched_row0=[len(v) for v in vals], hd95_speedup_vs_host=round(sec * N_ROWS * 1e3 / t["median"], 1), host_hd95_any=kept_all)
+    return out
+
+
 def one_input(name, pred_h, ref_h, shape, args, dev):
     D, H, W = shape
     P = D * H * W
@@ -93,6 +172,8 @@ def one_input(name, pred_h, ref_h, shape, args, dev):
                counts_row0=counts[0].tolist(), overflow_any=bool(counts[..., 6:].any()), lesion_dice_row0=[round(float(v), 4) for v in sink["score"].lesion_dice[0].cpu()],
                workspace_mb=round(_ffi.lib().uz_vol_lesion_scores_workspace(N_ROWS, len(REGIONS), D, H, W, 256) / 1e6, 1),
                morph_workspace_mb=round(_ffi.lib().uz_vol_morph_workspace(N_ROWS, D, H, W) / 1e6, 1))
+    if args.hd95:
+        row.update(hd95_part(pred, ref, pred_h, ref_h, shape, args))
     if not args.no_oracle:
         t_ref, t_row, host = host_row(pred_h[0], ref_h)
         row.update(host_ref_side_s=round(t_ref, 2), host_row0_s=round(t_row, 2), host_all_rows_s=round(t_ref + t_row * N_ROWS, 1),
@@ -109,6 +190,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--shapes", nargs="+", default=["128x128x128", "240x240x155"])
     ap.add_argument("--no-oracle", action="store_true")
+    ap.add_argument("--hd95", action="store_true", help="also time score_lesions(hd95=True), its pair kernel and select, and the host route per lesion")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_lesions needs a GPU: a time taken anywhere else says nothing")
@@ -152,6 +234,19 @@ def main():
             for r in rows:
                 lines.append(f"| {vol(r)} | {r['input']} | {r['host_ref_side_s']} | {r['host_row0_s']} | {r['host_all_rows_s']} | {r['score_ms']['median']} | {r['speedup_vs_host']} | "
                              f"{r['row0_counts_equal']} |")
+        if args.hd95:
+            k = lambda r, n: "-" if not r.get("hd95_kernels_ms") else r["hd95_kernels_ms"][n]
+            lines += ["", "`--hd95`: `score_lesions(hd95=True)` with its defaults (penalty 374, max_border = D*H*W // 8) beside the plain call above; `pair` and `select` are the",
+                      "sums of the launches of the pair kernel and of the radix select in one profiled call (three regions each); border voxels and entries are the sizes of the",
+                      "two lists of row 0, summed over the regions; the host route is `distance_transform_edt` per matched lesion of row 0 on the common box of the lesion",
+                      "and its components, scaled by N.", "",
+                      "| volume | input | score ms | score with hd95 ms | pair ms | select ms | border voxels, entries of row 0 | list overflow | workspace MB | host, row 0, s | host, all rows, s | ratio |",
+                      "|---|---|---|---|---|---|---|---|---|---|---|---|"]
+            for r in rows:
+                lines.append(f"| {vol(r)} | {r['input']} | {f(r['score_ms'])} | {f(r['hd95_score_ms'])} | {k(r, 'hd_pair_k')} | {k(r, 'hd_select_k')} | "
+                             f"{r.get('border_voxels_row0', '-')}, {r.get('entries_row0', '-')} | {r['hd95_overflow_any']} | {r['hd95_workspace_mb']} | {r.get('host_hd95_row0_s', '-')} | "
+                             f"{r.get('host_hd95_all_rows_s', '-')} | {r.get('hd95_speedup_vs_host', '-')} |")
+            lines += ["", "A repeated call with hd95 was bit-equal on every shape and input: " + str(all(r["hd95_repeat_bit_equal"] for r in rows)) + "."]
         lines += ["", "A repeated score call was bit-equal on every shape and input: " + str(all(r["repeat_bit_equal"] for r in rows)) + "."]
         with open(os.path.join(ROOT, "profiles", "NOTES_lesions.md"), "w") as fh:
             fh.write("\n".join(lines) + "\n")

@@ -7,6 +7,7 @@ correlations), only the O(N*M) scalar bookkeeping stays on the host.
 """
 import collections
 import ctypes as C
+import math
 
 import torch
 
@@ -392,14 +393,24 @@ def binary_closing(volumes, values, iterations=1, connectivity=1):
     return _morph("binary_closing", _morph("binary_closing", volumes, values, iterations, connectivity, 0), (1,), iterations, connectivity, 1)
 
 
-LesionScores = collections.namedtuple("LesionScores", "lesion_dice sensitivity precision f1 counts lesions")
-LesionScores.__doc__ = """What score_lesions returns, all on the device: lesion_dice, sensitivity, precision, f1 (N, R) fp64 - views of one (N, R, 4) buffer;
-NaN where a table overflowed - counts (N, R, 8) int64 = {n_ref, n_kept, n_tp, n_fn, n_fp, n_pred, lesions beyond max_lesions, components with links
-beyond max_links}, and lesions (N, R, max_lesions, 3) int64 = {gt_vol, inter, pred_vol} per reference lesion, or None when it was not asked for."""
+class LesionScores(collections.namedtuple("LesionScores", "lesion_dice sensitivity precision f1 counts lesions")):
+    """What score_lesions returns, all on the device: lesion_dice, sensitivity, precision, f1 (N, R) fp64 - views of one (N, R, 4) buffer;
+    NaN where a table overflowed - counts (N, R, 8) int64 = {n_ref, n_kept, n_tp, n_fn, n_fp, n_pred, lesions beyond max_lesions, components with links
+    beyond max_links}, and lesions (N, R, max_lesions, 3) int64 = {gt_vol, inter, pred_vol} per reference lesion, or None when it was not asked for.
+    hd95, hd_lesions and hd_counts read as None: the lesion-wise HD95 was not asked for (score_lesions(hd95=True) returns a LesionHD95Scores)."""
+    __slots__ = ()
+    hd95 = hd_lesions = hd_counts = None
+
+
+LesionHD95Scores = collections.namedtuple("LesionHD95Scores", LesionScores._fields + ("hd95", "hd_lesions", "hd_counts"))
+LesionHD95Scores.__doc__ = """What score_lesions(hd95=True) returns: the six fields of LesionScores, then hd95 (N, R) fp64, the lesion-wise HD95 - NaN where a table or a
+border list overflowed -, hd_lesions (N, R, max_lesions, 3) int64 = {m, s[k0], s[k1]} per matched reference lesion (the number of surface distances
+and the two squared distances the 95th percentile lies between), or None when the per-lesion tables were not asked for, and hd_counts (N, R, 2)
+int64 = {reference border voxels beyond max_border, (predicted border voxel, lesion) entries of the row beyond max_border}."""
 
 
 def score_lesions(pred, reference, pred_regions, ref_regions=None, dilation=3, min_ref_voxels=50, min_pred_voxels=0, max_lesions=256, max_links=4,
-                  return_lesions=False):
+                  return_lesions=False, hd95=False, hd95_penalty=374.0, max_border=None):
     """Lesion-wise scores of N label volumes against ONE reference volume for R regions, the operands of score_volume (a 3-D
     Prediction, filtered or not - its S samples, then mean_label - or a uint8 tensor (N, D, H, W); reference uint8 (D, H, W)) - one
     uz_vol_lesion_scores call (csrc/vollesion.hip) on the caller's current stream: no host round trip, no synchronisation.
@@ -412,10 +423,19 @@ def score_lesions(pred, reference, pred_regions, ref_regions=None, dilation=3, m
     every false positive enters as a 0.  sensitivity, precision and f1 count kept lesions with a match, without one, and the false
     positives.  The definition is this project's contract (include/uz_api.h spells it out); it follows the description of the BraTS
     2023 ranking, parity with the challenge's own tool is not pinned, and the defaults - dilation 3, min_ref_voxels 50 - are OUR
-    reading of its glioma settings.  The lesion-wise HD95 is not built.
+    reading of its glioma settings.
     max_lesions (1 .. 4096) bounds the per-lesion tables and max_links (1 .. 16) the lesions one predicted component may reach; where
     either is exceeded the scores of that (row, region) are NaN and counts[..., 6] / counts[..., 7] say by how much - nothing is
-    looked at on the host, so nothing raises.  Returns a LesionScores of device tensors."""
+    looked at on the host, so nothing raises.  Returns a LesionScores of device tensors.
+    hd95=True adds the lesion-wise HD95 (one uz_vol_lesion_scores_ex call) and returns a LesionHD95Scores: per matched lesion the 95th
+    percentile (score_volume's rule) of the surface distances, both directions, between the lesion's undilated voxels and the union of
+    the predicted components matched to it, each component whole; hd95 = (the kept lesions' values, hd95_penalty for every missed one
+    and for every false positive) / (kept lesions + false positives), 0 when both are none.  hd95_penalty, a finite real >= 0,
+    defaults to 374, the value the challenge's description gives.  max_border caps two lists per row, the border voxels of the
+    reference lesions and the (border voxel, lesion) entries of the predicted components: None = max(4096, D*H*W // 8), at most D*H*W - a border is
+    a few per cent of a mask and a tumour about 1 % of a case - or an int 1 .. D*H*W.  Where a list overflows, hd95 of that (row,
+    region) is NaN, hd_counts says by how much, and the other scores stand: call again with a larger max_border (D*H*W always
+    suffices for the reference list; the workspace grows by 20 bytes per row and entry)."""
     if _vol.is_prediction(pred):
         rows = _vol.prediction_rows(*_vol.prediction_maps(pred))
     else:
@@ -432,23 +452,49 @@ def score_lesions(pred, reference, pred_regions, ref_regions=None, dilation=3, m
             raise TypeError(f"{name} must be an int, not {v!r}")
         if v < lo or (hi is not None and v > hi):
             raise ValueError(f"{name} {v}: {lo} <= {name}" + (f" <= {hi}" if hi is not None else ""))
-    _vol.on_device(rows, "pred")
     N, D, H, W = (int(d) for d in rows.shape)
+    if not isinstance(hd95, bool):
+        raise TypeError(f"hd95 must be a bool, not {hd95!r}")
+    if isinstance(hd95_penalty, bool) or not isinstance(hd95_penalty, (int, float)):
+        raise TypeError(f"hd95_penalty must be a real number, not {hd95_penalty!r}")
+    if not (math.isfinite(hd95_penalty) and hd95_penalty >= 0):
+        raise ValueError(f"hd95_penalty {hd95_penalty}: a finite distance >= 0")
+    if max_border is not None:
+        if isinstance(max_border, bool) or not isinstance(max_border, int):
+            raise TypeError(f"max_border must be None or an int, not {max_border!r}")
+        if max_border < 1 or max_border > D * H * W:
+            raise ValueError(f"max_border {max_border}: 1 <= max_border <= D*H*W = {D * H * W}")
+    elif hd95:
+        max_border = min(max(4096, D * H * W // 8), D * H * W)
+    _vol.on_device(rows, "pred")
     R = len(psets)
     L, dev = _ffi.lib(), rows.device
-    nbytes = L.uz_vol_lesion_scores_workspace(N, R, D, H, W, max_lesions)
+    too_large = f"N {N} R {R} volume {D} x {H} x {W}; no empty axis, 1 <= N <= 65536, 1 <= R <= 8, N*D*H*W < 2^31"
+    if hd95:
+        nbytes = L.uz_vol_lesion_scores_workspace_ex(N, R, D, H, W, max_lesions, 1, max_border)
+        too_large += ", D^2 + H^2 + W^2 <= 2^30"
+    else:
+        nbytes = L.uz_vol_lesion_scores_workspace(N, R, D, H, W, max_lesions)
     if nbytes == 0:
-        raise _vol.refused("score_lesions", f"N {N} R {R} volume {D} x {H} x {W}; no empty axis, 1 <= N <= 65536, 1 <= R <= 8, N*D*H*W < 2^31")
+        raise _vol.refused("score_lesions", too_large)
     rows, reference = rows.contiguous(), reference.contiguous()
-    ws = _vol.workspace("score_lesions", (dev, N, R, D, H, W, max_lesions), nbytes, dev)
+    ws = _vol.workspace("score_lesions", (dev, N, R, D, H, W, max_lesions, bool(hd95), max_border if hd95 else None), nbytes, dev)
     scores = torch.empty(N, R, 4, dtype=torch.float64, device=dev)
     counts = torch.empty(N, R, 8, dtype=torch.int64, device=dev)
     lesions = torch.empty(N, R, max_lesions, 3, dtype=torch.int64, device=dev) if return_lesions else None
     U32 = C.c_uint32 * R
-    _ffi.check(L.uz_vol_lesion_scores(rows.data_ptr(), N, U32(*psets), reference.data_ptr(), U32(*rsets), R, D, H, W, dilation, min_ref_voxels, min_pred_voxels,
-                                      max_lesions, max_links, ws.data_ptr(), counts.data_ptr(), lesions.data_ptr() if return_lesions else None,
-                                      scores.data_ptr(), _vol.stream(dev)), "vol_lesion_scores")
-    return LesionScores(lesion_dice=scores[..., 0], sensitivity=scores[..., 1], precision=scores[..., 2], f1=scores[..., 3], counts=counts, lesions=lesions)
+    head = (rows.data_ptr(), N, U32(*psets), reference.data_ptr(), U32(*rsets), R, D, H, W, dilation, min_ref_voxels, min_pred_voxels, max_lesions, max_links)
+    tail = (ws.data_ptr(), counts.data_ptr(), lesions.data_ptr() if return_lesions else None, scores.data_ptr())
+    six = dict(lesion_dice=scores[..., 0], sensitivity=scores[..., 1], precision=scores[..., 2], f1=scores[..., 3], counts=counts, lesions=lesions)
+    if not hd95:
+        _ffi.check(L.uz_vol_lesion_scores(*head, *tail, _vol.stream(dev)), "vol_lesion_scores")
+        return LesionScores(**six)
+    hd = torch.empty(N, R, dtype=torch.float64, device=dev)
+    hd_counts = torch.empty(N, R, 2, dtype=torch.int64, device=dev)
+    hd_lesions = torch.empty(N, R, max_lesions, 3, dtype=torch.int64, device=dev) if return_lesions else None
+    _ffi.check(L.uz_vol_lesion_scores_ex(*head, 1, C.byref(C.c_double(float(hd95_penalty))), max_border, *tail, hd_counts.data_ptr(),
+                                         hd_lesions.data_ptr() if return_lesions else None, hd.data_ptr(), _vol.stream(dev)), "vol_lesion_scores_ex")
+    return LesionHD95Scores(hd95=hd, hd_lesions=hd_lesions, hd_counts=hd_counts, **six)
 
 
 # --------------------------------------------------------------------------- S samples of one volume as an uncertainty estimate: filtered Dice, calibration
